@@ -8,7 +8,12 @@ torch.distributed.run, one rank per GPU) every rank bootstraps its own batch aga
 key -- no collective on the data path (weak scaling); the only collectives are the barrier and the
 max-over-ranks of the timed region.
 
-Prints ONE JSON line (rank 0) with the contract fields plus
+A plain run sets up, warms up, times --steps steps and prints ONE JSON line (rank 0) with the contract fields (metric, value, unit,
+higher_is_better, dtype, ms_per_step = milliseconds of one timed step, ...) and nothing else.  --dump-outputs DIR writes the outputs of the last
+timed step to DIR/programmable_bootstrap_out.npy (float64 torus values; the inputs are seeded, identical from run to run).
+
+With --full the line also carries the other legs, each run after the timed region (the CPU baseline and the decrypt check of the first step's
+outputs, max_phase_error_log2, before it):
   roofline     : the dominant kernel (pbs_kernel) against the roof that binds it, FP64 vector issue: SURVEY.md 8(d)'s FLOP model
                  (171,008 FLOP per CMUX step x n steps x B) over the kernel's average launch duration, measured live with hipEvents on
                  the launch stream, against the 78.6 TFLOP/s FP64 vector peak.  SURVEY 8(d)'s byte model (bootstrap key streamed once
@@ -495,6 +500,25 @@ def usable_cores():
     return n
 
 
+DUMP_NAME = "programmable_bootstrap_out"
+DUMP_BUDGET_BYTES = 60 * 10 ** 6     # all ranks' files together (the limit is 64 MB)
+
+
+def dump_outputs(out_dir, out, rank, world):
+    """--dump-outputs: the LWE samples [B][kN + 1] the timed path returned in its last step, as float64 torus values in [-1/2, 1/2) (signed 64-bit word / 2^64:
+    the top 53 bits of every word, the message and its noise included).  Rank r > 0 writes <name>_rank<r>.npy.  When all ranks' rows exceed the budget, a fixed
+    seeded sample of rows is written, in order, and its row indices beside it (<name>_rows.npy)."""
+    B, width = out.shape
+    rows = min(B, DUMP_BUDGET_BYTES // (world * width * 8))
+    pick = np.sort(np.random.default_rng(SEED).choice(B, rows, replace=False)) if rows < B else None
+    words = out if pick is None else out[pick]
+    suffix = "" if rank == 0 else "_rank%d" % rank
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, DUMP_NAME + suffix + ".npy"), words.view(np.int64).astype(np.float64) * 2.0 ** -64)
+    if pick is not None:
+        np.save(os.path.join(out_dir, DUMP_NAME + "_rows" + suffix + ".npy"), pick.astype(np.float64))
+
+
 def launch_ranks(n_gpus):
     """One rank per GPU under torch.distributed.run on this node (127.0.0.1, a free port), started as a child process with this script's own arguments.
     The child's stdout / stderr are inherited, so rank 0's JSON line is this command's JSON line; returns the child's exit code."""
@@ -524,6 +548,10 @@ def main():
     ap.add_argument("--no-lvl2", action="store_true", help="skip the configs[2] leg (4096 lvl2 bootstraps, ~2 s) and with it configs[3] / [4]")
     ap.add_argument("--no-callers", action="store_true", help="skip the gate leg (4096 x key switch + bootstrap at SET_1) and the vector_callers leg (256 radix integers: add + ReLU + LUT; ~6 s with its keys)")
     ap.add_argument("--no-configs34", action="store_true", help="skip the configs[3] / [4] legs (circuit bootstrap, FDFB, multi-value, Galois bootstrap: ~10 s; N > 1: the batches split over the ranks)")
+    ap.add_argument("--full", action="store_true", help="besides the headline figure, run every other leg of the line (decrypt check, roofline, external-product, "
+                                                       "lvl2 and configs[3] / [4] legs, gate, vector callers, latency, sustained rate, host buffers, replicas, CPU baseline); "
+                                                       "the --no-* options above apply to it")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write the bootstrap outputs of the last timed step to DIR/%s.npy" % DUMP_NAME)
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -573,12 +601,12 @@ def main():
     tv = host.torus_packing(lut, P["k"], P["N"])
     msgs = [host.double2torus((b % 4) / 8.0) for b in range(B)]
     cts = host.tlwe_samples(msgs, lk)
-    # the CPU leg runs FIRST (rank 0, N = 1): the GPU legs then form one contiguous block at the end of the run
+    # --full: the CPU leg runs FIRST (rank 0, N = 1): the GPU legs then form one contiguous block at the end of the run
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(P, bk, tv, cts[:64], args.cpu_seconds)
         cpu["ffnt_single_ms"] = ffnt_single_ms(P, bk, tv, cts[0])      # BASELINE.json configs[0]
-    elif world > 1 and not args.no_cpu_baseline:
+    elif args.full and world > 1 and not args.no_cpu_baseline:
         # N > 1: the same sample, shorter, on rank 0 while the other ranks sleep in a socket wait (a gloo side group: an RCCL barrier would keep one host
         # core per rank spinning under the CPU measurement) -- so that a SCALE line carries its own cpu_baseline
         side = dist.new_group(backend="gloo") if backend == "nccl" else None
@@ -605,14 +633,16 @@ def main():
     step()
     torch.cuda.synchronize()
 
-    # correctness of what is being timed: every output must decrypt to its LUT slot.  The reference asserts 2^58 on a
+    # --full: correctness of what is being timed: every output must decrypt to its LUT slot.  The reference asserts 2^58 on a
     # single sample (test/tests.c:1560); over thousands of SET_1 samples the noise tail (sigma ~ 2^55.5) brushes that
     # bound, so the batch criterion is: all within 2^60 (no wrong slot: slots are >= 2^61 apart) and >= 99.5 % within 2^58.
-    ph = host.tlwe_phase(ma.to_numpy(d_out), rk.extracted_lwe_key().s)
-    dist_t = np.abs((ph - lut[np.arange(B) % 4]).astype(np.int64).astype(np.float64))
-    err = dist_t.max()
-    if not (err < 2.0 ** 60 and (dist_t < 2.0 ** 58).mean() >= 0.995):
-        sys.exit("bench.py: bootstrap outputs do not decrypt (max phase error 2^%.1f)" % np.log2(err + 1))
+    err = None
+    if args.full:
+        ph = host.tlwe_phase(ma.to_numpy(d_out), rk.extracted_lwe_key().s)
+        dist_t = np.abs((ph - lut[np.arange(B) % 4]).astype(np.int64).astype(np.float64))
+        err = dist_t.max()
+        if not (err < 2.0 ** 60 and (dist_t < 2.0 ** 58).mean() >= 0.995):
+            sys.exit("bench.py: bootstrap outputs do not decrypt (max phase error 2^%.1f)" % np.log2(err + 1))
 
     # W untimed warm-up steps directly before the timed region (the host-side decrypt check above idles the GPU)
     for _ in range(args.warmup):
@@ -621,6 +651,38 @@ def main():
 
     # timed region: barrier + synchronize on both sides, MAX over ranks (mosfhet_amd/shard.py)
     elapsed = shard.timed_region(step, args.steps, sync=torch.cuda.synchronize, device=eng.device if backend == "nccl" else "cpu")
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, ma.to_numpy(d_outs[(turn[0] - 1) % len(streams)]), rank, world)
+
+    line = {
+        "metric": "programmable bootstraps/sec (whole node), N=1024 k=1",
+        "value": world * args.steps * B / elapsed,
+        "unit": "bootstraps/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": 1e3 * elapsed / args.steps,
+        "value_regime": "%d HIP stream(s): consecutive steps are independent batches and %s" % (
+            len(streams), "overlap at launch boundaries" if len(streams) > 1 else "run strictly back to back"),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": "synthetic",
+        "process_group": (backend if (world > 1 or force_dist) else None),
+        "config": {"workload": "batch of %d programmable bootstraps per GPU, SET_1 n=585 N=1024 k=1 l=2 Bg=2^8 "
+                               "(BASELINE.json configs[1])" % B,
+                   "batch_per_gpu": B, "streams": len(streams), "parallelism": "batch sharded over %d GPU(s), bootstrap key replicated, "
+                                                      "no collective on the data path" % world},
+        "full": args.full,
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        if world > 1 or force_dist:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
 
     # The dominant kernel, timed in the state the timed region left the chip in (round 3 timed it after the host-buffer leg and read 9 % above the
     # step it is the whole of): (a) alone -- launches back to back on ONE stream between two hipEvents, the launch duration the roofline is priced on;
@@ -750,28 +812,9 @@ def main():
         sustained = {"bootstraps_per_s": n_sus * B / (time.perf_counter() - t0), "steps": n_sus, "seconds": time.perf_counter() - t0}
 
     if rank == 0:
-        total = world * args.steps * B
-        line = {
-            "metric": "programmable bootstraps/sec (whole node), N=1024 k=1",
-            "value": total / elapsed,
-            "unit": "bootstraps/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": 1e3 * elapsed / args.steps,
-            "value_regime": "%d HIP stream(s): consecutive steps are independent batches and %s; roofline.kernel_ms is the launch alone (one stream, "
-                            "timed right after the timed region), roofline.kernel_ms_in_stream_regime the same launches as they ran for `value`: "
-                            "ms_per_step = launch span - overlap" % (len(streams), "overlap at launch boundaries" if len(streams) > 1 else "run strictly back to back"),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f64",
-            "data": "synthetic",
-            "process_group": (backend if (world > 1 or force_dist) else None),
-            "config": {"workload": "batch of %d programmable bootstraps per GPU, SET_1 n=585 N=1024 k=1 l=2 Bg=2^8 "
-                                   "(BASELINE.json configs[1])" % B,
-                       "batch_per_gpu": B, "streams": len(streams), "parallelism": "batch sharded over %d GPU(s), bootstrap key replicated, "
-                                                          "no collective on the data path" % world},
+        line["value_regime"] += ("; roofline.kernel_ms is the launch alone (one stream, timed right after the timed region), roofline.kernel_ms_in_stream_regime "
+                                 "the same launches as they ran for `value`: ms_per_step = launch span - overlap")
+        line.update({
             "roofline": {"bound": "fp64_valu", "achieved": achieved_tflops, "peak": FP64_VECTOR_PEAK_TFLOPS, "unit": "TFLOP/s",
                          "frac": achieved_tflops / FP64_VECTOR_PEAK_TFLOPS, "traffic": traffic,
                          "traffic_source": ("profiles/latest_traffic.json: rocprofv3 PMC passes of this very build (source hash matched), taken once and committed -- not measured in this run"
@@ -795,7 +838,7 @@ def main():
             "cpu_baseline": cpu,
             "max_phase_error_log2": float(np.log2(err + 1)),
             "host_buffer_rate_per_gpu": host_rate,
-        }
+        })
         print(json.dumps(line), flush=True)
     if world > 1 or force_dist:
         dist.barrier()                  # (rank 0 runs a few legs of its own after the last collective: the ranks leave together)
