@@ -11,6 +11,7 @@
 #include <string.h>
 
 #include <memory>
+#include <string>
 #include <type_traits>
 #include <vector>
 
@@ -274,9 +275,56 @@ extern "C" int mosfhet_hip_ctx_sync(mosfhet_hip_ctx_t ctx, void *stream) {
   return MOSFHET_HIP_OK;
 }
 
+// ---- gadget dispatch ----
+// Each launcher family states which instantiations it has as a predicate over (ring degree N, gadget length L, gadget base bits BG), next to its launcher:
+// BG > 0 is a compile-time gadget, BG = 0 the run-time-gadget instantiation of length L.  gadget_dispatch maps a launch's (l, Bg_bit) onto them.
+using GadgetSet = bool (*)(int N, int L, int BG);
+template <int X> using Int = std::integral_constant<int, X>;
+
 // Compile-time gadgets (2 x 2^8, 4 x 2^9) exist where a parameter set of the reference or of BASELINE.json runs them: N = 1024 and N = 2048.  At N = 4096 (the reference's
 // sets there have l = 1) they take the run-time-gadget instantiations -- same bits, fewer kernels (round 6 pruning: tools/kernel_table.py).
-template <class F> constexpr bool kCompileTimeGadgets = F::N != 4096;
+constexpr bool reference_gadget(int N, int L, int BG) { return N != 4096 && ((L == 2 && BG == 8) || (L == 4 && BG == 9)); }
+
+// Calls go(Int<L>, Int<BG>) with the family's compile-time gadget (l, Bg_bit) when it has one, else with <l, 0> when it has that, and returns what go returns;
+// otherwise fails with MOSFHET_HIP_EINVAL.
+// bounded: every key coefficient is the transform of torus words (|x| <= 2^63: keys this library transformed itself).  Only then may the compile-time 2 x 2^8
+// gadget at N = 1024 skip the reduction mod 1 in its rounding (pbs_kernel: kReduce).  Caller-supplied DFT objects -- non-owning key views, TRGSW_DFT selectors,
+// sums made with trgsw_DFT_add / _mul_addto -- carry no such bound and take the run-time-gadget instantiation, which reduces like the reference
+// (fft_processor_spqlios.c:155-165 reduces any double).
+template <int N, GadgetSet HAS, class Go>
+static int gadget_dispatch(int l, int Bg_bit, bool bounded, Go &&go) {
+  int rc = MOSFHET_HIP_OK;
+  auto take = [&](auto L, auto BG) {
+    if constexpr (HAS(N, L, BG)) {
+      const bool allowed = bounded || !(N == 1024 && L == 2 && BG == 8);
+      if (l == L && (BG == 0 || Bg_bit == BG) && allowed) {
+        rc = go(L, BG);
+        return true;
+      }
+    }
+    return false;
+  };
+  // every family's compile-time gadgets are among the first four; run-time gadgets: l = 1 .. 6 (what check_params admits)
+  if (take(Int<2>(), Int<8>()) || take(Int<4>(), Int<9>()) || take(Int<6>(), Int<7>()) || take(Int<1>(), Int<23>()) || take(Int<1>(), Int<0>()) ||
+      take(Int<2>(), Int<0>()) || take(Int<3>(), Int<0>()) || take(Int<4>(), Int<0>()) || take(Int<5>(), Int<0>()) || take(Int<6>(), Int<0>()))
+    return rc;
+  return fail(MOSFHET_HIP_EINVAL, "l = %d not instantiated", l);
+}
+
+// status of the launches just queued
+static int launched() {
+  HIP_TRY(hipGetLastError());
+  return MOSFHET_HIP_OK;
+}
+
+// A launch with `lds` bytes of dynamic LDS.  The attribute is set at every launch, like general_lds: it belongs to the current device's copy of the kernel
+// (several devices in one process: mosfhet_compat_multi.c).
+template <class K, class... A>
+static int launch_dyn_lds(K kernel, dim3 grid, dim3 block, size_t lds, hipStream_t s, const A &...args) {
+  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(kernel, grid, block, lds, s, args...);
+  return launched();
+}
 
 // k = 1 and N in {1024, 2048, 4096}: the tuned kernels.  Any other power-of-two ring up to 16384 and k <= 3: the general path (general_kernels.h).
 static bool general_ring(int k, int N) { return !(k == 1 && ring_ok(N)); }
@@ -439,7 +487,9 @@ struct EpKernelInfo { const char *name; int pipelined_by_default, scratch_bytes,
 static std::mutex g_ep_info_lock;
 static std::vector<EpKernelInfo> g_ep_info;   // every instantiation that has been asked about (mosfhet_hip_ep_kernel_info)
 template <class F, int L, int BG, bool CMUX>
-static bool ep_multiwave_pipelined_ok(const char *name) {
+static bool ep_multiwave_pipelined_ok() {
+  static_assert(std::is_same<F, Fft2048L>::value && !CMUX, "ep_pipelined_by_default: the one multi-wavefront transform that takes the pipelined loop");
+  static const std::string name = "external_product_kernel<Fft2048L, " + std::to_string(L) + ", " + std::to_string(BG) + ">";
   static std::atomic<int> verdict{-1};
   int v = verdict.load(std::memory_order_acquire);
   if (v < 0) {
@@ -447,7 +497,7 @@ static bool ep_multiwave_pipelined_ok(const char *name) {
     const int scratch = kernel_scratch_bytes(external_product_kernel<F, L, BG, CMUX, 0>);
     v = (scratch == 0 && !(e && e[0] == '0')) ? 1 : 0;
     std::lock_guard<std::mutex> hold(g_ep_info_lock);
-    if (verdict.load(std::memory_order_relaxed) < 0) g_ep_info.push_back(EpKernelInfo{name, 1, scratch, v});
+    if (verdict.load(std::memory_order_relaxed) < 0) g_ep_info.push_back(EpKernelInfo{name.c_str(), 1, scratch, v});
     verdict.store(v, std::memory_order_release);
   }
   return v == 1;
@@ -460,10 +510,10 @@ extern "C" int mosfhet_hip_set_ep_plain_loop(int on) {
 }
 
 template <class FF, int LL, int BB, bool CM>
-static void ep_go(const char *name, dim3 grid, dim3 block, hipStream_t s, const d2 *row, const d2 *tw, const uint64_t *d_in, uint64_t *d_out, int Bg_bit, int count, size_t key_stride,
+static void ep_go(dim3 grid, dim3 block, hipStream_t s, const d2 *row, const d2 *tw, const uint64_t *d_in, uint64_t *d_out, int Bg_bit, int count, size_t key_stride,
                   size_t in_stride, const uint64_t *d_in0, d2 *d_out_dft) {
   if constexpr (FF::THREADS > 64 && ep_pipelined_by_default<FF, LL, CM>()) {
-    if (!ep_multiwave_pipelined_ok<FF, LL, BB, CM>(name) || g_ep_plain_loop.load(std::memory_order_relaxed)) {
+    if (!ep_multiwave_pipelined_ok<FF, LL, BB, CM>() || g_ep_plain_loop.load(std::memory_order_relaxed)) {
       hipLaunchKernelGGL((external_product_kernel<FF, LL, BB, CM, 1>), grid, block, 0, s, row, tw, d_in, d_out, Bg_bit, count, key_stride, in_stride, d_in0, d_out_dft);
       return;
     }
@@ -471,59 +521,39 @@ static void ep_go(const char *name, dim3 grid, dim3 block, hipStream_t s, const 
   hipLaunchKernelGGL((external_product_kernel<FF, LL, BB, CM, 0>), grid, block, 0, s, row, tw, d_in, d_out, Bg_bit, count, key_stride, in_stride, d_in0, d_out_dft);
 }
 
+// external_product_ldskey_kernel (N = 1024 only): 2 x 2^8, 1 x 23; run-time gadgets l = 1, 2 -- one key entry of that length fits LDS next to eight teams'
+// transpose buffers
+constexpr bool ep_ldskey_gadgets(int, int L, int BG) { return BG == 0 ? L <= 2 : (L == 2 && BG == 8) || (L == 1 && BG == 23); }
+// external_product_kernel: the reference gadgets, 1 x 23; run-time gadgets l = 1 .. 6.  N = 2048, l = 4 (lvl2) runs on Fft2048L (launch_external_product).
+constexpr bool ep_gadgets(int N, int L, int BG) { return BG == 0 || reference_gadget(N, L, BG) || (L == 1 && BG == 23); }
+
+// bounded: see gadget_dispatch
 template <class F>
-static void launch_external_product(int l, int Bg_bit, hipStream_t s, const d2 *row, const d2 *tw, const uint64_t *d_in, uint64_t *d_out, int count, size_t key_stride,
-                                    size_t in_stride, const uint64_t *d_in0, d2 *d_out_dft, bool bounded) {
-  // bounded: every key coefficient is the transform of torus words (|x| <= 2^63: keys this library transformed itself).  Only then may the compile-time
-  // 2 x 2^8 gadget skip the reduction mod 1 in its rounding (pbs_kernel: kReduce).  Caller-supplied DFT objects -- non-owning key views, TRGSW_DFT
-  // selectors, sums made with trgsw_DFT_add / _mul_addto -- carry no such bound and take the run-time-gadget instantiation, which reduces like
-  // the reference (fft_processor_spqlios.c:155-165 reduces any double).
-  if (!bounded && l == 2 && Bg_bit == 8 && std::is_same<F, Fft1024>::value) Bg_bit = -8;   // (negative: routed to the <2, 0> instantiation below)
+static int launch_external_product(int l, int Bg_bit, hipStream_t s, const d2 *row, const d2 *tw, const uint64_t *d_in, uint64_t *d_out, int count, size_t key_stride,
+                                   size_t in_stride, const uint64_t *d_in0, d2 *d_out_dft, bool bounded) {
   const int cap = resident_teams(F::THREADS);
-  if constexpr (std::is_same<F, Fft1024>::value) {
-    // one key entry for the whole batch at N = 1024, l <= 2: the entry fits LDS next to eight teams' transpose buffers (external_product_ldskey_kernel)
-    if (key_stride == 0 && l <= 2 && count >= 64) {
+  if constexpr (F::N == 1024) {
+    // one key entry for the whole batch (external_product_ldskey_kernel)
+    if (key_stride == 0 && ep_ldskey_gadgets(F::N, l, 0) && count >= 64) {
       const int wgs = (count + 7) / 8, cus = cap / 8;
       const dim3 grid((unsigned)(wgs < cus ? wgs : cus)), block(512);
-#define EPL_GO(LL, BB)                                                                                                                                    \
-  do {                                                                                                                                                    \
-    if (d_in0) hipLaunchKernelGGL((external_product_ldskey_kernel<LL, BB, true>), grid, block, 0, s, row, tw, d_in, d_out, Bg_bit, count, in_stride, d_in0, d_out_dft);   \
-    else hipLaunchKernelGGL((external_product_ldskey_kernel<LL, BB, false>), grid, block, 0, s, row, tw, d_in, d_out, Bg_bit, count, in_stride, d_in0, d_out_dft);      \
-  } while (0)
-      if (l == 2 && Bg_bit == 8) EPL_GO(2, 8);
-      else if (l == 1 && Bg_bit == 23) EPL_GO(1, 23);
-      else if (l == 1) EPL_GO(1, 0);
-      else { if (Bg_bit < 0) Bg_bit = -Bg_bit; EPL_GO(2, 0); }
-#undef EPL_GO
-      return;
+      return gadget_dispatch<F::N, ep_ldskey_gadgets>(l, Bg_bit, bounded, [&](auto L, auto BG) {
+        if (d_in0) hipLaunchKernelGGL((external_product_ldskey_kernel<L, BG, true>), grid, block, 0, s, row, tw, d_in, d_out, Bg_bit, count, in_stride, d_in0, d_out_dft);
+        else hipLaunchKernelGGL((external_product_ldskey_kernel<L, BG, false>), grid, block, 0, s, row, tw, d_in, d_out, Bg_bit, count, in_stride, d_in0, d_out_dft);
+        return launched();
+      });
     }
   }
-  const bool unbounded_2x8 = Bg_bit < 0;
-  if (unbounded_2x8) Bg_bit = -Bg_bit;
   const dim3 grid((unsigned)(count < cap ? count : cap)), block(F::THREADS);
-#define EP_GO_F(FF, LL, BB)                                                                                                                                        \
-  do {                                                                                                                                                             \
-    if (d_in0) ep_go<FF, LL, BB, true>("external_product_kernel<" #FF ", " #LL ", " #BB ", cmux>", grid, block, s, row, tw, d_in, d_out, Bg_bit, count, key_stride, in_stride, d_in0, d_out_dft); \
-    else ep_go<FF, LL, BB, false>("external_product_kernel<" #FF ", " #LL ", " #BB ">", grid, block, s, row, tw, d_in, d_out, Bg_bit, count, key_stride, in_stride, d_in0, d_out_dft);        \
-  } while (0)
-#define EP_GO(LL, BB) EP_GO_F(F, LL, BB)
-  if constexpr (std::is_same<F, Fft2048>::value) {
+  return gadget_dispatch<F::N, ep_gadgets>(l, Bg_bit, bounded, [&](auto L, auto BG) {
     // N = 2048, l = 4 (lvl2): rows two at a time with the pass twiddles in LDS and, outside the CMUX form, the pipelined unit loop
     // (external_product_kernel: kPairs / kPipe; bit-identical; lvl2: 0.437 against 0.492 ms per 16,384 units in a same-box A/B), guarded by ep_go.
-    if (l == 4 && Bg_bit == 9) { EP_GO_F(Fft2048L, 4, 9); return; }
-    if (l == 4) { EP_GO_F(Fft2048L, 4, 0); return; }   // (other even lengths: not measured)
-  }
-  if (kCompileTimeGadgets<F> && l == 2 && Bg_bit == 8 && !unbounded_2x8) { if constexpr (kCompileTimeGadgets<F>) EP_GO(2, 8); }
-  else if (kCompileTimeGadgets<F> && l == 4 && Bg_bit == 9) { if constexpr (kCompileTimeGadgets<F> && !std::is_same<F, Fft2048>::value) EP_GO(4, 9); }   // (N = 2048, l = 4 left above: no instantiation here)
-  else if (l == 1 && Bg_bit == 23) EP_GO(1, 23);
-  else if (l == 1) EP_GO(1, 0);
-  else if (l == 2) EP_GO(2, 0);
-  else if (l == 3) EP_GO(3, 0);
-  else if (l == 4) { if constexpr (!std::is_same<F, Fft2048>::value) EP_GO(4, 0); }
-  else if (l == 5) EP_GO(5, 0);
-  else EP_GO(6, 0);
-#undef EP_GO
-#undef EP_GO_F
+    // (Other even lengths: not measured.)
+    using T = typename std::conditional<F::N == 2048 && L == 4, Fft2048L, F>::type;
+    if (d_in0) ep_go<T, L, BG, true>(grid, block, s, row, tw, d_in, d_out, Bg_bit, count, key_stride, in_stride, d_in0, d_out_dft);
+    else ep_go<T, L, BG, false>(grid, block, s, row, tw, d_in, d_out, Bg_bit, count, key_stride, in_stride, d_in0, d_out_dft);
+    return launched();
+  });
 }
 
 // What the launcher decided for the multi-wavefront instantiations that take the pipelined unit loop by default, for tests and tools: entry i of those asked about so
@@ -615,6 +645,30 @@ extern "C" int mosfhet_hip_pace_skip_credit(mosfhet_hip_ctx_t ctx, int *credit) 
   return MOSFHET_HIP_OK;
 }
 
+// A batch of a one-team-per-input bootstrap kernel (PbsParams, or a parameter struct whose `p` is one) in one launch per residency round of `step` inputs
+// (0: one launch); pace: a fresh rendezvous block (pace_slot) for every launch.  Row mode (TRGSW accumulators, per-level test vectors: block b takes input
+// b / rows and test vector b % rows of ONE shared set): rounds of whole inputs.
+static PbsParams &pbs_part(PbsParams &p) { return p; }
+template <class P> static PbsParams &pbs_part(P &q) { return q.p; }
+template <int N, class K, class P>
+static void launch_rounds(K kernel, int threads, const P &prm, int count, int step, bool pace, hipStream_t s) {
+  P q = prm;
+  PbsParams &qp = pbs_part(q);
+  const PbsParams p = qp;   // the whole batch's pointers
+  const int rows = p.rows > 1 ? p.rows : 1;
+  if (step <= 0 || count <= step) step = count;
+  else step = step < rows ? rows : step - step % rows;   // (a round below one input's rows: one input per launch)
+  const size_t out_row = p.extract ? (size_t)N + 1 : (size_t)2 * N;
+  for (int lo = 0; lo < count; lo += step) {
+    qp.pace = pace ? pace_slot(s) : nullptr;
+    qp.in = p.in + (size_t)(lo / rows) * (p.n + 1);
+    qp.out = p.out + (size_t)lo * out_row;
+    qp.tv = rows > 1 ? p.tv : (p.tv ? p.tv + (size_t)lo * p.tv_stride : p.tv);
+    const int c = count - lo < step ? count - lo : step;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)c), dim3(threads), 0, s, q);
+  }
+}
+
 template <class F, int L, int BG>
 static void launch_pbs(const PbsParams &p_in, int count, hipStream_t s) {
   PbsParams p = p_in;
@@ -622,46 +676,24 @@ static void launch_pbs(const PbsParams &p_in, int count, hipStream_t s) {
   const bool pace = F::THREADS > 64 && pace_every() > 0 && chunk > 0 && count >= 64;   // (all teams of a launch of <= chunk are resident)
   p.pace_every = pace ? pace_every() : 0;
   p.pace_limit = pace_limit();
-  if (chunk > 0 && count > chunk) {
-    // row mode (TRGSW accumulators, per-level test vectors: block b takes input b / rows and test vector b % rows of ONE shared set): rounds of whole inputs
-    const int rows = p.rows > 1 ? p.rows : 1, step = chunk < rows ? rows : chunk - chunk % rows;   // (a chunk below one input's rows: one input per launch)
-    const size_t out_row = p.extract ? (size_t)F::N + 1 : (size_t)2 * F::N;
-    for (int lo = 0; lo < count; lo += step) {
-      PbsParams q = p;
-      q.pace = pace ? pace_slot(s) : nullptr;
-      q.in = p.in + (size_t)(lo / rows) * (p.n + 1);
-      q.out = p.out + (size_t)lo * out_row;
-      q.tv = rows > 1 ? p.tv : (p.tv ? p.tv + (size_t)lo * p.tv_stride : p.tv);
-      const int c = count - lo < step ? count - lo : step;
-      hipLaunchKernelGGL((pbs_kernel<F, L, BG>), dim3((unsigned)c), dim3(F::THREADS), 0, s, q);
-    }
-    return;
-  }
-  p.pace = pace && count <= chunk ? pace_slot(s) : nullptr;
-  hipLaunchKernelGGL((pbs_kernel<F, L, BG>), dim3((unsigned)count), dim3(F::THREADS), 0, s, p);
+  launch_rounds<F::N>(pbs_kernel<F, L, BG>, F::THREADS, p, count, chunk, pace, s);
 }
 
+// pbs_kernel: gadget bases of the reference's parameter sets get a compile-time instantiation (test/benchmark.c:53-75, test/tests.c:37-62,967); anything else
+// runs the run-time-Bg variant, l = 1 .. 6.  6 x 2^7 at N = 2048: the one parameter set of the reference's radix-integer application
+// (applications/multi-ciphertext-arith/src/ufhe.c:18-20); the compile-time gadget is worth 20 - 35 % on this kernel (l = 4: 17.1 against 21.7 ms per 1024 with
+// the gadget at run time).
+constexpr bool pbs_gadgets(int N, int L, int BG) { return BG == 0 || reference_gadget(N, L, BG) || (N == 2048 && L == 6 && BG == 7) || (L == 1 && BG == 23); }
+
+// bounded: see gadget_dispatch -- a key view over caller-held TRGSW_DFT objects (blind_rotate(tv, a, TRGSW_DFT *s, size)) takes the reducing run-time-gadget kernel
 template <class F>
 static int launch_pbs_f(int l, int Bg_bit, const PbsParams &p, int count, hipStream_t s, bool bounded) {
-  // Gadget bases of the reference's parameter sets get a compile-time instantiation (test/benchmark.c:53-75,
-  // test/tests.c:37-62,967); anything else runs the run-time-Bg variant.  bounded: see launch_external_product -- a key view over caller-held
-  // TRGSW_DFT objects (blind_rotate(tv, a, TRGSW_DFT *s, size)) takes the reducing run-time-gadget kernel.
-  if (kCompileTimeGadgets<F> && l == 2 && Bg_bit == 8 && (bounded || F::N != 1024)) { if constexpr (kCompileTimeGadgets<F>) launch_pbs<F, 2, 8>(p, count, s); }
-  else if (kCompileTimeGadgets<F> && l == 4 && Bg_bit == 9) { if constexpr (kCompileTimeGadgets<F>) launch_pbs<F, 4, 9>(p, count, s); }
-  // 6 x 2^7 at N = 2048: the one parameter set of the reference's radix-integer application (applications/multi-ciphertext-arith/src/ufhe.c:18-20); the compile-time
-  // gadget is worth 20 - 35 % on this kernel (l = 4: 17.1 against 21.7 ms per 1024 with the gadget at run time)
-  else if (l == 6 && Bg_bit == 7 && F::N == 2048) { if constexpr (F::N == 2048) launch_pbs<F, 6, 7>(p, count, s); }
-  // l = 1: the transform grouping with a full last pass (negacyclic_fft.h, Fft2048T: same results, same key layout; +2 % at SET_2, +6 % at SET_3)
-  else if (l == 1 && Bg_bit == 23) launch_pbs<typename WideTail<F>::type, 1, 23>(p, count, s);
-  else if (l == 1) launch_pbs<typename WideTail<F>::type, 1, 0>(p, count, s);
-  else if (l == 2) launch_pbs<F, 2, 0>(p, count, s);
-  else if (l == 3) launch_pbs<F, 3, 0>(p, count, s);
-  else if (l == 4) launch_pbs<F, 4, 0>(p, count, s);
-  else if (l == 5) launch_pbs<F, 5, 0>(p, count, s);
-  else if (l == 6) launch_pbs<F, 6, 0>(p, count, s);
-  else return fail(MOSFHET_HIP_EINVAL, "l = %d not instantiated", l);
-  HIP_TRY(hipGetLastError());
-  return MOSFHET_HIP_OK;
+  return gadget_dispatch<F::N, pbs_gadgets>(l, Bg_bit, bounded, [&](auto L, auto BG) {
+    // l = 1: the transform grouping with a full last pass (negacyclic_fft.h, Fft2048T: same results, same key layout; +2 % at SET_2, +6 % at SET_3)
+    using T = typename std::conditional<L == 1, typename WideTail<F>::type, F>::type;
+    launch_pbs<T, L, BG>(p, count, s);
+    return launched();
+  });
 }
 
 // Batches up to this size take pbs_team_kernel (N = 1024): below ~1.5 workgroups per CU the one-wavefront-per-ciphertext kernel leaves
@@ -694,17 +726,13 @@ extern "C" int mosfhet_hip_set_wide_team_max_batch(int max_batch) {
   return MOSFHET_HIP_OK;
 }
 
-template <class F, int LL, int BB>
-static int launch_wide_team(const PbsParams &p, int count, hipStream_t s) {
-  constexpr size_t lds = sizeof(d2) * (size_t)2 * F::XCH_SLOTS + sizeof(uint64_t) * 2 * F::N;
-  // per launch, like general_lds: the attribute belongs to the current device's copy of the kernel (several devices in one process: mosfhet_compat_multi.c)
-  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(pbs_wide_team_kernel<F, LL, BB>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL((pbs_wide_team_kernel<F, LL, BB>), dim3((unsigned)count), dim3(2 * F::THREADS), lds, s, p);
-  HIP_TRY(hipGetLastError());
-  return MOSFHET_HIP_OK;
-}
-// bounded: see launch_external_product -- at N = 1024 the compile-time 2 x 2^8 instantiation rounds without the reduction mod 1, which only keys this
-// library transformed itself allow; key views over caller-held TRGSW_DFT sums take the reducing run-time-gadget instantiation
+// Dynamic LDS of the two-team kernels: pbs_wide_team_kernel, pbs_ga_wide_kernel, ubr_phase2_wide_kernel -- and, with the rows taken in pairs (Fft2048L),
+// pbs_wide_pair_kernel, pbs_split_kernel, pbs_ga_split_kernel
+template <class F> constexpr size_t kWideLds = sizeof(d2) * (size_t)2 * F::XCH_SLOTS + sizeof(uint64_t) * 2 * F::N;
+constexpr size_t kPairLds = kWideLds<Fft2048L> + sizeof(d2) * (size_t)4 * Fft2048L::M;
+
+// pbs_wide_team_kernel: the reference gadgets, 1 x 23; run-time gadgets l = 1 .. 6
+constexpr bool wide_team_gadgets(int N, int L, int BG) { return BG == 0 || reference_gadget(N, L, BG) || (L == 1 && BG == 23); }
 // N = 2048, even gadget lengths, at most one workgroup per CU: the teams take their rows two at a time (pbs_wide_pair_kernel).  MOSFHET_HIP_WIDE_PAIRS=0 / 1.
 static int wide_pairs_enabled() {
   static std::atomic<int> v{-1};
@@ -712,15 +740,8 @@ static int wide_pairs_enabled() {
   if (r < 0) { const char *e = getenv("MOSFHET_HIP_WIDE_PAIRS"); r = e ? (atoi(e) != 0) : 1; v.store(r, std::memory_order_relaxed); }
   return r;
 }
-template <int LL, int BB>
-static int launch_wide_pair(const PbsParams &p, int count, hipStream_t s) {
-  using F = Fft2048L;
-  constexpr size_t lds = sizeof(d2) * ((size_t)2 * F::XCH_SLOTS + (size_t)4 * F::M) + sizeof(uint64_t) * 2 * F::N;
-  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(pbs_wide_pair_kernel<F, LL, BB>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL((pbs_wide_pair_kernel<F, LL, BB>), dim3((unsigned)count), dim3(2 * F::THREADS), lds, s, p);
-  HIP_TRY(hipGetLastError());
-  return MOSFHET_HIP_OK;
-}
+// pbs_wide_pair_kernel: 4 x 2^9; run-time gadgets l = 2, 4, 6
+constexpr bool wide_pair_gadgets(int, int L, int BG) { return L % 2 == 0 && (BG == 0 || (L == 4 && BG == 9)); }
 
 // ---- one bootstrap on two workgroups (pbs_split_kernel): N = 2048, l = 2, 4, 6, batches of at most half the CUs ----
 // MOSFHET_HIP_SPLIT_MAX: largest batch that takes it (-1 = CUs / 2, the default; 0 = never).  The ONE switch of this library that changes bits: the split kernel sums
@@ -829,50 +850,29 @@ static SplitSet *split_set(hipStream_t s, int count) {
   free_slot->cap = cap;
   return free_slot;
 }
-template <int LL, int BB>
-static int launch_split(const PbsParams &p, int count, hipStream_t s, bool *taken) {
-  using F = Fft2048L;
-  *taken = false;
-  SplitSet *set = split_set(s, count);
-  if (!set) return MOSFHET_HIP_OK;   // no slots for this stream: the caller goes on to the one-CU kernel
-  constexpr size_t lds = sizeof(d2) * ((size_t)2 * F::XCH_SLOTS + (size_t)4 * F::M) + sizeof(uint64_t) * 2 * F::N;
-  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(pbs_split_kernel<F, LL, BB>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  const size_t words = (size_t)count * 2 * 2 * F::M * 2;
-  hipLaunchKernelGGL(split_prepare_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, s, reinterpret_cast<uint64_t *>(set->xbuf), words, set->state, count);
-  SplitParams sp;
-  sp.xbuf = set->xbuf;
-  sp.state = set->state;
-  sp.count = count;
-  sp.limit = split_wait_limit();
-  hipLaunchKernelGGL((pbs_split_kernel<F, LL, BB>), dim3((unsigned)(16 * ((count + 7) / 8))), dim3(2 * F::THREADS), lds, s, p, sp);
-  HIP_TRY(hipGetLastError());
-  set->last_count = count;
-  t_split_last = set;
-  *taken = true;
-  return MOSFHET_HIP_OK;
-}
-template <int LL, int BB>
-static int launch_ga_split(const GaParams &g, int count, hipStream_t s, bool *taken) {
-  using F = Fft2048L;
+// pbs_split_kernel / pbs_ga_split_kernel on this thread's exchange slots for the stream; xch_words: exchange words per bootstrap.  *taken = false: no slots for this
+// stream, the caller goes on to the one-CU kernel.
+template <class K, class P>
+static int launch_split(K kernel, const P &prm, size_t xch_words, int count, hipStream_t s, bool *taken) {
   *taken = false;
   SplitSet *set = split_set(s, count);
   if (!set) return MOSFHET_HIP_OK;
-  constexpr size_t lds = sizeof(d2) * ((size_t)2 * F::XCH_SLOTS + (size_t)4 * F::M) + sizeof(uint64_t) * 2 * F::N;
-  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(pbs_ga_split_kernel<F, LL, BB>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  const size_t words = (size_t)count * 6 * F::M * 2;
+  const size_t words = (size_t)count * xch_words;
   hipLaunchKernelGGL(split_prepare_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, s, reinterpret_cast<uint64_t *>(set->xbuf), words, set->state, count);
   SplitParams sp;
   sp.xbuf = set->xbuf;
   sp.state = set->state;
   sp.count = count;
   sp.limit = split_wait_limit();
-  hipLaunchKernelGGL((pbs_ga_split_kernel<F, LL, BB>), dim3((unsigned)(16 * ((count + 7) / 8))), dim3(2 * F::THREADS), lds, s, g, sp);
-  HIP_TRY(hipGetLastError());
+  const int rc = launch_dyn_lds(kernel, dim3((unsigned)(16 * ((count + 7) / 8))), dim3(2 * Fft2048L::THREADS), kPairLds, s, prm, sp);
+  if (rc) return rc;
   set->last_count = count;
   t_split_last = set;
   *taken = true;
   return MOSFHET_HIP_OK;
 }
+// pbs_split_kernel: 4 x 2^9, 6 x 2^7 (the radix-integer application's set); run-time gadgets l = 2, 4, 6
+constexpr bool split_gadgets(int, int L, int BG) { return L % 2 == 0 && (BG == 0 || (L == 4 && BG == 9) || (L == 6 && BG == 7)); }
 
 // How the bootstraps of this host thread's LAST split launch were taken (synchronises its stream): by a pair of workgroups, or alone by the first to arrive.
 // For tests and bench.py.  EINVAL when the thread has not made one.
@@ -896,35 +896,27 @@ template <class F>
 static int launch_wide_team_f(int l, int Bg, const PbsParams &p, int count, hipStream_t s, bool bounded) {
   if constexpr (F::N == 2048) {
     // at most half the CUs' worth of ciphertexts, even gadget lengths up to 6: two CUs per bootstrap (pbs_split_kernel)
-    if ((l == 2 || l == 4 || l == 6) && count <= split_max_batch()) {
+    if (split_gadgets(F::N, l, 0) && count <= split_max_batch()) {
       bool taken = false;
-      int rc;
-      if (l == 4) rc = Bg == 9 ? launch_split<4, 9>(p, count, s, &taken) : launch_split<4, 0>(p, count, s, &taken);
-      else if (l == 6) rc = Bg == 7 ? launch_split<6, 7>(p, count, s, &taken) : launch_split<6, 0>(p, count, s, &taken);   // 6 x 2^7: the radix-integer application's set
-      else rc = launch_split<2, 0>(p, count, s, &taken);
+      const int rc = gadget_dispatch<F::N, split_gadgets>(l, Bg, bounded, [&](auto L, auto BG) {
+        return launch_split(pbs_split_kernel<Fft2048L, L, BG>, p, (size_t)2 * 2 * Fft2048L::M * 2, count, s, &taken);
+      });
       if (rc != MOSFHET_HIP_OK || taken) return rc;
     }
     // one workgroup per CU (137 KiB of LDS each): up to as many ciphertexts as the device has CUs; beyond that pbs_wide_team_kernel runs two workgroups per CU
-    if (wide_pairs_enabled() && l % 2 == 0 && count <= device_cus()) {
-      if (l == 4 && Bg == 9) return launch_wide_pair<4, 9>(p, count, s);
-      if (l == 2) return launch_wide_pair<2, 0>(p, count, s);
-      if (l == 4) return launch_wide_pair<4, 0>(p, count, s);
-      if (l == 6) return launch_wide_pair<6, 0>(p, count, s);
+    if (wide_pairs_enabled() && wide_pair_gadgets(F::N, l, 0) && count <= device_cus()) {
+      return gadget_dispatch<F::N, wide_pair_gadgets>(l, Bg, bounded, [&](auto L, auto BG) {
+        return launch_dyn_lds(pbs_wide_pair_kernel<Fft2048L, L, BG>, dim3((unsigned)count), dim3(2 * Fft2048L::THREADS), kPairLds, s, p);
+      });
     }
   }
-  if constexpr (kCompileTimeGadgets<F>) {
-    if (l == 4 && Bg == 9) return launch_wide_team<F, 4, 9>(p, count, s);
-    if (l == 2 && Bg == 8 && (bounded || F::N != 1024)) return launch_wide_team<F, 2, 8>(p, count, s);
-  }
-  if (l == 1 && Bg == 23) return launch_wide_team<F, 1, 23>(p, count, s);
-  if (l == 1) return launch_wide_team<F, 1, 0>(p, count, s);
-  if (l == 2) return launch_wide_team<F, 2, 0>(p, count, s);
-  if (l == 3) return launch_wide_team<F, 3, 0>(p, count, s);
-  if (l == 4) return launch_wide_team<F, 4, 0>(p, count, s);
-  if (l == 5) return launch_wide_team<F, 5, 0>(p, count, s);
-  if (l == 6) return launch_wide_team<F, 6, 0>(p, count, s);
-  return fail(MOSFHET_HIP_EINVAL, "l = %d not instantiated", l);
+  return gadget_dispatch<F::N, wide_team_gadgets>(l, Bg, bounded, [&](auto L, auto BG) {
+    return launch_dyn_lds(pbs_wide_team_kernel<F, L, BG>, dim3((unsigned)count), dim3(2 * F::THREADS), kWideLds<F>, s, p);
+  });
 }
+
+// pbs_team_kernel (N = 1024): the reference gadgets; run-time gadgets l = 1 .. 4 (1 x 23 takes 1 x 0)
+constexpr bool team_gadgets(int N, int L, int BG) { return BG == 0 ? L <= 4 : reference_gadget(N, L, BG); }
 
 static int bootstrap_unfolded(const char *who, mosfhet_hip_ctx_t ctx, mosfhet_hip_bsk_t bsk, uint64_t *d_out, const uint64_t *d_tv, int tv_count,
                               const uint64_t *d_in, int count, int pre, int kappa, int theta, int torus_base, int extract, int skip_init, void *stream, int rows);
@@ -983,23 +975,16 @@ static int bootstrap_common(const char *who, mosfhet_hip_ctx_t ctx, mosfhet_hip_
   p.count = bsk->bytes > ((size_t)96 << 20) ? -1 : 0;   // launch hint: split into residency rounds (launch_pbs)
   p.rows = rows;
   // small batches: the latency-oriented team kernel (one workgroup of 2l wavefronts per ciphertext), N = 1024
-  if (bsk->N == 1024 && rows == 1 && count <= team_max_batch() && bsk->l <= 4) {
+  if (bsk->N == 1024 && rows == 1 && count <= team_max_batch() && team_gadgets(bsk->N, bsk->l, 0)) {
     hipStream_t s = pick(ctx, stream);
-    const int l = bsk->l, Bg = bsk->Bg_bit;
-#define TEAM_LAUNCH(LL, BB) hipLaunchKernelGGL((pbs_team_kernel<LL, BB>), dim3((unsigned)count), dim3(64 * 2 * LL), 0, s, p)
-    if (l == 2 && Bg == 8 && bsk->owns) TEAM_LAUNCH(2, 8);
-    else if (l == 4 && Bg == 9) TEAM_LAUNCH(4, 9);
-    else if (l == 1) TEAM_LAUNCH(1, 0);
-    else if (l == 2) TEAM_LAUNCH(2, 0);
-    else if (l == 3) TEAM_LAUNCH(3, 0);
-    else TEAM_LAUNCH(4, 0);
-#undef TEAM_LAUNCH
-    HIP_TRY(hipGetLastError());
-    return MOSFHET_HIP_OK;
+    return gadget_dispatch<1024, team_gadgets>(bsk->l, bsk->Bg_bit, bsk->owns, [&](auto L, auto BG) {
+      hipLaunchKernelGGL((pbs_team_kernel<L, BG>), dim3((unsigned)count), dim3(64 * 2 * L), 0, s, p);
+      return launched();
+    });
   }
   // (count = workgroups: ciphertexts x accumulator rows; N = 4096: 136 KiB of LDS, one workgroup per CU -- half the batch)
   // N = 1024: what pbs_team_kernel (above) does not take -- gadgets longer than 4, TRGSW accumulator rows
-  if (bsk->N == 1024 && (bsk->l > 4 || rows > 1) && count <= team_max_batch()) return launch_wide_team_f<Fft1024>(bsk->l, bsk->Bg_bit, p, count, pick(ctx, stream), bsk->owns);
+  if (bsk->N == 1024 && (!team_gadgets(bsk->N, bsk->l, 0) || rows > 1) && count <= team_max_batch()) return launch_wide_team_f<Fft1024>(bsk->l, bsk->Bg_bit, p, count, pick(ctx, stream), bsk->owns);
   if (bsk->N == 2048 && count <= wide_team_max_batch()) return launch_wide_team_f<Fft2048>(bsk->l, bsk->Bg_bit, p, count, pick(ctx, stream), bsk->owns);
   if (bsk->N == 4096 && count <= wide_team_max_batch() / 2) return launch_wide_team_f<Fft4096>(bsk->l, bsk->Bg_bit, p, count, pick(ctx, stream), bsk->owns);
   int rc_pbs = MOSFHET_HIP_OK;
@@ -1058,9 +1043,9 @@ extern "C" int mosfhet_hip_external_product_batch(mosfhet_hip_ctx_t ctx, mosfhet
   if (bsk->general) return external_product_general(ctx, bsk, key_index, d_out, d_in, nullptr, count, stream);
   const d2 *row = bsk->d_bk + (size_t)key_index * (2 * bsk->l * 2 * (bsk->N / 2));
   hipStream_t s = pick(ctx, stream);
-  RING_DISPATCH(ctx, bsk->N, launch_external_product<F>(bsk->l, bsk->Bg_bit, s, row, TW, d_in, d_out, count, (size_t)0, (size_t)2 * F::N, nullptr, nullptr, bsk->owns));
-  HIP_TRY(hipGetLastError());
-  return MOSFHET_HIP_OK;
+  int rc = MOSFHET_HIP_OK;
+  RING_DISPATCH(ctx, bsk->N, rc = launch_external_product<F>(bsk->l, bsk->Bg_bit, s, row, TW, d_in, d_out, count, (size_t)0, (size_t)2 * F::N, nullptr, nullptr, bsk->owns));
+  return rc;
 }
 
 // ---- polynomial-level entry points ----
@@ -1282,65 +1267,44 @@ static void launch_ga(const GaParams &g_in, int count, hipStream_t s) {
     g.p.pace_every = pace_every();
     g.p.pace_limit = pace_limit();
   }
-  if (round > 0 && count > round) {
-    const size_t out_row = g.p.extract ? (size_t)F::N + 1 : (size_t)2 * F::N;
-    for (int lo = 0; lo < count; lo += round) {
-      GaParams q = g;
-      q.p.pace = pace ? pace_slot(s) : nullptr;
-      q.p.in = g.p.in + (size_t)lo * (g.p.n + 1);
-      q.p.out = g.p.out + (size_t)lo * out_row;
-      q.p.tv = g.p.tv ? g.p.tv + (size_t)lo * g.p.tv_stride : g.p.tv;
-      const int c = count - lo < round ? count - lo : round;
-      hipLaunchKernelGGL((pbs_ga_kernel<F, L, BG>), dim3((unsigned)c), dim3(F::THREADS), 0, s, q);
-    }
-    return;
-  }
-  if (pace) g.p.pace = pace_slot(s);
-  hipLaunchKernelGGL((pbs_ga_kernel<F, L, BG>), dim3((unsigned)count), dim3(F::THREADS), 0, s, g);
+  launch_rounds<F::N>(pbs_ga_kernel<F, L, BG>, F::THREADS, g, count, round, pace, s);
 }
 
+// pbs_ga_split_kernel (N = 2048): 4 x 2^9; run-time gadget l = 4
+constexpr bool ga_split_gadgets(int, int L, int BG) { return L == 4 && (BG == 0 || BG == 9); }
+// pbs_ga_kernel: the reference gadgets (no 1 x 23); run-time gadgets l = 1 .. 6.  N = 2048, 4 x 2^9 runs on Fft2048L (launch_ga_f).
+constexpr bool ga_gadgets(int N, int L, int BG) { return BG == 0 || reference_gadget(N, L, BG); }
+
+// bounded = true below: the Galois bootstraps have never applied the bounded-key rule, though a key view reaches them (blind_rotate_ga in mosfhet_compat_dft.c).
 template <class F>
 static int launch_ga_f(int l, int Bg_bit, const GaParams &g, int count, hipStream_t s) {
   // at most half the CUs' worth of ciphertexts at N = 2048, l = 4: two CUs per bootstrap (pbs_ga_split_kernel; the external products in pbs_split_kernel's summation order)
   if constexpr (F::N == 2048) {
-    if (g.mode == 0 && l == 4 && count <= split_max_batch()) {
+    if (g.mode == 0 && ga_split_gadgets(F::N, l, 0) && count <= split_max_batch()) {
       GaParams gs = g;
       gs.p.Bg_bit = Bg_bit;
       bool taken = false;
-      const int rc = Bg_bit == 9 ? launch_ga_split<4, 9>(gs, count, s, &taken) : launch_ga_split<4, 0>(gs, count, s, &taken);
+      const int rc = gadget_dispatch<F::N, ga_split_gadgets>(l, Bg_bit, true, [&](auto L, auto BG) {
+        return launch_split(pbs_ga_split_kernel<Fft2048L, L, BG>, gs, (size_t)6 * Fft2048L::M * 2, count, s, &taken);
+      });
       if (rc != MOSFHET_HIP_OK || taken) return rc;
     }
   }
   // few ciphertexts: two transform teams per ciphertext (pbs_ga_wide_kernel, bit-identical; the switch-overs of the plain bootstrap's latency kernels)
   if constexpr (F::N <= 2048) {
     if (g.mode == 0 && count <= (F::N == 1024 ? team_max_batch() : wide_team_max_batch())) {
-      constexpr size_t lds = sizeof(d2) * (size_t)2 * F::XCH_SLOTS + sizeof(uint64_t) * 2 * F::N;
-      if (lds > 48 * 1024) HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(pbs_ga_wide_kernel<F>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
       GaParams gw = g;
       gw.p.Bg_bit = Bg_bit;
-      hipLaunchKernelGGL(pbs_ga_wide_kernel<F>, dim3((unsigned)count), dim3(2 * F::THREADS), lds, s, gw, l);
-      HIP_TRY(hipGetLastError());
-      return MOSFHET_HIP_OK;
+      return launch_dyn_lds(pbs_ga_wide_kernel<F>, dim3((unsigned)count), dim3(2 * F::THREADS), kWideLds<F>, s, gw, l);
     }
   }
-  if constexpr (std::is_same<F, Fft2048>::value) {
+  return gadget_dispatch<F::N, ga_gadgets>(l, Bg_bit, true, [&](auto L, auto BG) {
     // lvl2: the pass twiddles in LDS (Fft2048L) take the kernel out of scratch (68 bytes -> 0, 250 registers; same speed: experiments/README.md round 4).
     // The run-time-gadget instantiations spill with either transform and stay where they were.
-    if (l == 4 && Bg_bit == 9) { launch_ga<Fft2048L, 4, 9>(g, count, s); HIP_TRY(hipGetLastError()); return MOSFHET_HIP_OK; }
-  }
-  if (kCompileTimeGadgets<F> && l == 2 && Bg_bit == 8) { if constexpr (kCompileTimeGadgets<F>) launch_ga<F, 2, 8>(g, count, s); }
-  else if (kCompileTimeGadgets<F> && !std::is_same<F, Fft2048>::value && l == 4 && Bg_bit == 9) {   // (N = 2048: left above with the LDS-twiddle transform)
-    if constexpr (kCompileTimeGadgets<F> && !std::is_same<F, Fft2048>::value) launch_ga<F, 4, 9>(g, count, s);
-  }
-  else if (l == 1) launch_ga<F, 1, 0>(g, count, s);
-  else if (l == 2) launch_ga<F, 2, 0>(g, count, s);
-  else if (l == 3) launch_ga<F, 3, 0>(g, count, s);
-  else if (l == 4) launch_ga<F, 4, 0>(g, count, s);
-  else if (l == 5) launch_ga<F, 5, 0>(g, count, s);
-  else if (l == 6) launch_ga<F, 6, 0>(g, count, s);
-  else return fail(MOSFHET_HIP_EINVAL, "l = %d not instantiated", l);
-  HIP_TRY(hipGetLastError());
-  return MOSFHET_HIP_OK;
+    using T = typename std::conditional<F::N == 2048 && L == 4 && BG == 9, Fft2048L, F>::type;
+    launch_ga<T, L, BG>(g, count, s);
+    return launched();
+  });
 }
 
 extern "C" int mosfhet_hip_trlwe_eval_automorphism_batch(mosfhet_hip_ctx_t ctx, mosfhet_hip_gak_t gak, uint64_t *d_out,

@@ -337,7 +337,8 @@ extern "C" int mosfhet_hip_functional_bootstrap_trgsw_phase2_batch(mosfhet_hip_c
   hipStream_t s = pick(ctx, stream);
   const size_t key_stride = (size_t)2 * l * 2 * (N / 2), in_stride = tv_count == 1 ? 0 : (size_t)2 * N;
   const d2 *g = (const d2 *)d_in_dft;
-  RING_DISPATCH(ctx, N, launch_external_product<F>(l, bsk->Bg_bit, s, g, TW, d_tv, tmp, count, key_stride, in_stride, nullptr, nullptr, false));
+  RING_DISPATCH(ctx, N, rc = launch_external_product<F>(l, bsk->Bg_bit, s, g, TW, d_tv, tmp, count, key_stride, in_stride, nullptr, nullptr, false));
+  if (rc) return rc;
   hipLaunchKernelGGL(trlwe_extract_kernel, dim3((N + 255) / 256, count), dim3(256), 0, s, d_out, (size_t)N + 1, tmp, (size_t)2 * N, N, 0);
   HIP_TRY(hipGetLastError());
   return MOSFHET_HIP_OK;
@@ -488,37 +489,19 @@ static int unfold2_ready(mosfhet_hip_ctx_t ctx, mosfhet_hip_bsk *b) {
   return MOSFHET_HIP_OK;
 }
 
+// pbs_unfold2_kernel: the reference gadgets; run-time gadgets l = 1 .. 6
+constexpr bool unfold2_gadgets(int N, int L, int BG) { return BG == 0 || reference_gadget(N, L, BG); }
+
+// bounded = true below: unfolding-2 keys are always samples this library transformed itself (unfold2_ready); no key view reaches this launcher.
 template <class F>
-static int launch_unfold2_f(int l, int Bg_bit, const Unfold2Params &u_in, int count, hipStream_t s) {
+static int launch_unfold2_f(int l, int Bg_bit, const Unfold2Params &u, int count, hipStream_t s) {
   // N = 2048: the transformed samples (1.5 x a plain key) do not fit the L2s either -- one launch per residency round, like launch_pbs (4096 at lvl2: 120.9 -> 99.7 ms)
+  // (the per-XCD rendezvous of the plain kernel was tried here too: 100.8 against 99.7 ms per 4096 without it -- not adopted)
   const int round = F::N == 2048 ? round_chunk(F::THREADS) : 0;
-  if (round > 0 && count > round) {
-    const size_t out_row = u_in.p.extract ? (size_t)F::N + 1 : (size_t)2 * F::N;
-    for (int lo = 0; lo < count; lo += round) {
-      Unfold2Params q = u_in;
-      q.p.in = u_in.p.in + (size_t)lo * (u_in.p.n + 1);
-      q.p.out = u_in.p.out + (size_t)lo * out_row;
-      q.p.tv = u_in.p.tv ? u_in.p.tv + (size_t)lo * u_in.p.tv_stride : u_in.p.tv;
-      const int c = count - lo < round ? count - lo : round;
-      const int rc = launch_unfold2_f<F>(l, Bg_bit, q, c, s);
-      if (rc) return rc;
-    }
-    return MOSFHET_HIP_OK;
-  }
-  const Unfold2Params &u = u_in;   // (the per-XCD rendezvous of the plain kernel was tried here too: 100.8 against 99.7 ms per 4096 without it -- not adopted)
-#define UNFOLD2_LAUNCH(LL, BB) hipLaunchKernelGGL((pbs_unfold2_kernel<F, LL, BB>), dim3((unsigned)count), dim3(F::THREADS), 0, s, u)
-  if (kCompileTimeGadgets<F> && l == 2 && Bg_bit == 8) { if constexpr (kCompileTimeGadgets<F>) UNFOLD2_LAUNCH(2, 8); }
-  else if (kCompileTimeGadgets<F> && l == 4 && Bg_bit == 9) { if constexpr (kCompileTimeGadgets<F>) UNFOLD2_LAUNCH(4, 9); }
-  else if (l == 1) UNFOLD2_LAUNCH(1, 0);
-  else if (l == 2) UNFOLD2_LAUNCH(2, 0);
-  else if (l == 3) UNFOLD2_LAUNCH(3, 0);
-  else if (l == 4) UNFOLD2_LAUNCH(4, 0);
-  else if (l == 5) UNFOLD2_LAUNCH(5, 0);
-  else if (l == 6) UNFOLD2_LAUNCH(6, 0);
-  else return fail(MOSFHET_HIP_EINVAL, "l = %d not instantiated", l);
-#undef UNFOLD2_LAUNCH
-  HIP_TRY(hipGetLastError());
-  return MOSFHET_HIP_OK;
+  return gadget_dispatch<F::N, unfold2_gadgets>(l, Bg_bit, true, [&](auto L, auto BG) {
+    launch_rounds<F::N>(pbs_unfold2_kernel<F, L, BG>, F::THREADS, u, count, round, false, s);
+    return launched();
+  });
 }
 
 extern "C" int mosfhet_hip_bsk_unfolded_create(mosfhet_hip_ctx_t ctx, mosfhet_hip_bsk_t *out, const uint64_t *h_su, int n, int N, int l, int Bg_bit,
@@ -575,13 +558,12 @@ static int launch_ubr_phase2(mosfhet_hip_ctx_t ctx, mosfhet_hip_bsk_t bsk, hipSt
   const int N = bsk->N, groups = bsk->n / bsk->unfolding;
   if (N == 2048 && units <= wide_team_max_batch()) {
     using F = Fft2048;
-    constexpr size_t lds = sizeof(d2) * (size_t)2 * F::XCH_SLOTS + sizeof(uint64_t) * 2 * F::N;
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(ubr_phase2_wide_kernel<F>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));   // per device: see launch_wide_team
-    hipLaunchKernelGGL(ubr_phase2_wide_kernel<F>, dim3(units), dim3(2 * F::THREADS), lds, s, sa, ctx->tw2048, d_in, d_tvs, acc, bsk->n, bsk->l, bsk->Bg_bit, groups, tv_count, prec, tv_stride_b);
+    return launch_dyn_lds(ubr_phase2_wide_kernel<F>, dim3(units), dim3(2 * F::THREADS), kWideLds<F>, s, sa, ctx->tw2048, d_in, d_tvs, acc, bsk->n, bsk->l, bsk->Bg_bit, groups,
+                          tv_count, prec, tv_stride_b);
   } else if (N == 1024 && units <= team_max_batch()) {
-    using F = Fft1024;
-    constexpr size_t lds = sizeof(d2) * (size_t)2 * F::XCH_SLOTS + sizeof(uint64_t) * 2 * F::N;   // < 48 KiB: no attribute needed
-    hipLaunchKernelGGL(ubr_phase2_wide_kernel<F>, dim3(units), dim3(2 * F::THREADS), lds, s, sa, ctx->tw1024, d_in, d_tvs, acc, bsk->n, bsk->l, bsk->Bg_bit, groups, tv_count, prec, tv_stride_b);
+    using F = Fft1024;   // (< 48 KiB of LDS: no attribute needed)
+    hipLaunchKernelGGL(ubr_phase2_wide_kernel<F>, dim3(units), dim3(2 * F::THREADS), kWideLds<F>, s, sa, ctx->tw1024, d_in, d_tvs, acc, bsk->n, bsk->l, bsk->Bg_bit, groups, tv_count, prec,
+                       tv_stride_b);
   } else {
     RING_DISPATCH(ctx, N, hipLaunchKernelGGL(ubr_phase2_kernel<F>, dim3(units), dim3(F::THREADS), 0, s, sa, TW, d_in, d_tvs, acc, bsk->n, bsk->l, bsk->Bg_bit, groups, tv_count, prec, tv_stride_b));
   }
@@ -1089,9 +1071,9 @@ extern "C" int mosfhet_hip_cmux_batch(mosfhet_hip_ctx_t ctx, mosfhet_hip_bsk_t b
   if (bsk->general) return external_product_general(ctx, bsk, key_index, d_out, d_in1, d_in0, count, stream);
   const d2 *row = bsk->d_bk + (size_t)key_index * (2 * bsk->l * 2 * (bsk->N / 2));
   hipStream_t s = pick(ctx, stream);
-  RING_DISPATCH(ctx, bsk->N, launch_external_product<F>(bsk->l, bsk->Bg_bit, s, row, TW, d_in1, d_out, count, (size_t)0, (size_t)2 * F::N, d_in0, nullptr, bsk->owns));
-  HIP_TRY(hipGetLastError());
-  return MOSFHET_HIP_OK;
+  int rc = MOSFHET_HIP_OK;
+  RING_DISPATCH(ctx, bsk->N, rc = launch_external_product<F>(bsk->l, bsk->Bg_bit, s, row, TW, d_in1, d_out, count, (size_t)0, (size_t)2 * F::N, d_in0, nullptr, bsk->owns));
+  return rc;
 }
 
 // ---- key images for the on-disk formats (SURVEY 8(f).2; save_bootstrap_key / load_new_bootstrap_key src/bootstrap.c:63-104,

@@ -3,6 +3,7 @@ object's own metadata (the .hip_fatbin section -> gfx950 code object -> AMDGPU n
 
     python tools/kernel_table.py [--scratch] [name filter]        (--scratch: only kernels with a private segment)
 
+Which instantiations exist is decided by the launcher families' gadget predicates (capi.hip: gadget_dispatch and the *_gadgets next to each launcher).
 tests/test_host_and_abi.py uses table() to hold the build to what the launcher assumes about it (capi.hip: ep_go).
 """
 import os
