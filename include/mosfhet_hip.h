@@ -87,7 +87,9 @@ int mosfhet_hip_bsk_export_dft(mosfhet_hip_bsk_t bsk, double *h_out);
 /* programmable_bootstrap over a batch (src/bootstrap.c:208-220): for every b < count
  *   d_out[b] = TLWE(kN) = SampleExtract_0( BlindRotate( tv_b * X^{-round(2N b'/2^64)}, a', BK ) )
  * with (a', b') = ((x << kappa) + 2^(63-log2(2N)+theta)) & ~(2^(64-log2(2N)+theta) - 1) and
- * torus_base = 2^(precision-1).  d_tv holds tv_count test vectors; tv_count == 1 shares one test
+ * torus_base = 2^(precision-1).  Ranges: 1 <= precision <= 30, 0 <= kappa <= 63 and
+ * 0 <= theta <= log2(2N) - 1 (from theta = log2(2N) on the mask's shift would be 64 or more);
+ * anything else fails with MOSFHET_HIP_EINVAL.  d_tv holds tv_count test vectors; tv_count == 1 shares one test
  * vector across the batch (the reference's callers pass one LUT per call), tv_count == count gives
  * each ciphertext its own. */
 int mosfhet_hip_programmable_bootstrap_batch(mosfhet_hip_ctx_t ctx, mosfhet_hip_bsk_t bsk,

@@ -930,7 +930,10 @@ static int bootstrap_common(const char *who, mosfhet_hip_ctx_t ctx, mosfhet_hip_
   if (!skip_init && rows == 1 && (!d_tv || (tv_count != 1 && tv_count != count)))
     return fail(MOSFHET_HIP_EINVAL, "%s: tv_count must be 1 or count (got %d, count %d)", who, tv_count, count);
   if (!skip_init && torus_base < 1) return fail(MOSFHET_HIP_EINVAL, "%s: torus_base %d", who, torus_base);
-  if (pre && (kappa < 0 || kappa > 63 || theta < 0 || theta > 52)) return fail(MOSFHET_HIP_EINVAL, "%s: kappa/theta out of range", who);
+  if (pre && (kappa < 0 || kappa > 63)) return fail(MOSFHET_HIP_EINVAL, "%s: kappa = %d out of range (0 .. 63)", who, kappa);
+  // the pre-processing mask is 2^(64 - log2(2N) + theta): a shift of 64 or more (theta >= log2(2N)) is undefined, so the range depends on the ring
+  if (pre && (theta < 0 || theta > ilog2(2 * bsk->N) - 1))
+    return fail(MOSFHET_HIP_EINVAL, "%s: theta = %d out of range at N = %d (0 .. %d)", who, theta, bsk->N, ilog2(2 * bsk->N) - 1);
   if (count == 0) return MOSFHET_HIP_OK;
   HIP_TRY(hipSetDevice(ctx->device));
   if (bsk->unfolding > 1) return bootstrap_unfolded(who, ctx, bsk, d_out, d_tv, tv_count, d_in, count, pre, kappa, theta, torus_base, extract, skip_init, stream, rows);
@@ -1275,7 +1278,9 @@ constexpr bool ga_split_gadgets(int, int L, int BG) { return L == 4 && (BG == 0 
 // pbs_ga_kernel: the reference gadgets (no 1 x 23); run-time gadgets l = 1 .. 6.  N = 2048, 4 x 2^9 runs on Fft2048L (launch_ga_f).
 constexpr bool ga_gadgets(int N, int L, int BG) { return BG == 0 || reference_gadget(N, L, BG); }
 
-// bounded = true below: the Galois bootstraps have never applied the bounded-key rule, though a key view reaches them (blind_rotate_ga in mosfhet_compat_dft.c).
+// bounded = true below is safe for any key, a view over caller-held TRGSW_DFT sums included (blind_rotate_ga in mosfhet_compat_dft.c builds one): the Galois
+// kernels (pbs_ga_kernel, pbs_ga_wide_kernel, pbs_ga_split_kernel) always round with round_mod_2_64, whatever the instantiation
+// (tests/test_gpu_parity.py: test_unbounded_key_views_take_the_reducing_kernels).
 template <class F>
 static int launch_ga_f(int l, int Bg_bit, const GaParams &g, int count, hipStream_t s) {
   // at most half the CUs' worth of ciphertexts at N = 2048, l = 4: two CUs per bootstrap (pbs_ga_split_kernel; the external products in pbs_split_kernel's summation order)

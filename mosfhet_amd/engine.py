@@ -650,6 +650,15 @@ class Engine:
         _check(lib().mosfhet_hip_dft_to_torus_batch(self.h, _ptr(out), _ptr(dfts), N, count, self._stream()))
         return out
 
+    def dft_lincomb(self, a, b, cb, out=None):
+        """out = a + cb * b elementwise over DFT-domain doubles (a may be None: cb * b) -- trgsw_DFT_add / _sub and their kin (src/trgsw.c, src/polynomial.c:102-128)"""
+        assert a is None or a.shape == b.shape
+        if out is None:
+            out = self.torch.empty_like(b)
+        _check(lib().mosfhet_hip_dft_lincomb_batch(self.h, _ptr(out), None if a is None else _ptr(a), _ptr(b), C.c_double(cb), C.c_size_t(b.numel()),
+                                                   self._stream()))
+        return out
+
     def dft_mul(self, a, b, out=None, addto=False):
         count, N = a.shape
         if out is None:

@@ -185,7 +185,13 @@ def trlwe_phase(c, s):
     return out
 
 
+def _check_pre(N, kappa, theta):
+    """the range where programmable_bootstrap's pre-processing is defined: the mask's shift 64 - log2(2N) + theta stays below 64"""
+    assert 0 <= kappa <= 63 and 0 <= theta < (2 * N).bit_length() - 1, (N, kappa, theta)
+
+
 def pbs_preprocess(c, N, kappa, theta):
+    _check_pre(N, kappa, theta)
     out = np.empty_like(c)
     lib().orc_pbs_preprocess(_u(out), _u(c), C.c_int(c.size - 1), N, kappa, theta)
     return out
@@ -288,6 +294,7 @@ def functional_bootstrap(tv, c, bk_dft, l, Bg_bit, torus_base):
 
 def programmable_bootstrap(tv, c, bk_dft, l, Bg_bit, precision, kappa, theta):
     k1, N = tv.shape
+    _check_pre(N, kappa, theta)
     out = np.empty((k1 - 1) * N + 1, dtype=np.uint64)
     lib().orc_programmable_bootstrap(plan(N).h, _u(out), _u(tv), _u(c), _d(bk_dft),
                                      C.c_int(c.size - 1), k1 - 1, l, Bg_bit, precision, kappa, theta)

@@ -355,6 +355,18 @@ void *ref_bk_ga_new(const Torus *bk_flat, const Torus *ak_flat, int n, int N, in
 
 void ref_bk_ga_free(void *h) { free_bootstrap_key_ga((Bootstrap_GA_Key)h); }
 
+/* blind_rotate_ga (src/bootstrap_ga.c:39-60) in place on a caller-supplied accumulator; a: the n mask words */
+void ref_blind_rotate_ga(Torus *acc, const Torus *a, void *h) {
+  Bootstrap_GA_Key bk = (Bootstrap_GA_Key)h;
+  TRLWE t = trlwe_from_flat(acc, 1, bk->N);
+  Torus *aa = (Torus *)safe_malloc(sizeof(Torus) * bk->n);
+  memcpy(aa, a, sizeof(Torus) * bk->n);
+  blind_rotate_ga(t, aa, bk->s, bk->ak, bk->n);
+  trlwe_to_flat(acc, t, bk->N);
+  free(aa);
+  free_trlwe(t);
+}
+
 void ref_functional_bootstrap_ga(Torus *out, const Torus *tv, const Torus *in, void *h, int torus_base, int extract) {
   Bootstrap_GA_Key bk = (Bootstrap_GA_Key)h;
   TRLWE t = trlwe_from_flat(tv, 1, bk->N);
@@ -470,6 +482,51 @@ void ref_generic_keyswitch(int kind, Torus *out, const Torus *in, void *h, int N
   else trlwe_priv_keyswitch(o, c, key);
   trlwe_to_flat(out, o, N);
   free_tlwe(c);
+  free_trlwe(o);
+}
+
+/* LUT packing key switch: trlwe_new_packing_KS_key (keyswitch.c:244-270) made by the library from our key words, exported as rows
+ * [n][torus_base][t][2^bb-1][2][N] (the oracle's and the device's layout), and the library's trlwe_packing_keyswitch (keyswitch.c:343-366) on
+ * its own seed-compressed key */
+void *ref_packing_ks_new(const Torus *s_out, int N, const Torus *s_in, int n, int t, int base_bit, int torus_base, double sigma) {
+  TRLWE_Key ko = trlwe_key_from_words(s_out, N, sigma);
+  TLWE_Key ki = tlwe_key_from_words(s_in, n, sigma);
+  LUT_Packing_KS_Key res = trlwe_new_packing_KS_key(ko, ki, t, base_bit, torus_base);
+  free_trlwe_key(ko);
+  free_tlwe_key(ki);
+  return res;
+}
+
+void ref_packing_ks_free(void *h) { free_trlwe_packing_ks_key((LUT_Packing_KS_Key)h); }
+
+void ref_packing_ks_export(void *h, Torus *flat, int N) {
+  LUT_Packing_KS_Key key = (LUT_Packing_KS_Key)h;
+  const int per_j = (1 << key->base_bit) - 1;
+  TRLWE tmp = trlwe_alloc_new_sample(1, N);
+  for (int i = 0; i < key->n; i++)
+    for (int e = 0; e < key->torus_base; e++)
+      for (int j = 0; j < key->t; j++)
+        for (int v = 0; v < per_j; v++) {
+          trlwe_noiseless_trivial_sample(tmp, NULL);
+          trlwe_compressed_subto(tmp, key->s[i][e][j][v]);
+          Torus *dst = flat + ((((size_t)i * key->torus_base + e) * key->t + j) * per_j + v) * 2 * N;
+          for (int c = 0; c < N; c++) {
+            dst[c] = (Torus)0 - tmp->a[0]->coeffs[c];
+            dst[N + c] = (Torus)0 - tmp->b->coeffs[c];
+          }
+        }
+  free_trlwe(tmp);
+}
+
+void ref_packing_keyswitch(Torus *out, const Torus *in /*[torus_base][n+1]*/, void *h, int N) {
+  LUT_Packing_KS_Key key = (LUT_Packing_KS_Key)h;
+  TLWE *c = (TLWE *)safe_malloc(sizeof(TLWE) * key->torus_base);
+  for (int e = 0; e < key->torus_base; e++) c[e] = tlwe_from_flat(in + (size_t)e * (key->n + 1), key->n);
+  TRLWE o = trlwe_alloc_new_sample(1, N);
+  trlwe_packing_keyswitch(o, c, key);
+  trlwe_to_flat(out, o, N);
+  for (int e = 0; e < key->torus_base; e++) free_tlwe(c[e]);
+  free(c);
   free_trlwe(o);
 }
 
