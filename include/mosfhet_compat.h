@@ -64,6 +64,12 @@ void mosfhet_replication_stats(unsigned long long bytes[4], double seconds[4], i
                                                     * peer (xGMI), 2 device to device without peer access, 3 host bounce buffer (mosfhet_hip_last_clone_route) */
 void *mosfhet_engine_ctx(void);                /* the mosfhet_hip_ctx_t behind the compat layer */
 void *mosfhet_bootstrap_key_device(Bootstrap_Key key);   /* the mosfhet_hip_bsk_t behind a Bootstrap_Key */
+/* Summation order of the key's external products (mosfhet_hip.h: MOSFHET_HIP_ORDER_AUTO / _REFERENCE / _BY_COMPONENT, which see for the launchers it governs):
+ * forwarded to the key's engine handle and to its replicas on the other GPUs of mosfhet_set_devices, those made already and those made later.  With REFERENCE or
+ * BY_COMPONENT the words of a batch do not depend on its size, on how it is cut into chunks or on the number of GPUs.  Not while another thread bootstraps with
+ * the key.  blind_rotate(tv, a, key->s, n) and blind_rotate_ga(..., key->s, ...) sum as `key` does (the order is looked up from the entries handed over);
+ * TRGSW_DFT arrays of the caller's own, and entries gathered from several places, are AUTO.  Saved keys do not carry it: set it again after load_new_bootstrap_key.  An unknown value aborts like every bad argument of this layer. */
+void mosfhet_bootstrap_key_set_product_order(Bootstrap_Key key, int order);
 
 /* ---- torus scalars (src/misc.c:13-28) ---- */
 double torus2double(Torus x);
@@ -189,6 +195,7 @@ typedef struct _TRLWE_KS_Key { void **s; int base_bit, t, k;                    
 typedef struct _Bootstrap_GA_Key { TRGSW_DFT *s; TRGSW *su; TRLWE_KS_Key *ak; int n, k, N, Bg_bit, l, unfolding; void *device, *ak_device; } *Bootstrap_GA_Key;
 Bootstrap_GA_Key new_bootstrap_key_ga(TRGSW_Key out_key, TLWE_Key in_key);                                   /* :5-24 */
 void free_bootstrap_key_ga(Bootstrap_GA_Key key);                                                            /* :26-33 */
+void mosfhet_bootstrap_ga_key_set_product_order(Bootstrap_GA_Key key, int order);   /* (new) as mosfhet_bootstrap_key_set_product_order; governs N = 2048, l = 4 */
 void functional_bootstrap_wo_extract_ga(TRLWE out, TRLWE tv, TLWE in, Bootstrap_GA_Key key, int torus_base); /* :62-68 */
 void functional_bootstrap_ga(TLWE out, TRLWE tv, TLWE in, Bootstrap_GA_Key key, int torus_base);             /* :70-76 */
 void blind_rotate_ga(TRLWE tv, Torus *a, TRGSW_DFT *s, TRLWE_KS_Key *ak, int size);                          /* :35-60; s and ak from one Bootstrap_GA_Key */

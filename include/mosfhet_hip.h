@@ -357,7 +357,47 @@ int mosfhet_hip_ks_words_plan(int count, int n_in, int row, int t, int base_bit,
  * alone (same summation order, same bits); 0 = always alone (test switch) */
 int mosfhet_hip_set_split_wait_limit(int ticks);
 /* of the calling host thread's last split launch (synchronises its stream): bootstraps taken by a pair of workgroups / alone */
-int mosfhet_hip_split_last_launch(int *count, int *paired, int *alone);
+int mosfhet_hip_split_last_launch(int *count, int *paired, int *alone);   /* (the one-CU and throughput by-component launches of a BY_COMPONENT key are no split launches and do not update it) */
+
+/* Summation order of a bootstrap key's external products -- a property of the KEY, so that the same key and ciphertext give the same words at every batch
+ * size, on every device and on every shard of a batch.
+ *   AUTO          (every new key) the kernel chosen for the batch size decides: by component on the split kernels, the reference's one chain elsewhere
+ *   REFERENCE     one fma chain over all 2 l rows (src/trgsw.c:393-419): the split kernels are never taken for this key, whatever
+ *                 MOSFHET_HIP_SPLIT_MAX / mosfhet_hip_set_split_max_batch say
+ *   BY_COMPONENT  the split kernels' order (rows 0 .. l-1 chained from zero, rows l .. 2l-1 chained from zero, one IEEE addition of the two sums) at EVERY
+ *                 batch size: batches of at most split_max_batch bootstraps still take two CUs each (a matter of speed only), larger ones and launches that
+ *                 find no exchange slots take the one-CU by-component kernel (the split kernel's alone path with a launch shape of its own), batches beyond
+ *                 wide_team_max_batch the by-component form of the throughput kernel (pbs_kernel<.., BYC = true>; the Galois family: the one-CU kernel in residency
+ *                 rounds of one workgroup per CU).  The split switches are pure performance switches for such a key.
+ * Rule: the property governs every launcher family in which AUTO can pick a by-component kernel for SOME batch size: the plain bootstrap family at N = 2048
+ * with l = 2, 4, 6 (programmable / functional bootstrap with and without extract, blind_rotate, row mode and every composition built on them: FDFB and its
+ * KS21 / CLOT21 forms, multi-value CLOT21, key switch + bootstrap, circuit bootstraps, the vec_* callers) and the Galois family at N = 2048 with l = 4.
+ * Everywhere else (other rings, odd l, Galois at l != 4, unfolded keys, the general-ring path, stand-alone external products and CMUX) results do not depend
+ * on the batch size already: the setter accepts any valid value there and it changes nothing.
+ * The field is read by the launchers: setting it while another thread issues launches on the key is the caller's race; keys stay read-only otherwise.
+ * mosfhet_hip_bsk_clone copies it (replicas on other GPUs sum alike).  Key images and on-disk formats do not carry it (formats unchanged): set it after loading.
+ * Unknown values: MOSFHET_HIP_EINVAL. */
+#define MOSFHET_HIP_ORDER_AUTO          0
+#define MOSFHET_HIP_ORDER_REFERENCE     1
+#define MOSFHET_HIP_ORDER_BY_COMPONENT  2
+int mosfhet_hip_bsk_set_product_order(mosfhet_hip_bsk_t bsk, int order);
+int mosfhet_hip_bsk_get_product_order(mosfhet_hip_bsk_t bsk, int *order);
+/* Which kernel family a bootstrap launch of a tuned, folded key takes, without a device: the function the launchers themselves decide with, at the current values
+ * of the batch-threshold setters (team / wide_team / split max_batch, MOSFHET_HIP_ROUND_CHUNK), with `cus` in place of the device's CU count.
+ * count: bootstraps of the launch (ciphertexts x rows in row mode); rows: accumulator rows per ciphertext (1 = plain); galois: 0 plain family, 1 Galois family.
+ *   plan[0]  kernel family (below)      plan[1]  1 = that kernel sums by component
+ *   plan[2]  launches (residency rounds) of a key that does not fit the L2s      plan[3]  reserved, 0
+ * (SPLIT: a BY_COMPONENT key whose launch finds no exchange slots runs LATENCY_BY_COMPONENT instead, an AUTO key LATENCY.) */
+#define MOSFHET_HIP_FAMILY_THROUGHPUT               0   /* one team per bootstrap, several per CU (pbs_kernel, pbs_ga_kernel) */
+#define MOSFHET_HIP_FAMILY_LATENCY                  1   /* one workgroup of several teams per bootstrap (pbs_team / wide_team / wide_pair, pbs_ga_wide) */
+#define MOSFHET_HIP_FAMILY_SPLIT                    2   /* two CUs per bootstrap (pbs_split_kernel, pbs_ga_split_kernel): by component */
+#define MOSFHET_HIP_FAMILY_LATENCY_BY_COMPONENT     3   /* the one-CU by-component kernel, one launch */
+#define MOSFHET_HIP_FAMILY_THROUGHPUT_BY_COMPONENT  4   /* pbs_kernel<.., BYC = true> (plain family); Galois family: the one-CU by-component kernel in rounds of one workgroup per CU */
+int mosfhet_hip_bootstrap_plan(int N, int l, int Bg_bit, int count, int rows, int galois, int order, int cus, int plan[4]);
+/* The throughput by-component kernel parks one partial sum per workgroup in device memory (32 KiB each, at most 128 MiB per host thread and stream, allocated at the
+ * first such launch -- outside a stream capture).  When that memory is refused the launch runs the one-CU by-component kernel in residency rounds instead: the same
+ * bits at about 1.8 x the time.  set_bycomp_parking(0) takes that path always (tests, and the yardstick of tools/product_order_ab.py); 1 = default. */
+int mosfhet_hip_set_bycomp_parking(int on);
 
 /* Unit-loop form of the external-product kernel on rings of two wavefronts per team (N = 2048, l = 4; trgsw_mul_trlwe_DFT, src/trgsw.c:385-423).  The
  * software-pipelined loop is taken only by the instantiation that has been soaked clean and only while its build has no scratch (capi.hip: ep_go); the plain

@@ -373,8 +373,16 @@ __device__ __forceinline__ void cmux_rows2(const typename Digits<L, BG>::word_t 
 // the transpose buffer that is 17 KiB of LDS per wavefront and <= 256 VGPRs, i.e. two wavefronts per SIMD /
 // eight per CU.  (Both components in LDS: 25 KiB -> 6 per CU, measured 22 % slower; both in registers spills.)
 // F = Fft1024: one wavefront per ciphertext; F = Fft2048: two wavefronts (128 threads) per ciphertext.
-template <class F, int L, int BG>
-__global__ __launch_bounds__(F::THREADS, 2) void pbs_kernel(PbsParams p) {
+// BYC = true (N = 2048, even l): the external product summed BY ACCUMULATOR COMPONENT, the order of pbs_split_kernel (which see) -- the rows of component 0 chained from
+// zero, the rows of component 1 chained from zero, the two sums added (one IEEE addition).  One team accumulates both output components (64 registers) and has none
+// to spare for a second pair of sums, so the partial sum of component 0's rows waits in `parked.park` (device memory, [workgroups of the launch][16][T] complex: 32 KiB
+// per workgroup, written and read once per step by the same lane, so it stays in the L2) while component 1's rows are chained from zero.  The existing instantiations
+// (BYC = false) take an empty struct there.
+template <bool BYC> struct ParkArg {};
+template <> struct ParkArg<true> { double *park; };
+template <class F, int L, int BG, bool BYC = false>
+__global__ __launch_bounds__(F::THREADS, 2) void pbs_kernel(PbsParams p, ParkArg<BYC> parked) {
+  static_assert(!BYC || (F::N == 2048 && L % 2 == 0), "the by-component order exists where pbs_split_kernel does");
   constexpr int N = F::N, M = F::M, T = F::THREADS, LOG2N2 = F::LOGM + 2;
   // Every output of the external product is a sum of 2L * N products digit * key coefficient with |digit| <= 2^(BG-1) and |key| <= 2^63
   // (the key is (double)(int64_t) of torus words): |sum| <= 2^(ceil log2(2L) + log2 N + BG - 1 + 63).  Below 2^83 the rounding needs no
@@ -446,6 +454,31 @@ __global__ __launch_bounds__(F::THREADS, 2) void pbs_kernel(PbsParams p) {
         // the pairs gain nothing here (experiments/README.md round 4): production instantiates pbs_kernel on the register-twiddle transforms
         if constexpr (F::kLtw && F::kForward2 && L % 2 == 0) cmux_rows2<F, L, BG>(w_lo, w_hi, ext, q, o_re, o_im, xch, fft, bkrow, Bg_bit, t);
         else cmux_rows<F, L, BG>(w_lo, w_hi, ext, q, o_re, o_im, xch, fft, bkrow, Bg_bit, t);
+        if constexpr (BYC) {
+          // (the slot addresses are made inside the step: hoisted out of the loop over the key they would hold 32 registers and spill, like cmux_digits' rotated addresses)
+          int here = 0;
+          asm volatile("" : "+s"(here));
+          d2 *__restrict__ mine = reinterpret_cast<d2 *>(parked.park) + (size_t)blockIdx.x * (16 * T) + here + t;
+          if (q == 0) {   // S_0 is parked; S_1 starts from zero
+#pragma unroll
+            for (int c = 0; c < 2; c++)
+#pragma unroll
+              for (int m = 0; m < 8; m++) {
+                mine[(c * 8 + m) * T] = d2{o_re[c][m], o_im[c][m]};
+                o_re[c][m] = 0.0;
+                o_im[c][m] = 0.0;
+              }
+          } else {        // S_0 + S_1
+#pragma unroll
+            for (int c = 0; c < 2; c++)
+#pragma unroll
+              for (int m = 0; m < 8; m++) {
+                const d2 s0 = mine[(c * 8 + m) * T];
+                o_re[c][m] = s0.x + o_re[c][m];
+                o_im[c][m] = s0.y + o_im[c][m];
+              }
+          }
+        }
       }
     }
     fft.inverse2(o_re[0], o_im[0], o_re[1], o_im[1], xch, t);
@@ -915,7 +948,7 @@ __device__ __forceinline__ void split_load8(d2 (&v)[8], const d2 *p) {
       : "memory");
 }
 
-template <class F, int L, int BG>
+template <class F, int L, int BG, bool SOLO = false>
 __global__ __launch_bounds__(2 * F::THREADS) void pbs_split_kernel(PbsParams p, SplitParams sp) {
   static_assert(F::kForward2 && F::kLtw && L % 2 == 0 && L >= 2 && L <= 6 && F::THREADS == 128,
                 "the l rows of one accumulator component: l / 4 double phases of pbs_wide_pair_kernel (two pipelined rows per team) and, for l = 2 and 6, one row per team");
@@ -929,11 +962,11 @@ __global__ __launch_bounds__(2 * F::THREADS) void pbs_split_kernel(PbsParams p, 
   __shared__ int mode_s;
   const int tid = threadIdx.x, team = __builtin_amdgcn_readfirstlane(tid / T), t = tid % T;
   d2 *xch = xch_all + (size_t)team * F::XCH_SLOTS;
-  const int h = (int)((blockIdx.x >> 3) & 1u);
-  const size_t b = (size_t)(blockIdx.x >> 4) * 8 + (blockIdx.x & 7u);
+  const int h = SOLO ? 0 : (int)((blockIdx.x >> 3) & 1u);
+  const size_t b = SOLO ? (size_t)blockIdx.x : (size_t)(blockIdx.x >> 4) * 8 + (blockIdx.x & 7u);
   if (b >= (size_t)sp.count) return;
   // ---- pairing ----
-  if (tid == 0) {
+  if (!SOLO && tid == 0) {
     unsigned int *st = sp.state + b;
     int mode;   // 0 paired, 1 alone, 2 leave
     if (sp.limit <= 0) {
@@ -959,10 +992,10 @@ __global__ __launch_bounds__(2 * F::THREADS) void pbs_split_kernel(PbsParams p, 
     }
     mode_s = mode;
   }
-  workgroup_sync();
-  const int mode = mode_s;
+  if (!SOLO) workgroup_sync();
+  const int mode = SOLO ? 1 : mode_s;
   if (mode == 2) return;
-  const bool alone = mode == 1;
+  const bool alone = SOLO || mode == 1;
   const int dp_lo = alone ? 0 : h, dp_hi = alone ? 2 : h + 1;
   d2 *recv = sp.xbuf + ((size_t)b * 2 + (size_t)h) * 2 * M, *send = sp.xbuf + ((size_t)b * 2 + (size_t)(1 - h)) * 2 * M;
 
@@ -1557,7 +1590,7 @@ __global__ __launch_bounds__(2 * F::THREADS) void pbs_ga_wide_kernel(GaParams g,
 //     goes to workgroup 1 (a second slot set), whose team 1 inverse-transforms it and subtracts it from the permuted b.
 // Two exchanges per step; a step is two forward pairs and two inverse transforms deep instead of the three forward phases and two inverse pairs of one CU.
 // ------------------------------------------------------------------------------------------------------------
-template <class F, int L, int BG>
+template <class F, int L, int BG, bool SOLO = false>
 __global__ __launch_bounds__(2 * F::THREADS) void pbs_ga_split_kernel(GaParams g, SplitParams sp) {
   static_assert(F::kForward2 && F::kLtw && L == 4 && F::THREADS == 128, "one double phase = the l = 4 rows of a component / of an automorphism key");
   constexpr int N = F::N, M = F::M, T = F::THREADS, LOG2N2 = F::LOGM + 2, WG = 2 * T;
@@ -1569,10 +1602,10 @@ __global__ __launch_bounds__(2 * F::THREADS) void pbs_ga_split_kernel(GaParams g
   const PbsParams &p = g.p;
   const int tid = threadIdx.x, team = __builtin_amdgcn_readfirstlane(tid / T), t = tid % T;
   d2 *xch = xch_all + (size_t)team * F::XCH_SLOTS;
-  const int h = (int)((blockIdx.x >> 3) & 1u);
-  const size_t b = (size_t)(blockIdx.x >> 4) * 8 + (blockIdx.x & 7u);
+  const int h = SOLO ? 0 : (int)((blockIdx.x >> 3) & 1u);
+  const size_t b = SOLO ? (size_t)blockIdx.x : (size_t)(blockIdx.x >> 4) * 8 + (blockIdx.x & 7u);
   if (b >= (size_t)sp.count) return;
-  if (tid == 0) {   // pairing: see pbs_split_kernel
+  if (!SOLO && tid == 0) {   // pairing: see pbs_split_kernel
     unsigned int *st = sp.state + b;
     int mode;
     if (sp.limit <= 0) {
@@ -1598,10 +1631,10 @@ __global__ __launch_bounds__(2 * F::THREADS) void pbs_ga_split_kernel(GaParams g
     }
     mode_s = mode;
   }
-  workgroup_sync();
-  const int mode = mode_s;
+  if (!SOLO) workgroup_sync();
+  const int mode = SOLO ? 1 : mode_s;
   if (mode == 2) return;
-  const bool alone = mode == 1;
+  const bool alone = SOLO || mode == 1;
   const int dp_lo = alone ? 0 : h, dp_hi = alone ? 2 : h + 1;
   d2 *recv_ep = sp.xbuf + ((size_t)b * 2 + (size_t)h) * 2 * M, *send_ep = sp.xbuf + ((size_t)b * 2 + (size_t)(1 - h)) * 2 * M;
   d2 *slot_ks = sp.xbuf + (size_t)sp.count * 4 * M + (size_t)b * 2 * M;   // [2 parities][M]: workgroup 0's team 1 -> workgroup 1's team 1

@@ -131,6 +131,7 @@ struct mosfhet_hip_bsk {
   size_t bytes = 0;
   bool general = false;       // k > 1 or a ring without a tuned kernel: natural slot order, general_kernels.h (bootstraps and external products only)
   bool owns = true;           // false: d_bk belongs to the caller (mosfhet_hip_bsk_view_create)
+  int order = MOSFHET_HIP_ORDER_AUTO;   // summation order of the external products (mosfhet_hip_bsk_set_product_order): read by the launchers through bootstrap_plan
   ~mosfhet_hip_bsk() {
     if (ctx) (void)hipSetDevice(ctx->device);
     if (d_bk && owns) (void)hipFree(d_bk);
@@ -573,13 +574,19 @@ extern "C" int mosfhet_hip_ep_kernel_info(int i, const char **name, int *scratch
 // ones finish, the phases smear out and the sharing collapses (4096 bootstraps at lvl2 in one launch: L2 hit rate 52 %, 318 GB of
 // fabric reads; one round alone: 96 %, 7 GB).  Kernel boundaries re-align the teams: 79 -> 74 ms.  A round = CUs x resident teams
 // per CU (LDS-limited: 4 at N = 2048, 2 at N = 4096).  MOSFHET_HIP_ROUND_CHUNK overrides (0 = single launch).
-static int round_chunk(int threads) {
+static int round_chunk_setting() {
   static std::atomic<int> env{-2};
   int e = env.load(std::memory_order_relaxed);
   if (e == -2) { const char *v = getenv("MOSFHET_HIP_ROUND_CHUNK"); e = v ? atoi(v) : -1; if (e < -1) e = -1; env.store(e, std::memory_order_relaxed); }
+  return e;
+}
+static int round_chunk_for(int threads, int cus) {
+  const int e = round_chunk_setting();
   if (e >= 0) return e;
-  const int cus = device_cus();   // of the current device (several devices in one process: mosfhet_compat_multi.c)
   return threads == 128 ? 4 * (cus > 0 ? cus : 256) : 0;   // N = 4096 (2 teams per CU) measured slower in rounds (tail idling): single launch
+}
+static int round_chunk(int threads) {
+  return round_chunk_for(threads, device_cus());   // of the current device (several devices in one process: mosfhet_compat_multi.c)
 }
 
 // Teams of one residency round re-align every K CMUX steps (pace_teams, bootstrap_kernels.h): kernel boundaries alone leave them drifting apart inside
@@ -650,8 +657,9 @@ extern "C" int mosfhet_hip_pace_skip_credit(mosfhet_hip_ctx_t ctx, int *credit) 
 // b / rows and test vector b % rows of ONE shared set): rounds of whole inputs.
 static PbsParams &pbs_part(PbsParams &p) { return p; }
 template <class P> static PbsParams &pbs_part(P &q) { return q.p; }
-template <int N, class K, class P>
-static void launch_rounds(K kernel, int threads, const P &prm, int count, int step, bool pace, hipStream_t s) {
+// lds, extra: dynamic LDS of the kernel (its attribute is the caller's business) and further kernel arguments behind the parameter struct.
+template <int N, class K, class P, class... X>
+static void launch_rounds(K kernel, int threads, const P &prm, int count, int step, bool pace, hipStream_t s, size_t lds = 0, const X &...extra) {
   P q = prm;
   PbsParams &qp = pbs_part(q);
   const PbsParams p = qp;   // the whole batch's pointers
@@ -665,7 +673,7 @@ static void launch_rounds(K kernel, int threads, const P &prm, int count, int st
     qp.out = p.out + (size_t)lo * out_row;
     qp.tv = rows > 1 ? p.tv : (p.tv ? p.tv + (size_t)lo * p.tv_stride : p.tv);
     const int c = count - lo < step ? count - lo : step;
-    hipLaunchKernelGGL(kernel, dim3((unsigned)c), dim3(threads), 0, s, q);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)c), dim3(threads), lds, s, q, extra...);
   }
 }
 
@@ -676,7 +684,7 @@ static void launch_pbs(const PbsParams &p_in, int count, hipStream_t s) {
   const bool pace = F::THREADS > 64 && pace_every() > 0 && chunk > 0 && count >= 64;   // (all teams of a launch of <= chunk are resident)
   p.pace_every = pace ? pace_every() : 0;
   p.pace_limit = pace_limit();
-  launch_rounds<F::N>(pbs_kernel<F, L, BG>, F::THREADS, p, count, chunk, pace, s);
+  launch_rounds<F::N>(pbs_kernel<F, L, BG>, F::THREADS, p, count, chunk, pace, s, 0, ParkArg<false>());
 }
 
 // pbs_kernel: gadget bases of the reference's parameter sets get a compile-time instantiation (test/benchmark.c:53-75, test/tests.c:37-62,967); anything else
@@ -747,7 +755,7 @@ constexpr bool wide_pair_gadgets(int, int L, int BG) { return L % 2 == 0 && (BG 
 // MOSFHET_HIP_SPLIT_MAX: largest batch that takes it (-1 = CUs / 2, the default; 0 = never).  The ONE switch of this library that changes bits: the split kernel sums
 // the external product per accumulator component (see the kernel), within FFT rounding of every other kernel's order.
 static std::atomic<int> g_split_max{-2};
-static int split_max_batch() {
+static int split_max_setting() {
   int v = g_split_max.load(std::memory_order_relaxed);
   if (v == -2) {
     const char *e = getenv("MOSFHET_HIP_SPLIT_MAX");
@@ -755,7 +763,11 @@ static int split_max_batch() {
     if (v < -1) v = -1;
     g_split_max.store(v, std::memory_order_relaxed);
   }
-  return v < 0 ? device_cus() / 2 : v;
+  return v;
+}
+static int split_max_batch(int cus) {
+  const int v = split_max_setting();
+  return v < 0 ? cus / 2 : v;
 }
 extern "C" int mosfhet_hip_set_split_max_batch(int max_batch) {
   g_split_max = max_batch < -1 ? -1 : max_batch;
@@ -892,16 +904,182 @@ extern "C" int mosfhet_hip_split_last_launch(int *count, int *paired, int *alone
   return MOSFHET_HIP_OK;
 }
 
+// pbs_ga_split_kernel (N = 2048): 4 x 2^9; run-time gadget l = 4
+constexpr bool ga_split_gadgets(int, int L, int BG) { return L == 4 && (BG == 0 || BG == 9); }
+
+// ---- which kernel family a bootstrap launch takes: the ONE place that decides it, for the launchers below and for mosfhet_hip_bootstrap_plan ----
+// The key's summation order (mosfhet_hip.h: MOSFHET_HIP_ORDER_*) governs the families in which AUTO can take a by-component kernel for some batch size:
+// N = 2048 with split_gadgets (plain) / ga_split_gadgets (Galois).  There REFERENCE never takes a split kernel and BY_COMPONENT never takes anything else than a
+// by-component kernel: the split kernel while the batch is small enough for two CUs each (speed only), else its one-CU form (SOLO) up to wide_team_max_batch, and
+// beyond that the by-component form of the throughput kernel (pbs_kernel<.., BYC>; the Galois family has none and runs the one-CU form in residency rounds of one
+// workgroup per CU, 137 KiB of LDS each).
+struct BootstrapPlan { int family, by_component, rounds; };
+static bool order_governs(int N, int l, bool galois) {
+  return N == 2048 && l >= 1 && l <= 6 && (galois ? ga_split_gadgets(N, l, 0) : split_gadgets(N, l, 0));
+}
+static int rounds_of(int count, int step, int rows) {
+  if (step <= 0 || count <= step) return 1;
+  step = step < rows ? rows : step - step % rows;   // launch_rounds: rounds of whole inputs
+  return (count + step - 1) / step;
+}
+// one-CU by-component kernels per launch: as many as the device has CUs (MOSFHET_HIP_ROUND_CHUNK overrides, 0 = one launch)
+static int solo_round_chunk(int cus) {
+  const int e = round_chunk_setting();
+  return e >= 0 ? e : (cus > 0 ? cus : 256);
+}
+// workgroups per launch of the throughput by-component kernel: the throughput kernel's residency round where the key does not fit the L2s; never more than
+// PARK_MAX_WORKGROUPS, which bounds its parking memory (32 KiB per workgroup of a launch: 128 MiB) whatever the batch
+constexpr int PARK_MAX_WORKGROUPS = 4096;
+static int bycomp_chunk(int cus, bool big_key) {
+  const int c = big_key ? round_chunk_for(128, cus) : 0;
+  return c > 0 && c < PARK_MAX_WORKGROUPS ? c : PARK_MAX_WORKGROUPS;
+}
+// count: workgroups of the one-team kernels (ciphertexts x accumulator rows); big_key: the key does not fit the L2s (the throughput kernel then runs in residency rounds)
+static BootstrapPlan bootstrap_plan(int N, int l, int count, int rows, bool galois, int order, int cus, bool big_key) {
+  BootstrapPlan r = {MOSFHET_HIP_FAMILY_THROUGHPUT, 0, 1};
+  if (rows < 1) rows = 1;
+  const int latency_max = N == 1024 ? team_max_batch() : (N == 2048 ? wide_team_max_batch() : (galois ? 0 : wide_team_max_batch() / 2));
+  if (order_governs(N, l, galois)) {
+    // (the plain family reaches its split kernel through the latency launcher: wide_team_max_batch = 0 switches both off; the Galois family asks split_max_batch alone)
+    const bool two_cus = order != MOSFHET_HIP_ORDER_REFERENCE && count <= split_max_batch(cus) && (galois || count <= latency_max);
+    if (two_cus) return BootstrapPlan{MOSFHET_HIP_FAMILY_SPLIT, 1, 1};
+    if (order == MOSFHET_HIP_ORDER_BY_COMPONENT) {
+      if (count <= latency_max) return BootstrapPlan{MOSFHET_HIP_FAMILY_LATENCY_BY_COMPONENT, 1, 1};
+      // plain family: pbs_kernel<.., BYC>, the throughput kernel's residency rounds; Galois family: the one-CU kernel in rounds of one workgroup per CU
+      if (!galois) return BootstrapPlan{MOSFHET_HIP_FAMILY_THROUGHPUT_BY_COMPONENT, 1, rounds_of(count, bycomp_chunk(cus, big_key), rows)};
+      return BootstrapPlan{MOSFHET_HIP_FAMILY_THROUGHPUT_BY_COMPONENT, 1, rounds_of(count, solo_round_chunk(cus), rows)};
+    }
+  }
+  if (count <= latency_max) { r.family = MOSFHET_HIP_FAMILY_LATENCY; return r; }
+  // launch_pbs / launch_ga: rounds at N = 2048 only (two-wavefront teams; N = 4096 measured slower in rounds: round_chunk)
+  if (N == 2048 && (galois || big_key)) r.rounds = rounds_of(count, round_chunk_for(128, cus), rows);
+  return r;
+}
+extern "C" int mosfhet_hip_bootstrap_plan(int N, int l, int Bg_bit, int count, int rows, int galois, int order, int cus, int plan[4]) {
+  if (!plan || !ring_ok(N) || l < 1 || l > 6 || Bg_bit < 1 || l * Bg_bit >= 64 || count < 1 || rows < 1 || cus < 1)
+    return fail(MOSFHET_HIP_EINVAL, "bootstrap_plan: bad shape (N = %d, l = %d, Bg_bit = %d, count = %d, rows = %d, cus = %d)", N, l, Bg_bit, count, rows, cus);
+  if (order < MOSFHET_HIP_ORDER_AUTO || order > MOSFHET_HIP_ORDER_BY_COMPONENT) return fail(MOSFHET_HIP_EINVAL, "bootstrap_plan: unknown product order %d", order);
+  const BootstrapPlan r = bootstrap_plan(N, l, count, rows, galois != 0, order, cus, true);
+  plan[0] = r.family; plan[1] = r.by_component; plan[2] = r.rounds; plan[3] = 0;
+  return MOSFHET_HIP_OK;
+}
+extern "C" int mosfhet_hip_bsk_set_product_order(mosfhet_hip_bsk_t bsk, int order) {
+  if (!bsk) return fail(MOSFHET_HIP_EINVAL, "bsk_set_product_order: null key");
+  if (order < MOSFHET_HIP_ORDER_AUTO || order > MOSFHET_HIP_ORDER_BY_COMPONENT)
+    return fail(MOSFHET_HIP_EINVAL, "bsk_set_product_order: unknown order %d (0 auto, 1 reference, 2 by component)", order);
+  bsk->order = order;
+  return MOSFHET_HIP_OK;
+}
+extern "C" int mosfhet_hip_bsk_get_product_order(mosfhet_hip_bsk_t bsk, int *order) {
+  if (!bsk || !order) return fail(MOSFHET_HIP_EINVAL, "bsk_get_product_order: null argument");
+  *order = bsk->order;
+  return MOSFHET_HIP_OK;
+}
+
+// The one-CU by-component kernels (pbs_split_kernel / pbs_ga_split_kernel with SOLO: one workgroup per bootstrap, no partner, no pairing word, no exchange slots),
+// `step` per launch (0: one launch).
+template <class K, class P>
+static int launch_solo(K kernel, const P &prm, int count, int step, hipStream_t s) {
+  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPairLds));
+  SplitParams sp;
+  sp.xbuf = nullptr;
+  sp.state = nullptr;
+  sp.count = count;   // (every launch of a round has at most this many workgroups)
+  sp.limit = 0;
+  launch_rounds<2048>(kernel, 2 * Fft2048L::THREADS, prm, count, step, false, s, kPairLds, sp);
+  return launched();
+}
+
+// Parking memory of pbs_kernel<.., BYC> (32 KiB per workgroup of a launch): one buffer per (host thread, device, stream), like the split kernels' exchange slots -- launches
+// on one stream are ordered, launches of one thread on different streams (the host-struct pipeline's two) may overlap and must not share it.  PARK_SETS per thread; a
+// further stream takes over the least recently used one once everything queued on its device has finished.
+constexpr int PARK_SETS = 8;
+struct ParkSet { int device = -1; hipStream_t stream = nullptr; uint64_t *buf = nullptr; size_t words = 0; unsigned long long used = 0; };
+struct ParkSets {
+  ParkSet set[PARK_SETS];
+  ~ParkSets() {
+    for (ParkSet &x : set)
+      if (x.buf && hipSetDevice(x.device) == hipSuccess) (void)hipFree(x.buf);
+  }
+};
+static thread_local ParkSets t_park;
+// nullptr: no memory for it (the caller runs the one-CU form instead: same bits).  An allocation happens when a stream's first such launch comes or a larger one
+// (hipMalloc / hipFree synchronise the device and cannot run inside a stream capture, like every growable buffer of this library: warm the shape up outside the capture).
+static std::atomic<int> g_park_on{1};
+extern "C" int mosfhet_hip_set_bycomp_parking(int on) {
+  g_park_on = on ? 1 : 0;
+  return MOSFHET_HIP_OK;
+}
+static double *park_get(hipStream_t s, size_t words) {
+  if (!g_park_on.load(std::memory_order_relaxed)) return nullptr;
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+  static thread_local unsigned long long tick = 0;
+  ParkSet *hit = nullptr, *free_slot = nullptr, *oldest = nullptr;
+  for (ParkSet &x : t_park.set) {
+    if (x.buf && x.device == dev && x.stream == s) hit = &x;
+    if (!x.buf && !free_slot) free_slot = &x;
+    if (x.buf && (!oldest || x.used < oldest->used)) oldest = &x;
+  }
+  if (!hit) {
+    hit = free_slot ? free_slot : oldest;
+    if (hit->buf) {   // changes hands: hipFree waits for the work in flight on its device; the caller's device is current again on every way out
+      const bool ok = hipSetDevice(hit->device) == hipSuccess && hipFree(hit->buf) == hipSuccess;
+      const bool back = hipSetDevice(dev) == hipSuccess;
+      if (!ok || !back) { (void)hipGetLastError(); return nullptr; }
+      hit->buf = nullptr;
+      hit->words = 0;
+    }
+    hit->device = dev;
+    hit->stream = s;
+  }
+  if (hit->words < words) {
+    if (hit->buf) (void)hipFree(hit->buf);
+    hit->buf = nullptr;
+    hit->words = 0;
+    if (hipMalloc((void **)&hit->buf, words * sizeof(uint64_t)) != hipSuccess) { (void)hipGetLastError(); hit->buf = nullptr; return nullptr; }
+    hit->words = words;
+  }
+  hit->used = ++tick;
+  return reinterpret_cast<double *>(hit->buf);
+}
+// pbs_kernel<Fft2048, L, BG, BYC = true>: split_gadgets' instantiations, the residency rounds and pacing of launch_pbs.  *taken = false: no parking memory, the caller
+// goes on to the one-CU form.
+template <int L, int BG>
+static int launch_pbs_bycomp(const PbsParams &p_in, int count, hipStream_t s, bool *taken) {
+  using F = Fft2048;
+  *taken = false;
+  PbsParams p = p_in;
+  const bool big_key = p.count < 0;
+  const int chunk = bycomp_chunk(device_cus(), big_key);
+  const bool pace = big_key && round_chunk(F::THREADS) > 0 && pace_every() > 0 && count >= 64;   // (all teams of a launch resident: launch_pbs)
+  p.pace_every = pace ? pace_every() : 0;
+  p.pace_limit = pace_limit();
+  const int rows = p.rows > 1 ? p.rows : 1;
+  const int per_launch = count > chunk ? (chunk > rows ? chunk : rows) : count;   // (launch_rounds: rounds of whole inputs, never more than this)
+  double *park = park_get(s, (size_t)per_launch * 32 * F::THREADS);
+  if (!park) return MOSFHET_HIP_OK;
+  launch_rounds<F::N>(pbs_kernel<F, L, BG, true>, F::THREADS, p, count, chunk, pace, s, 0, ParkArg<true>{park});
+  *taken = true;
+  return launched();
+}
+
 template <class F>
-static int launch_wide_team_f(int l, int Bg, const PbsParams &p, int count, hipStream_t s, bool bounded) {
+static int launch_wide_team_f(int l, int Bg, const PbsParams &p, int count, hipStream_t s, bool bounded, const BootstrapPlan &plan, int order) {
   if constexpr (F::N == 2048) {
     // at most half the CUs' worth of ciphertexts, even gadget lengths up to 6: two CUs per bootstrap (pbs_split_kernel)
-    if (split_gadgets(F::N, l, 0) && count <= split_max_batch()) {
+    if (plan.family == MOSFHET_HIP_FAMILY_SPLIT) {
       bool taken = false;
       const int rc = gadget_dispatch<F::N, split_gadgets>(l, Bg, bounded, [&](auto L, auto BG) {
         return launch_split(pbs_split_kernel<Fft2048L, L, BG>, p, (size_t)2 * 2 * Fft2048L::M * 2, count, s, &taken);
       });
       if (rc != MOSFHET_HIP_OK || taken) return rc;
+    }
+    // a by-component key beyond the split kernel's batches, or without exchange slots: the same order on one CU
+    if (plan.family == MOSFHET_HIP_FAMILY_LATENCY_BY_COMPONENT || (plan.family == MOSFHET_HIP_FAMILY_SPLIT && order == MOSFHET_HIP_ORDER_BY_COMPONENT)) {
+      return gadget_dispatch<F::N, split_gadgets>(l, Bg, bounded, [&](auto L, auto BG) {
+        return launch_solo(pbs_split_kernel<Fft2048L, L, BG, true>, p, count, 0, s);
+      });
     }
     // one workgroup per CU (137 KiB of LDS each): up to as many ciphertexts as the device has CUs; beyond that pbs_wide_team_kernel runs two workgroups per CU
     if (wide_pairs_enabled() && wide_pair_gadgets(F::N, l, 0) && count <= device_cus()) {
@@ -977,8 +1155,10 @@ static int bootstrap_common(const char *who, mosfhet_hip_ctx_t ctx, mosfhet_hip_
   p.skip_init = skip_init;
   p.count = bsk->bytes > ((size_t)96 << 20) ? -1 : 0;   // launch hint: split into residency rounds (launch_pbs)
   p.rows = rows;
+  const BootstrapPlan plan = bootstrap_plan(bsk->N, bsk->l, count, rows, false, bsk->order, device_cus(), p.count < 0);
+  const bool latency = plan.family != MOSFHET_HIP_FAMILY_THROUGHPUT && plan.family != MOSFHET_HIP_FAMILY_THROUGHPUT_BY_COMPONENT;
   // small batches: the latency-oriented team kernel (one workgroup of 2l wavefronts per ciphertext), N = 1024
-  if (bsk->N == 1024 && rows == 1 && count <= team_max_batch() && team_gadgets(bsk->N, bsk->l, 0)) {
+  if (bsk->N == 1024 && rows == 1 && latency && team_gadgets(bsk->N, bsk->l, 0)) {
     hipStream_t s = pick(ctx, stream);
     return gadget_dispatch<1024, team_gadgets>(bsk->l, bsk->Bg_bit, bsk->owns, [&](auto L, auto BG) {
       hipLaunchKernelGGL((pbs_team_kernel<L, BG>), dim3((unsigned)count), dim3(64 * 2 * L), 0, s, p);
@@ -987,9 +1167,19 @@ static int bootstrap_common(const char *who, mosfhet_hip_ctx_t ctx, mosfhet_hip_
   }
   // (count = workgroups: ciphertexts x accumulator rows; N = 4096: 136 KiB of LDS, one workgroup per CU -- half the batch)
   // N = 1024: what pbs_team_kernel (above) does not take -- gadgets longer than 4, TRGSW accumulator rows
-  if (bsk->N == 1024 && (!team_gadgets(bsk->N, bsk->l, 0) || rows > 1) && count <= team_max_batch()) return launch_wide_team_f<Fft1024>(bsk->l, bsk->Bg_bit, p, count, pick(ctx, stream), bsk->owns);
-  if (bsk->N == 2048 && count <= wide_team_max_batch()) return launch_wide_team_f<Fft2048>(bsk->l, bsk->Bg_bit, p, count, pick(ctx, stream), bsk->owns);
-  if (bsk->N == 4096 && count <= wide_team_max_batch() / 2) return launch_wide_team_f<Fft4096>(bsk->l, bsk->Bg_bit, p, count, pick(ctx, stream), bsk->owns);
+  if (bsk->N == 1024 && latency) return launch_wide_team_f<Fft1024>(bsk->l, bsk->Bg_bit, p, count, pick(ctx, stream), bsk->owns, plan, bsk->order);
+  if (bsk->N == 2048 && latency) return launch_wide_team_f<Fft2048>(bsk->l, bsk->Bg_bit, p, count, pick(ctx, stream), bsk->owns, plan, bsk->order);
+  if (bsk->N == 4096 && latency) return launch_wide_team_f<Fft4096>(bsk->l, bsk->Bg_bit, p, count, pick(ctx, stream), bsk->owns, plan, bsk->order);
+  // a by-component key's large batches: the by-component form of the throughput kernel
+  if (plan.family == MOSFHET_HIP_FAMILY_THROUGHPUT_BY_COMPONENT) {
+    hipStream_t s = pick(ctx, stream);
+    return gadget_dispatch<2048, split_gadgets>(bsk->l, bsk->Bg_bit, bsk->owns, [&](auto L, auto BG) {
+      bool taken = false;
+      const int rc = launch_pbs_bycomp<L, BG>(p, count, s, &taken);
+      if (rc != MOSFHET_HIP_OK || taken) return rc;
+      return launch_solo(pbs_split_kernel<Fft2048L, L, BG, true>, p, count, solo_round_chunk(device_cus()), s);   // no parking memory: the same order on one CU each, in rounds
+    });
+  }
   int rc_pbs = MOSFHET_HIP_OK;
   RING_DISPATCH(ctx, bsk->N, rc_pbs = launch_pbs_f<F>(bsk->l, bsk->Bg_bit, p, count, pick(ctx, stream), bsk->owns));
   return rc_pbs;
@@ -1273,8 +1463,6 @@ static void launch_ga(const GaParams &g_in, int count, hipStream_t s) {
   launch_rounds<F::N>(pbs_ga_kernel<F, L, BG>, F::THREADS, g, count, round, pace, s);
 }
 
-// pbs_ga_split_kernel (N = 2048): 4 x 2^9; run-time gadget l = 4
-constexpr bool ga_split_gadgets(int, int L, int BG) { return L == 4 && (BG == 0 || BG == 9); }
 // pbs_ga_kernel: the reference gadgets (no 1 x 23); run-time gadgets l = 1 .. 6.  N = 2048, 4 x 2^9 runs on Fft2048L (launch_ga_f).
 constexpr bool ga_gadgets(int N, int L, int BG) { return BG == 0 || reference_gadget(N, L, BG); }
 
@@ -1282,10 +1470,12 @@ constexpr bool ga_gadgets(int N, int L, int BG) { return BG == 0 || reference_ga
 // kernels (pbs_ga_kernel, pbs_ga_wide_kernel, pbs_ga_split_kernel) always round with round_mod_2_64, whatever the instantiation
 // (tests/test_gpu_parity.py: test_unbounded_key_views_take_the_reducing_kernels).
 template <class F>
-static int launch_ga_f(int l, int Bg_bit, const GaParams &g, int count, hipStream_t s) {
+static int launch_ga_f(int l, int Bg_bit, const GaParams &g, int count, hipStream_t s, int order) {
+  // (mode 1, the stand-alone automorphism, has no external product: nothing for the order to govern, and it never took the latency kernels)
+  const BootstrapPlan plan = g.mode == 0 ? bootstrap_plan(F::N, l, count, 1, true, order, device_cus(), true) : BootstrapPlan{MOSFHET_HIP_FAMILY_THROUGHPUT, 0, 1};
   // at most half the CUs' worth of ciphertexts at N = 2048, l = 4: two CUs per bootstrap (pbs_ga_split_kernel; the external products in pbs_split_kernel's summation order)
   if constexpr (F::N == 2048) {
-    if (g.mode == 0 && ga_split_gadgets(F::N, l, 0) && count <= split_max_batch()) {
+    if (plan.family == MOSFHET_HIP_FAMILY_SPLIT) {
       GaParams gs = g;
       gs.p.Bg_bit = Bg_bit;
       bool taken = false;
@@ -1294,10 +1484,19 @@ static int launch_ga_f(int l, int Bg_bit, const GaParams &g, int count, hipStrea
       });
       if (rc != MOSFHET_HIP_OK || taken) return rc;
     }
+    // a by-component key beyond the split kernel's batches, or without exchange slots: the same order on one CU, large batches in residency rounds
+    if (plan.by_component && (plan.family != MOSFHET_HIP_FAMILY_SPLIT || order == MOSFHET_HIP_ORDER_BY_COMPONENT)) {
+      GaParams gs = g;
+      gs.p.Bg_bit = Bg_bit;
+      const int step = plan.family == MOSFHET_HIP_FAMILY_THROUGHPUT_BY_COMPONENT ? solo_round_chunk(device_cus()) : 0;
+      return gadget_dispatch<F::N, ga_split_gadgets>(l, Bg_bit, true, [&](auto L, auto BG) {
+        return launch_solo(pbs_ga_split_kernel<Fft2048L, L, BG, true>, gs, count, step, s);
+      });
+    }
   }
   // few ciphertexts: two transform teams per ciphertext (pbs_ga_wide_kernel, bit-identical; the switch-overs of the plain bootstrap's latency kernels)
   if constexpr (F::N <= 2048) {
-    if (g.mode == 0 && count <= (F::N == 1024 ? team_max_batch() : wide_team_max_batch())) {
+    if (plan.family != MOSFHET_HIP_FAMILY_THROUGHPUT && count <= (F::N == 1024 ? team_max_batch() : wide_team_max_batch())) {   // (a split launch without slots: as before)
       GaParams gw = g;
       gw.p.Bg_bit = Bg_bit;
       return launch_dyn_lds(pbs_ga_wide_kernel<F>, dim3((unsigned)count), dim3(2 * F::THREADS), kWideLds<F>, s, gw, l);
@@ -1329,7 +1528,7 @@ extern "C" int mosfhet_hip_trlwe_eval_automorphism_batch(mosfhet_hip_ctx_t ctx, 
   g.gen = gen;
   g.entry = -1;
   int rc_ga = MOSFHET_HIP_OK;
-  RING_DISPATCH(ctx, gak->N, rc_ga = launch_ga_f<F>(gak->t, gak->base_bit, g, count, pick(ctx, stream)));
+  RING_DISPATCH(ctx, gak->N, rc_ga = launch_ga_f<F>(gak->t, gak->base_bit, g, count, pick(ctx, stream), MOSFHET_HIP_ORDER_AUTO));   // (mode 1: no external product, nothing to govern)
   return rc_ga;
 }
 
@@ -1360,7 +1559,7 @@ extern "C" int mosfhet_hip_functional_bootstrap_ga_batch(mosfhet_hip_ctx_t ctx, 
   g.ak = gak->d_ak;
   g.mode = 0;
   int rc_ga = MOSFHET_HIP_OK;
-  RING_DISPATCH(ctx, bsk->N, rc_ga = launch_ga_f<F>(bsk->l, bsk->Bg_bit, g, count, pick(ctx, stream)));
+  RING_DISPATCH(ctx, bsk->N, rc_ga = launch_ga_f<F>(bsk->l, bsk->Bg_bit, g, count, pick(ctx, stream), bsk->order));
   return rc_ga;
 }
 

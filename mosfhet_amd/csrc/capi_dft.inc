@@ -87,7 +87,7 @@ extern "C" int mosfhet_hip_blind_rotate_ga_batch(mosfhet_hip_ctx_t ctx, mosfhet_
   g.mode = 0;
   g.entry = -1;
   int rc_ga = MOSFHET_HIP_OK;
-  RING_DISPATCH(ctx, bsk->N, rc_ga = launch_ga_f<F>(bsk->l, bsk->Bg_bit, g, count, pick(ctx, stream)));
+  RING_DISPATCH(ctx, bsk->N, rc_ga = launch_ga_f<F>(bsk->l, bsk->Bg_bit, g, count, pick(ctx, stream), bsk->order));
   return rc_ga;
 }
 
@@ -110,7 +110,7 @@ extern "C" int mosfhet_hip_trlwe_eval_automorphism_entry_batch(mosfhet_hip_ctx_t
   g.gen = gen;
   g.entry = entry;
   int rc_ga = MOSFHET_HIP_OK;
-  RING_DISPATCH(ctx, gak->N, rc_ga = launch_ga_f<F>(gak->t, gak->base_bit, g, count, pick(ctx, stream)));
+  RING_DISPATCH(ctx, gak->N, rc_ga = launch_ga_f<F>(gak->t, gak->base_bit, g, count, pick(ctx, stream), MOSFHET_HIP_ORDER_AUTO));   // (mode 1: no external product)
   return rc_ga;
 }
 

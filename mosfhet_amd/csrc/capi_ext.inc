@@ -1248,6 +1248,7 @@ extern "C" int mosfhet_hip_bsk_clone(mosfhet_hip_ctx_t dst_ctx, mosfhet_hip_bsk_
   mosfhet_hip_bsk *b = b_owner.get();
   b->ctx = dst_ctx; b->n = src->n; b->k = src->k; b->N = src->N; b->l = src->l; b->Bg_bit = src->Bg_bit;
   b->unfolding = src->unfolding; b->bytes = src->bytes; b->general = src->general;
+  b->order = src->order;   // replicas sum alike (mosfhet_hip_bsk_set_product_order)
   int rc;
   if (src->unfolding > 1) {
     HIP_TRY(hipMalloc((void **)&b->d_su, b->bytes));

@@ -35,6 +35,7 @@ extern int hipGetDevice(int *device);
 #define HIP_D2D 3
 
 /* mosfhet_compat.c */
+MC_HIDDEN int mc_order_of_block(const double *blk);             /* MOSFHET_HIP_ORDER_* of the live bootstrap key whose device entries hold blk (AUTO: none) */
 MC_HIDDEN void mc_die(const char *what);                       /* prints the C ABI's last error and aborts (the reference's assert / exit behaviour) */
 MC_HIDDEN void *mc_xmalloc(size_t sz);                         /* 64-byte aligned, exits on failure (src/misc.c:115-128) */
 MC_HIDDEN void *mc_dev_alloc(size_t bytes);                    /* hipMalloc on the engine's device, aborts on failure */
@@ -58,6 +59,7 @@ MC_HIDDEN mosfhet_hip_ctx_t mc_ctx_of(int d);      /* context of device index d 
 MC_HIDDEN void mc_devices_from_env(void);
 MC_HIDDEN void *mc_key_here(void *primary, int kind);   /* the key's handle on the calling thread's device */
 MC_HIDDEN void mc_replicas_free(void *primary);
+MC_HIDDEN void mc_replicas_set_order(void *primary, int order);   /* a bootstrap key's replicas made so far (later ones copy the primary's: mosfhet_hip_bsk_clone) */
 typedef void (*mc_slice_fn)(void *args, int lo, int hi);
 MC_HIDDEN void mc_run_sharded(mc_slice_fn fn, void *args, int count, void *const *keys, const int *kinds, int n_keys);
 

@@ -738,6 +738,19 @@ void mosfhet_gen_bootstrap_key_flat(Torus *out, TRGSW_Key out_key, TLWE_Key in_k
 /* Keys alive in this process, for the one reference signature that names no key (functional_bootstrap_trgsw_phase2, src/bootstrap.c:297). */
 #define MAX_KEYS 64
 static Bootstrap_Key g_keys[MAX_KEYS];
+static void *g_key_handles[MAX_KEYS];   /* engine handles of the live Bootstrap_Key and Bootstrap_GA_Key objects (mc_order_of_block) */
+static void remember_handle(void *dev) {
+  pthread_mutex_lock(&g_lock);
+  for (int i = 0; i < MAX_KEYS; i++)
+    if (!g_key_handles[i] || g_key_handles[i] == dev) { g_key_handles[i] = dev; break; }
+  pthread_mutex_unlock(&g_lock);
+}
+static void forget_handle(void *dev) {
+  pthread_mutex_lock(&g_lock);
+  for (int i = 0; i < MAX_KEYS; i++)
+    if (g_key_handles[i] == dev) g_key_handles[i] = NULL;
+  pthread_mutex_unlock(&g_lock);
+}
 
 static void remember_key(Bootstrap_Key key) {
   pthread_mutex_lock(&g_lock);
@@ -747,6 +760,7 @@ static void remember_key(Bootstrap_Key key) {
   for (int i = 0; i < MAX_KEYS && !seen; i++)
     if (!g_keys[i]) { g_keys[i] = key; seen = 1; }
   pthread_mutex_unlock(&g_lock);
+  remember_handle(key->device);
 }
 
 static void forget_key(Bootstrap_Key key) {
@@ -754,9 +768,33 @@ static void forget_key(Bootstrap_Key key) {
   for (int i = 0; i < MAX_KEYS; i++)
     if (g_keys[i] == key) g_keys[i] = NULL;
   pthread_mutex_unlock(&g_lock);
+  forget_handle(key->device);
 }
 
 void *mosfhet_bootstrap_key_device(Bootstrap_Key key) { return key ? key->device : NULL; }
+
+/* the primary handle first (it validates the value), then the replicas made so far; later replicas copy the primary's */
+static void key_set_product_order(void *device, int order) {
+  if (!device) return;
+  if (mosfhet_hip_bsk_set_product_order((mosfhet_hip_bsk_t)device, order)) mc_die("bootstrap key: product order");
+  mc_replicas_set_order(device, order);
+}
+/* The order of the key a block of TRGSW_DFT entries lies in (blind_rotate(tv, a, key->s, n) and blind_rotate_ga hand over Bootstrap_Key.s, views of the device key: the
+ * temporary key view made over them sums as the key does).  Entries of no live key -- a caller's own TRGSW_DFT array, a gathered copy -- are AUTO. */
+int mc_order_of_block(const double *blk) {
+  int order = MOSFHET_HIP_ORDER_AUTO;
+  pthread_mutex_lock(&g_lock);
+  for (int i = 0; i < MAX_KEYS; i++) {
+    void *dev = g_key_handles[i];
+    if (!dev) continue;
+    const char *base = (const char *)mosfhet_hip_bsk_device_dft((mosfhet_hip_bsk_t)dev);
+    if (base && (const char *)blk >= base && (const char *)blk < base + mosfhet_hip_bsk_bytes((mosfhet_hip_bsk_t)dev)) (void)mosfhet_hip_bsk_get_product_order((mosfhet_hip_bsk_t)dev, &order);
+  }
+  pthread_mutex_unlock(&g_lock);
+  return order;
+}
+void mosfhet_bootstrap_key_set_product_order(Bootstrap_Key key, int order) { if (key) key_set_product_order(key->device, order); }
+void mosfhet_bootstrap_ga_key_set_product_order(Bootstrap_GA_Key key, int order) { if (key) key_set_product_order(key->device, order); }
 
 /* Bootstrap_Key.s: the reference's array of n TRGSW_DFT (src/bootstrap.c:7-19), here n views of the device-resident key */
 static TRGSW_DFT *key_views(void *dev, int n, int l, int Bg_bit, int N) {
@@ -1191,11 +1229,13 @@ Bootstrap_GA_Key new_bootstrap_key_ga(TRGSW_Key out_key, TLWE_Key in_key) {
   res->s = key_views(dev, n, l, out_key->Bg_bit, N);
   res->ak = (TRLWE_KS_Key *)mc_xmalloc(sizeof(TRLWE_KS_Key) * (size_t)N);   /* src/bootstrap_ga.c:10: entry j <-> generator 2j + 1 */
   for (int j = 0; j < N; j++) res->ak[j] = trlwe_ks_header(gak, j, 0, l, out_key->Bg_bit);
+  remember_handle(dev);
   return res;
 }
 
 void free_bootstrap_key_ga(Bootstrap_GA_Key key) {
   if (!key) return;
+  forget_handle(key->device);
   if (key->s) mc_trgsw_dft_views_free(key->s, key->n);
   for (int j = 0; j < key->N; j++) free(key->ak[j]);
   free(key->ak);

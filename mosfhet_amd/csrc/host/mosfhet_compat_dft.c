@@ -233,6 +233,7 @@ void blind_rotate(TRLWE tv, Torus *a, TRGSW_DFT *s, int size) {
   need(tv->b->N == N, "blind_rotate: ring degrees of tv and s differ");
   mosfhet_hip_bsk_t view = NULL;
   if (mosfhet_hip_bsk_view_create(ectx(), &view, blk, size, 1, N, l, Bg_bit)) mc_die("blind_rotate");
+  if (!owned && mosfhet_hip_bsk_set_product_order(view, mc_order_of_block(blk))) mc_die("blind_rotate");   /* Bootstrap_Key.s: the view sums as its key does */
   const size_t acc_w = (size_t)2 * N;
   Torus *h = (Torus *)mc_hstage_alloc(sizeof(Torus) * (acc_w + size + 1)), *d = (Torus *)mc_stage_alloc(sizeof(Torus) * (acc_w + size + 1));
   mc_trlwe_to_flat(h, tv);
@@ -254,6 +255,7 @@ void blind_rotate_ga(TRLWE tv, Torus *a, TRGSW_DFT *s, TRLWE_KS_Key *ak, int siz
   need(ak && ak[0] && ak[0]->device && ak[0]->entry == 0, "blind_rotate_ga: `ak` must be the .ak of a Bootstrap_GA_Key");
   mosfhet_hip_bsk_t view = NULL;
   if (mosfhet_hip_bsk_view_create(ectx(), &view, blk, size, 1, N, l, Bg_bit)) mc_die("blind_rotate_ga");
+  if (!owned && mosfhet_hip_bsk_set_product_order(view, mc_order_of_block(blk))) mc_die("blind_rotate_ga");   /* Bootstrap_Key.s: the view sums as its key does */
   const size_t acc_w = (size_t)2 * N;
   Torus *h = (Torus *)mc_hstage_alloc(sizeof(Torus) * (acc_w + size + 1)), *d = (Torus *)mc_stage_alloc(sizeof(Torus) * (acc_w + size + 1));
   mc_trlwe_to_flat(h, tv);

@@ -123,6 +123,16 @@ void mc_replicas_free(void *primary) {
   pthread_mutex_unlock(&g_rep_lock);
 }
 
+void mc_replicas_set_order(void *primary, int order) {
+  if (!primary) return;
+  pthread_mutex_lock(&g_rep_lock);
+  for (int i = 0; i < MAX_REPLICATED; i++)
+    if (g_reps[i].primary == primary && g_reps[i].kind == MC_KEY_BSK)
+      for (int d = 1; d < MC_MAX_DEVICES; d++)
+        if (g_reps[i].rep[d] && mosfhet_hip_bsk_set_product_order((mosfhet_hip_bsk_t)g_reps[i].rep[d], order)) mc_die("bootstrap key: product order");
+  pthread_mutex_unlock(&g_rep_lock);
+}
+
 typedef struct { mc_slice_fn fn; void *args; int lo, hi; } Job;
 
 /* one persistent host thread per extra device (its staging buffers, streams and device pool live as long as the process): a sharded call hands

@@ -74,6 +74,18 @@ def _ptr(t):
     return C.c_void_p(t.data_ptr())
 
 
+PRODUCT_ORDERS = ("auto", "reference", "by_component")                                                           # MOSFHET_HIP_ORDER_*
+KERNEL_FAMILIES = ("throughput", "latency", "split", "latency_by_component", "throughput_by_component")         # MOSFHET_HIP_FAMILY_*
+
+
+def bootstrap_plan(N, l, Bg_bit, count, order="auto", cus=256, rows=1, galois=False):
+    """Which kernel family a bootstrap launch takes (no device needed; the launchers' own decision at the current batch-threshold setters, `cus` in place of the
+    device's CU count): dict(family, by_component, rounds).  include/mosfhet_hip.h: mosfhet_hip_bootstrap_plan."""
+    plan = (C.c_int * 4)()
+    _check(lib().mosfhet_hip_bootstrap_plan(int(N), int(l), int(Bg_bit), int(count), int(rows), int(bool(galois)), PRODUCT_ORDERS.index(order), int(cus), plan))
+    return dict(family=KERNEL_FAMILIES[plan[0]], by_component=bool(plan[1]), rounds=int(plan[2]))
+
+
 class BootstrapKey:
     def __init__(self, engine, handle, n, k, N, l, Bg_bit):
         self.engine, self.h = engine, handle
@@ -82,6 +94,19 @@ class BootstrapKey:
     @property
     def nbytes(self):
         return lib().mosfhet_hip_bsk_bytes(self.h)
+
+    def set_product_order(self, order):
+        """Summation order of this key's external products: "auto" (the kernel chosen for the batch size decides: the default), "reference" (one chain over all rows:
+        never a split kernel) or "by_component" (the split kernels' order at every batch size).  include/mosfhet_hip.h: mosfhet_hip_bsk_set_product_order."""
+        if order not in PRODUCT_ORDERS:
+            raise MosfhetHipError("product order %r: one of %s" % (order, ", ".join(PRODUCT_ORDERS)))
+        _check(lib().mosfhet_hip_bsk_set_product_order(self.h, PRODUCT_ORDERS.index(order)))
+
+    @property
+    def product_order(self):
+        v = C.c_int(0)
+        _check(lib().mosfhet_hip_bsk_get_product_order(self.h, C.byref(v)))
+        return PRODUCT_ORDERS[v.value]
 
     def export_dft(self):
         out = np.empty((self.n, (self.k + 1) * self.l, self.k + 1, self.N), dtype=np.float64)
@@ -485,6 +510,11 @@ class Engine:
             out = AutomorphismKeys(self, h, key.N, key.t, key.base_bit)
         return out, int(lib().mosfhet_hip_last_clone_route())
 
+    def bootstrap_plan(self, bsk, count, rows=1, galois=False):
+        """bootstrap_plan() for a key of this engine at its product order and this device's CU count."""
+        cus = self.torch.cuda.get_device_properties(self.device).multi_processor_count
+        return bootstrap_plan(bsk.N, bsk.l, bsk.Bg_bit, count, bsk.product_order, cus, rows, galois)
+
     def bootstrap_key_info(self, bsk):
         v = (C.c_int * 6)()
         _check(lib().mosfhet_hip_bsk_info(bsk.h, v))
@@ -751,6 +781,12 @@ def set_split_max_batch(max_batch):
 def set_ks_words(min_count):
     """Table key switches with 2 - 4 digit bits take the word-lane kernel (keyswitch_words_kernels.h) from this many ciphertexts on (default 17, 0 = never; same bits)."""
     _check(lib().mosfhet_hip_set_ks_words(int(min_count)))
+
+
+def set_bycomp_parking(on):
+    """0: a by-component key's large batches run the one-CU by-component kernel in residency rounds, as when the parking memory of the throughput form is refused
+    (same bits, about 1.8 x the time); 1 = default"""
+    _check(lib().mosfhet_hip_set_bycomp_parking(int(bool(on))))
 
 
 def set_split_wait_limit(ticks):

@@ -66,7 +66,7 @@ extern "C" int ab_pbs(const double *d_bk, const double *d_tw, const uint64_t *d_
 #ifdef AB_PACE
     (void)hipMemsetAsync(d_pace, 0, 288 * 4, nullptr);
 #endif
-    hipLaunchKernelGGL((pbs_kernel<ABF, AB_L, AB_BG>), dim3((unsigned)count), dim3(ABF::THREADS), 0, nullptr, p);
+    hipLaunchKernelGGL((pbs_kernel<ABF, AB_L, AB_BG>), dim3((unsigned)count), dim3(ABF::THREADS), 0, nullptr, p, ParkArg<false>());
   }
   hipEventRecord(e1, nullptr);
   if (hipEventSynchronize(e1) != hipSuccess) return -2;

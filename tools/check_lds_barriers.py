@@ -9,7 +9,8 @@ The two-wavefront exchanges (ds_write ; s_barrier ; ds_read ; s_barrier: both wa
 inside one basic block, LDS writes followed by TWO barriers with no LDS read in between mean the reads went behind the barrier that releases the buffer.
 
     python tools/check_lds_barriers.py listing.s [...]        exit status 1 and one line per violation
-    build_and_check()                                          compiles tools/ab/ep_ab.hip in the forms that used to fail and checks them (CPU, seconds)
+    build_and_check()                                          compiles tools/ab/ep_ab.hip in the forms that used to fail, and the one-CU by-component bootstrap
+                                                               kernels (tools/ab/bycomp_ab.hip), and checks them (CPU, seconds)
 """
 import os
 import re
@@ -62,16 +63,22 @@ def check(text):
 FORMS = [("N = 2048, l = 1, pipelined loop (the build that failed)", ["-DAB_N=2048", "-DAB_L=1", "-DAB_BG=23", "-DAB_FORM=2"]),
          ("N = 4096, l = 1, pipelined loop", ["-DAB_N=4096", "-DAB_L=1", "-DAB_BG=22", "-DAB_FORM=2"]),
          ("N = 2048, l = 4, rows in pairs, pipelined loop (lvl2 production)", ["-DAB_N=2048", "-DAB_L=4", "-DAB_BG=9", "-DAB_LTW"]),
-         ("N = 2048, l = 4, plain loop", ["-DAB_N=2048", "-DAB_L=4", "-DAB_BG=9", "-DAB_LTW", "-DAB_FORM=1"])]
+         ("N = 2048, l = 4, plain loop", ["-DAB_N=2048", "-DAB_L=4", "-DAB_BG=9", "-DAB_LTW", "-DAB_FORM=1"]),
+         # the one-CU by-component bootstrap kernels (tools/ab/bycomp_ab.hip): a double phase (l = 4), a double phase and a row per team (l = 6), a row per team (l = 2)
+         ("bootstrap by component on one CU, 4 x 2^9", ["-DAB_L=4", "-DAB_BG=9"], "bycomp_ab.hip"),
+         ("bootstrap by component on one CU, 6 x 2^7", ["-DAB_L=6", "-DAB_BG=7"], "bycomp_ab.hip"),
+         ("bootstrap by component on one CU, l = 2, run-time gadget", ["-DAB_L=2", "-DAB_BG=0"], "bycomp_ab.hip"),
+         ("Galois bootstrap by component on one CU, 4 x 2^9", ["-DAB_L=4", "-DAB_BG=9", "-DAB_GA"], "bycomp_ab.hip"),
+         ("bootstrap by component, throughput form, 4 x 2^9", ["-DAB_L=4", "-DAB_BG=9", "-DAB_TP"], "bycomp_ab.hip")]
 
 
 def build_and_check(forms=FORMS):
     bad = []
     with tempfile.TemporaryDirectory() as tmp:
-        for name, flags in forms:
+        for name, flags, *source in forms:
             s = os.path.join(tmp, "k.s")
             subprocess.check_call(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-Wno-unused-value", "-Wno-comment", "-S", "--cuda-device-only"] + flags +
-                                  [os.path.join(ROOT, "tools", "ab", "ep_ab.hip"), "-o", s], stderr=subprocess.DEVNULL)
+                                  [os.path.join(ROOT, "tools", "ab", source[0] if source else "ep_ab.hip"), "-o", s], stderr=subprocess.DEVNULL)
             text = open(s).read()
             assert "; wave barrier" in text and "s_barrier" in text, "the listing of `%s` has no barriers to check" % name
             bad += [(name,) + v for v in check(text)]

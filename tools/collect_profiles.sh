@@ -11,7 +11,7 @@ for pair in pbs:pbs ep:ep ep2:ep_lvl2 lvl2:lvl2 ks:ks cb:cb unf:unf split:split;
   ks=$(grep -o "trace/[^ )]*kernel_stats.csv" $d/summary.txt | head -1)
   [ -n "$ks" ] && cp $d/$ks profiles/${TAG}_${dst}_kernel_stats.csv
 done
-python tools/make_traffic_json.py profiles/${TAG}_pbs_summary.txt profiles/latest_traffic.json "pbs_kernel<mosfhet::Fft1024, 2, 8>" 4096 > /dev/null
+python tools/make_traffic_json.py profiles/${TAG}_pbs_summary.txt profiles/latest_traffic.json "pbs_kernel<mosfhet::Fft1024, 2, 8" 4096 > /dev/null
 python tools/make_traffic_json.py profiles/${TAG}_ep_summary.txt profiles/latest_traffic_ep.json "external_product_ldskey_kernel<2, 8" 65536 > /dev/null
 python tools/make_traffic_json.py profiles/${TAG}_ep_lvl2_summary.txt profiles/latest_traffic_ep_lvl2.json "external_product_kernel<mosfhet::Fft" 16384 > /dev/null
 grep -h "srchash\|traffic_bytes" profiles/latest_traffic*.json
