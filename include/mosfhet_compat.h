@@ -285,6 +285,13 @@ void tlwe_keyswitch_batch(TLWE *out, TLWE *in, int count, TLWE_KS_Key ks_key);
 void full_domain_functional_bootstrap_batch(TLWE *out, TRLWE tv, TLWE *in, int count, Bootstrap_Key key, TLWE_KS_Key tlwe_ksk,
                                             int precision);
 
+/* Leveled look-up table for `count` independent TRGSW-encrypted inputs against one shared table (new): eval_LUT of the reference's leveled application
+ * (applications/leveled_lut/vertical_packing.c:36-52) with input = inputs[b], for every b.  inputs[b] is an array of `size` samples as
+ * trgsw_alloc_new_DFT_sample_array makes it (bit i of the index at inputs[b][i], least significant first), LUT the reference's array of max(1, 2^size / N) TRLWEs,
+ * LEFT UNCHANGED (the reference's eval_LUT destroys its table).  Synchronous; aborts on error like the rest of this layer.  N = 1024 or 2048.  Runs on the
+ * primary device: it is not cut over the GPUs of mosfhet_set_devices (hence no _batch suffix, which promises that above). */
+void mosfhet_eval_LUT_inputs(TLWE *out, TRGSW_DFT **inputs, int size, TRLWE *LUT, int count);
+
 /* ---- flat helpers used by the Python binding and bench.py (new) ----
  * Generate a whole bootstrap / key-switch key in the flat torus-domain layouts of mosfhet_hip.h. */
 void mosfhet_gen_bootstrap_key_flat(Torus *out /*[n][(k+1)l][k+1][N]*/, TRGSW_Key out_key, TLWE_Key in_key);

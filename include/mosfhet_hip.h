@@ -451,6 +451,37 @@ int mosfhet_hip_keyswitch_functional_bootstrap_batch(mosfhet_hip_ctx_t ctx, mosf
 int mosfhet_hip_cmux_batch(mosfhet_hip_ctx_t ctx, mosfhet_hip_bsk_t bsk, int key_index, uint64_t *d_out /*[count][2][N]*/, const uint64_t *d_in0,
                            const uint64_t *d_in1, int count, void *stream);
 
+/* Leveled look-up-table evaluation for a batch of INDEPENDENT inputs against ONE shared table: eval_LUT of the reference's leveled application
+ * (applications/leveled_lut/vertical_packing.c:36-52) with input = the selectors of input b, for b < count.  (mosfhet_hip_cmux_batch and
+ * mosfhet_hip_blind_rotate_batch share one selector / one key over their batch: one encrypted input, many table copies.)
+ *   d_sel_dft  [count][size][2l][2][N/2] complex, engine slot order: selector i of input b encrypts bit i (least significant first, vertical_packing.c:16-20)
+ *              of b's index -- the layout of `size` consecutive bootstrap-key entries, i.e. what mosfhet_hip_torus_to_dft_batch makes of
+ *              mosfhet_hip_circuit_bootstrap_3_batch's [count * size][2l][2][N]
+ *   d_lut      [n_luts][2][N] torus-domain TRLWEs, n_luts = max(1, 2^size / N), trivial or encrypted; READ ONLY (the reference destroys its table, a batch
+ *              needs it for every input)
+ *   d_out      [count][N + 1]: SampleExtract_0 of the rotated survivor
+ * Per input: tree level i = 0 .. size - log2(N) - 1 halves the table with selector size - i - 1, T[j] <- T[j] + sel (.) (T[j + half] - T[j]); then blind_rotate of
+ * T[0] with a[i] = int2torus(2N - 2^i, log2(2N)) and the first min(size, log2 N) selectors as key; then trlwe_extract_tlwe(.., 0).  Level 0's differences, their
+ * gadget digits and forward transforms are the same for every input and are made once per call.
+ * k = 1, N in {1024, 2048}, 1 <= l <= 6, Bg_bit <= 31, l * Bg_bit < 64, 1 <= size <= log2(N) + MOSFHET_HIP_LUT_MAX_LEVELS; anything else MOSFHET_HIP_EINVAL with a
+ * message, before any HIP call.
+ * Summation order: every external product is one chain over rows 0 .. 2l-1, the reference's order, rounded with the reduction mod 1 (the selectors are
+ * caller-held DFT content without a magnitude bound).  These launches consult no key handle, so the by-component order (MOSFHET_HIP_ORDER_BY_COMPONENT) never
+ * applies here.  No output word depends on count or on the chunking below.
+ * Asynchronous on `stream`.  The prepared table rows and the tree's intermediates live in the CALLING THREAD's pool (one set of buffers per host thread and
+ * device): no allocation and no synchronisation from the second call of a shape on -- and therefore ONE STREAM PER HOST THREAD at a time for this call: a thread
+ * that queues two calls on two streams that may overlap must wait for the first before it issues the second.  (The first call of a larger shape allocates, which
+ * synchronises the device and cannot run inside a stream capture.)
+ * A batch whose intermediates ([count][2^(levels-1)][2][N] words) exceed the workspace bound (1 GiB; mosfhet_hip_set_leveled_lut_workspace, 0 = default; results
+ * do not depend on it) is cut into chunks of whole inputs.  mosfhet_hip_leveled_lut_plan says what the launcher will do, as a pure function (no GPU):
+ * plan = {tree levels = max(0, size - log2 N), first-level nodes = 2^(levels - 1) (0 without a tree), inputs per chunk, workspace bytes}; `cus` (the device's
+ * CU count) sizes the grids only and changes none of the four. */
+#define MOSFHET_HIP_LUT_MAX_LEVELS 10
+int mosfhet_hip_leveled_lut_batch(mosfhet_hip_ctx_t ctx, uint64_t *d_out, const double *d_sel_dft, const uint64_t *d_lut, int size, int N, int l, int Bg_bit,
+                                  int count, void *stream);
+int mosfhet_hip_leveled_lut_plan(int N, int l, int size, int count, int cus, long long *plan /*[4]*/);
+int mosfhet_hip_set_leveled_lut_workspace(long long bytes);
+
 /* Key images for the on-disk formats (save_bootstrap_key / load_new_bootstrap_key src/bootstrap.c:63-104, trlwe_save_KS_key /
  * trlwe_load_new_KS_key src/keyswitch.c:122-160, tlwe_save_KS_key / tlwe_load_new_KS_key src/tlwe.c:247-287, trlwe_save_generic_ks_key /
  * trlwe_load_new_generic_ks_key src/keyswitch.c:409-455).  DFT-domain contents are backend-defined in the reference too (src/polynomial.c:336-357):

@@ -25,6 +25,7 @@
 #include "ext_kernels.h"
 #include "unfold_kernels.h"
 #include "keygen_kernels.h"
+#include "leveled_lut_kernels.h"
 
 using namespace mosfhet;
 
@@ -76,7 +77,7 @@ struct DevBuf {
 // handle: handles are read-only after creation, so any number of host threads may share them, as the reference's callers share its keys
 // (re-entrant through thread-local scratch, src/polynomial.c:269-352).  A thread's launches are ordered by the stream it passes; buffers are
 // released at thread exit (hipFree waits for work in flight).
-enum { POOL_BSK = 0, POOL_EXT0 = 1, POOL_EXT1 = 2, POOL_CTX0 = 3, POOL_UNFOLD = 6, POOL_PACK = 7, POOL_VEC = 8, POOL_VEC2 = 9, POOL_VEC3 = 10, POOL_VEC4 = 11, POOL_SLOTS = 12 };
+enum { POOL_BSK = 0, POOL_EXT0 = 1, POOL_EXT1 = 2, POOL_CTX0 = 3, POOL_UNFOLD = 6, POOL_PACK = 7, POOL_VEC = 8, POOL_VEC2 = 9, POOL_VEC3 = 10, POOL_VEC4 = 11, POOL_LUT = 12, POOL_SLOTS = 13 };
 struct ThreadPool {
   struct Dev {
     int device = -1;
@@ -1721,3 +1722,4 @@ extern "C" int mosfhet_hip_time_programmable_bootstrap(mosfhet_hip_ctx_t ctx, mo
 #include "capi_ext.inc"
 #include "capi_dft.inc"
 #include "capi_vec.inc"
+#include "capi_lut.inc"

@@ -1,0 +1,118 @@
+// capi_lut.inc -- leveled look-up-table evaluation for a batch of independent TRGSW-encrypted inputs (leveled_lut_kernels.h): eval_LUT of
+// applications/leveled_lut/vertical_packing.c:36-52 for `count` inputs against one shared table.  Own code: the reference application is the specification
+// (which selector halves which level, which mask the rotation takes), nothing of it is compiled in.
+//
+// Launches of one chunk of inputs: level 0 (count x first-level nodes units, no forward transform), one launch per deeper tree level, one finishing launch (rotation
+// steps + extraction); in front of the first chunk the table preparation, once per call.  The prepared rows and the intermediates live in the calling thread's
+// pool (slot POOL_LUT): no allocation and no synchronisation from the second call of a shape on, everything queues on the given stream.
+
+// Workspace bound: the prepared rows [half][2l][N/2] complex plus the intermediates [chunk][half][2][N] of one chunk of inputs stay within it; a batch that
+// needs more is cut into chunks of whole inputs.  Results do not depend on it.
+constexpr long long LUT_WORKSPACE_DEFAULT = 1ll << 30;
+static std::atomic<long long> g_lut_workspace{LUT_WORKSPACE_DEFAULT};
+constexpr int LUT_MAX_CHUNK = 32768;   // level 0 indexes the inputs of a chunk by gridDim.y
+
+extern "C" int mosfhet_hip_set_leveled_lut_workspace(long long bytes) {
+  if (bytes < 0) return fail(MOSFHET_HIP_EINVAL, "set_leveled_lut_workspace: bytes = %lld (0 restores the default)", bytes);
+  g_lut_workspace = bytes ? bytes : LUT_WORKSPACE_DEFAULT;
+  return MOSFHET_HIP_OK;
+}
+
+struct LutPlan { int levels, nodes, chunk; long long table_bytes, input_bytes, bytes; };
+
+// The one place that decides the shape of a call: for the launcher and for mosfhet_hip_leveled_lut_plan.
+static int lut_plan(const char *who, int N, int l, int size, int count, int cus, LutPlan *r) {
+  if (N != 1024 && N != 2048) return fail(MOSFHET_HIP_EINVAL, "%s: ring degree N = %d not supported here (1024, 2048)", who, N);
+  if (l < 1 || l > 6) return fail(MOSFHET_HIP_EINVAL, "%s: l = %d (1 .. 6)", who, l);
+  const int log_N = ilog2(N);
+  if (size < 1 || size > log_N + MOSFHET_HIP_LUT_MAX_LEVELS)
+    return fail(MOSFHET_HIP_EINVAL, "%s: size = %d (1 .. log2 N + %d = %d selector bits)", who, size, MOSFHET_HIP_LUT_MAX_LEVELS, log_N + MOSFHET_HIP_LUT_MAX_LEVELS);
+  if (count < 1) return fail(MOSFHET_HIP_EINVAL, "%s: count = %d", who, count);
+  if (cus < 1) return fail(MOSFHET_HIP_EINVAL, "%s: cus = %d", who, cus);
+  r->levels = size > log_N ? size - log_N : 0;
+  r->nodes = r->levels ? 1 << (r->levels - 1) : 0;
+  r->table_bytes = (long long)r->nodes * 2 * l * (N / 2) * (long long)sizeof(d2);
+  r->input_bytes = (long long)r->nodes * 2 * N * (long long)sizeof(uint64_t);
+  r->chunk = count < LUT_MAX_CHUNK ? count : LUT_MAX_CHUNK;
+  if (r->levels) {
+    const long long bound = g_lut_workspace.load(std::memory_order_relaxed);
+    if (r->table_bytes + r->input_bytes > bound)
+      return fail(MOSFHET_HIP_EINVAL, "%s: the workspace bound of %lld bytes does not hold the prepared table (%lld) and one input's intermediates (%lld)", who, bound,
+                  r->table_bytes, r->input_bytes);
+    const long long fit = (bound - r->table_bytes) / r->input_bytes;
+    if (fit < r->chunk) r->chunk = (int)fit;
+  }
+  r->bytes = r->table_bytes + (long long)r->chunk * r->input_bytes;
+  return MOSFHET_HIP_OK;
+}
+
+extern "C" int mosfhet_hip_leveled_lut_plan(int N, int l, int size, int count, int cus, long long *plan) {
+  if (!plan) return fail(MOSFHET_HIP_EINVAL, "leveled_lut_plan: null plan");
+  LutPlan r;
+  const int rc = lut_plan("leveled_lut_plan", N, l, size, count, cus, &r);
+  if (rc) return rc;
+  plan[0] = r.levels; plan[1] = r.nodes; plan[2] = r.chunk; plan[3] = r.bytes;
+  return MOSFHET_HIP_OK;
+}
+
+template <class F>
+static int launch_leveled_lut(const LutPlan &plan, LutParams p, int count, int cus, hipStream_t s) {
+  const int teams = cus * 8 / (F::THREADS / 64);   // resident capacity at two wavefronts per SIMD: level 0's workgroups (one team each) ...
+  const int pairs = teams / 2;                     // ... and the two-team workgroups of lut_cmux_kernel
+  int rc;
+  if (plan.levels) {
+    p.first = 0; p.inputs = 0;
+    hipLaunchKernelGGL(lut_prepare_kernel<F>, dim3((unsigned)(plan.nodes * 2 * p.l)), dim3(F::THREADS), 0, s, p);
+  }
+  for (int first = 0; first < count; first += plan.chunk) {
+    p.first = first;
+    p.inputs = count - first < plan.chunk ? count - first : plan.chunk;
+    if (plan.levels) {
+      // level 0: a workgroup works for one input; the nodes of an input are cut over as many workgroups as it takes to fill the device
+      int slices = (teams + p.inputs - 1) / p.inputs;
+      slices = slices < 1 ? 1 : (slices > plan.nodes ? plan.nodes : slices);
+      hipLaunchKernelGGL(lut_level0_kernel<F>, dim3((unsigned)slices, (unsigned)p.inputs), dim3(F::THREADS), 0, s, p);
+      for (int i = 1; i < plan.levels; i++) {
+        p.mode = 0;
+        p.half = plan.nodes >> i;
+        p.sel_index = p.size - i - 1;
+        const size_t units = (size_t)p.inputs * p.half;
+        if ((rc = launch_dyn_lds(lut_cmux_kernel<F>, dim3((unsigned)(units < (size_t)pairs ? units : (size_t)pairs)), dim3(2 * F::THREADS), lut_cmux_lds<F>(), s, p))) return rc;
+      }
+    }
+    p.mode = 1;
+    if ((rc = launch_dyn_lds(lut_cmux_kernel<F>, dim3((unsigned)p.inputs), dim3(2 * F::THREADS), lut_cmux_lds<F>(), s, p))) return rc;
+  }
+  return launched();
+}
+
+extern "C" int mosfhet_hip_leveled_lut_batch(mosfhet_hip_ctx_t ctx, uint64_t *d_out, const double *d_sel_dft, const uint64_t *d_lut, int size, int N, int l, int Bg_bit,
+                                             int count, void *stream) {
+  // (argument checks come before any HIP call)
+  if (!ctx) return fail(MOSFHET_HIP_EINVAL, "leveled_lut: null ctx");
+  if (count < 0) return fail(MOSFHET_HIP_EINVAL, "leveled_lut: count = %d", count);
+  if (l < 1 || Bg_bit < 1 || Bg_bit > 31 || l * Bg_bit >= 64) return fail(MOSFHET_HIP_EINVAL, "leveled_lut: bad gadget l=%d Bg_bit=%d (Bg_bit <= 31, l*Bg_bit < 64)", l, Bg_bit);
+  LutPlan plan;
+  int rc = lut_plan("leveled_lut", N, l, size, count ? count : 1, 256, &plan);
+  if (rc) return rc;
+  if (count == 0) return MOSFHET_HIP_OK;
+  if (!d_out || !d_sel_dft || !d_lut) return fail(MOSFHET_HIP_EINVAL, "leveled_lut: null buffer");
+  HIP_TRY(hipSetDevice(ctx->device));
+  const int cus = device_cus() > 0 ? device_cus() : 256;
+  uint64_t *ws = nullptr;
+  if (plan.levels && (rc = pool_get(ctx->device, POOL_LUT, (size_t)(plan.bytes / (long long)sizeof(uint64_t)), &ws))) return rc;
+  LutParams p;
+  p.sel = reinterpret_cast<const d2 *>(d_sel_dft);
+  p.lut = d_lut;
+  p.dtab = reinterpret_cast<d2 *>(ws);
+  p.work = ws ? ws + plan.table_bytes / (long long)sizeof(uint64_t) : nullptr;
+  p.out = d_out;
+  p.size = size; p.l = l; p.Bg_bit = Bg_bit;
+  p.half0 = plan.nodes;
+  p.first = 0; p.inputs = 0; p.mode = 1; p.half = 0; p.sel_index = 0;
+  p.steps = size < ilog2(N) ? size : ilog2(N);
+  hipStream_t s = pick(ctx, stream);
+  if (N == 1024) { p.tw = ctx->tw1024; return launch_leveled_lut<Fft1024>(plan, p, count, cus, s); }
+  p.tw = ctx->tw2048;
+  return launch_leveled_lut<Fft2048>(plan, p, count, cus, s);
+}

@@ -1,0 +1,240 @@
+// leveled_lut_kernels.h -- device code of mosfhet_hip_leveled_lut_batch (gfx950): eval_LUT of the reference's leveled application
+// (applications/leveled_lut/vertical_packing.c:24-52: a CMUX tree over the top bits of the index, blind_rotate with the low selectors as key and the
+// powers of two as mask, sample extract) for a batch of INDEPENDENT inputs, each given bit by bit as TRGSW_DFT selectors, against ONE shared table.
+//
+// What the batch shares, and what is therefore done once per call instead of once per input: on tree level 0 both CMUX operands are rows of the
+// table, so T[j + half] - T[j], its 2l gadget digit polynomials and their forward transforms do not depend on the input.
+//   lut_prepare_kernel   D[j][r] = DFT(digit_r(table[j + half] - table[j]))                              one workgroup per (node, row)
+//   lut_level0_kernel    T[b][j] = table[j] + round(inverse(sum_r D[j][r] sel[b][size-1][r]))            no forward transform at all
+//   lut_cmux_kernel      mode 0: one deeper tree level in place on the per-input intermediates, T[b][j] += sel[b][s] (.) (T[b][j + half] - T[b][j])
+//                        mode 1: one workgroup per input, accumulator in LDS across the min(size, log2 N) rotate-CMUX steps, then SampleExtract_0
+//                        (workgroups of two teams that share the rows of every product: half the forward transforms on the critical path, one inverse each)
+// The gadget (l, Bg_bit) is a run-time argument of all three (one instantiation per ring): level 0 uses l only as the trip count of its
+// multiply-add loop, and a CMUX is a loop over (component, digit) -- digit r of the difference, forward transform, two multiply-adds.
+// Arithmetic: digits as Digits<L, 0> extracts them (src/polynomial.c:74-89), the transforms of negacyclic_fft.h, the fma chain of cmux_rows over rows
+// 0 .. 2l-1 starting from zero, the inverse transforms, add_rounded<true> (selectors are caller-held DFT content and carry no magnitude bound): the words of
+// external_product_kernel<.., CMUX> and pbs_kernel at the run-time gadget, i.e. the reference's order.
+#pragma once
+#include "bootstrap_kernels.h"
+
+namespace mosfhet {
+
+struct LutParams {
+  const d2 *__restrict__ sel;        // [count][size][2l][2][M] complex, slot order: selector i of input b encrypts bit i of b's index
+  const d2 *__restrict__ tw;         // twiddle table of the ring
+  const uint64_t *__restrict__ lut;  // [n_luts][2][N] the shared table (read only)
+  d2 *dtab;                          // [half0][2l][M] complex: the transformed digit rows of level 0's differences
+  uint64_t *work;                    // [inputs of the chunk][half0][2][N] intermediates of the tree (null without a tree)
+  uint64_t *out;                     // [count][N + 1]
+  int size, l, Bg_bit;
+  int half0;                         // nodes of tree level 0 (0: no tree)
+  int first, inputs;                 // the chunk: inputs first .. first + inputs - 1 of the batch
+  int mode, half, sel_index;         // lut_cmux_kernel: mode 0 = the tree level with `half` nodes and selector `sel_index`; mode 1 = finish
+  int steps;                         // mode 1: min(size, log2 N) rotation steps
+};
+
+// 2^(63 - l Bg) + sum_i 2^(63 - i Bg): the rounding offset of polynomial_decompose_i for all l digits at once (pbs_kernel's `off`)
+__device__ __forceinline__ uint64_t lut_gadget_offset(int l, int Bg_bit) {
+  uint64_t off = 1ull << (63 - l * Bg_bit);
+  for (int i = 0; i < l; i++) off += 1ull << (63 - i * Bg_bit);
+  return off;
+}
+
+// Table preparation: block (j, r = q l + lv) writes D[j][r] = DFT(digit lv of (table[j + half0] - table[j]).component q), slot order [m][thread].
+template <class F>
+__global__ __launch_bounds__(F::THREADS) void lut_prepare_kernel(LutParams p) {
+  constexpr int N = F::N, M = F::M, T = F::THREADS;
+  __shared__ __attribute__((aligned(16))) d2 xch[F::XCH_SLOTS];
+  const int t = threadIdx.x;
+  const int rows = 2 * p.l;
+  const int j = blockIdx.x / rows, r = blockIdx.x % rows, q = r / p.l, lv = r % p.l;
+  F fft;
+  fft_setup(fft, p.tw, t);
+  const uint64_t off = lut_gadget_offset(p.l, p.Bg_bit);
+  const uint64_t *__restrict__ lo = p.lut + ((size_t)j * 2 + q) * N, *__restrict__ hi = p.lut + ((size_t)(j + p.half0) * 2 + q) * N;
+  double re[8], im[8];
+#pragma unroll
+  for (int m = 0; m < 8; m++) {
+    re[m] = Digits<1, 0>::digit(hi[m * T + t] - lo[m * T + t] + off, 0, 0, lv, p.Bg_bit);
+    im[m] = Digits<1, 0>::digit(hi[M + m * T + t] - lo[M + m * T + t] + off, 0, 1, lv, p.Bg_bit);
+  }
+  fft.forward(re, im, xch, t);
+  d2 *dst = p.dtab + ((size_t)j * rows + r) * M;
+#pragma unroll
+  for (int m = 0; m < 8; m++) dst[m * T + t] = d2{re[m], im[m]};
+}
+
+// Level 0: workgroup (slice, b) works for input b and walks the nodes j = slice, slice + slices, ... (every workgroup in the same direction, so the rows of D
+// are shared through the L2s); per node 2l complex multiply-add rows per output component, the inverse pair and the rounded addition onto the table row.
+template <class F>
+__global__ __launch_bounds__(F::THREADS, 2) void lut_level0_kernel(LutParams p) {
+  constexpr int N = F::N, M = F::M, T = F::THREADS;
+  __shared__ __attribute__((aligned(16))) d2 xch[F::XCH_SLOTS];
+  const int t = threadIdx.x;
+  const int rows = 2 * p.l;
+  const size_t b = blockIdx.y;
+  F fft;
+  fft_setup(fft, p.tw, t);
+  const RoundCtx scale(0x1p-64 / (double)M);
+  const d2 *__restrict__ sel = p.sel + (((size_t)p.first + b) * p.size + (size_t)(p.size - 1)) * ((size_t)rows * 2 * M);
+  for (int j = blockIdx.x; j < p.half0; j += gridDim.x) {
+    const d2 *__restrict__ drow = p.dtab + (size_t)j * rows * M;
+    double o_re[2][8], o_im[2][8];
+#pragma unroll
+    for (int c = 0; c < 2; c++)
+#pragma unroll
+      for (int m = 0; m < 8; m++) { o_re[c][m] = 0.0; o_im[c][m] = 0.0; }
+#pragma unroll 1
+    for (int r = 0; r < rows; r++) {
+      const d2 *__restrict__ row = sel + (size_t)r * (2 * M);
+      d2 x[8], k0[8], k1[8];
+#pragma unroll
+      for (int m = 0; m < 8; m++) x[m] = drow[(size_t)r * M + m * T + t];
+#pragma unroll
+      for (int m = 0; m < 8; m++) k0[m] = row[m * T + t];
+#pragma unroll
+      for (int m = 0; m < 8; m++) k1[m] = row[M + m * T + t];
+#pragma unroll
+      for (int m = 0; m < 8; m++) {
+        o_re[0][m] = __builtin_fma(-x[m].y, k0[m].y, __builtin_fma(x[m].x, k0[m].x, o_re[0][m]));
+        o_im[0][m] = __builtin_fma(x[m].y, k0[m].x, __builtin_fma(x[m].x, k0[m].y, o_im[0][m]));
+      }
+#pragma unroll
+      for (int m = 0; m < 8; m++) {
+        o_re[1][m] = __builtin_fma(-x[m].y, k1[m].y, __builtin_fma(x[m].x, k1[m].x, o_re[1][m]));
+        o_im[1][m] = __builtin_fma(x[m].y, k1[m].x, __builtin_fma(x[m].x, k1[m].y, o_im[1][m]));
+      }
+    }
+    fft.inverse2(o_re[0], o_im[0], o_re[1], o_im[1], xch, t);
+    const uint64_t *__restrict__ base = p.lut + (size_t)j * 2 * N;
+    uint64_t *dst = p.work + (b * p.half0 + (size_t)j) * 2 * N;
+#pragma unroll
+    for (int c = 0; c < 2; c++)
+#pragma unroll
+      for (int m = 0; m < 8; m++) {
+        dst[c * N + m * T + t] = add_rounded<true>(base[c * N + m * T + t], o_re[c][m], scale);
+        dst[c * N + M + m * T + t] = add_rounded<true>(base[c * N + M + m * T + t], o_im[c][m], scale);
+      }
+  }
+}
+
+// sel (.) d by the TWO TEAMS of a workgroup (F::THREADS threads each), the form of pbs_wide_team_kernel with the gadget length as the loop bound: in phase ph team w
+// owns row 2 ph + w (component q = row / l, digit row % l): its digits, its forward transform, the transformed digits handed over through its exchange buffer;
+// then team w multiplies the phase's two rows with ITS output component of the selector -- in row order, the fma chain of cmux_rows starting from zero --
+// and after the last phase runs the inverse transform of that component.  Critical path per product: l forward transforms + 1 inverse instead of 2l + 2.
+// `home` (LDS, [2][N]): rotate -- the accumulator, d = (X^abar - 1) home; else the difference itself.  Leaves the inverse's output (unscaled) in o_re / o_im.
+template <class F>
+__device__ __forceinline__ void lut_team_product(const uint64_t *home, bool rotate, int a_lo, bool flip, const d2 *__restrict__ sel, int l, int Bg_bit, uint64_t off,
+                                                 const F &fft, d2 *xch_all, int team, int t, double (&o_re)[8], double (&o_im)[8]) {
+  constexpr int N = F::N, M = F::M, T = F::THREADS;
+  d2 *xch = xch_all + (size_t)team * F::XCH_SLOTS;
+  const uint32_t mask = (1u << Bg_bit) - 1;
+  const int half_bg = 1 << (Bg_bit - 1);
+#pragma unroll
+  for (int m = 0; m < 8; m++) { o_re[m] = 0.0; o_im[m] = 0.0; }
+#pragma unroll 1
+  for (int ph = 0; ph < l; ph++) {
+    // this team's component of the phase's two selector rows: requested now, under the digit extraction and the forward transform
+    d2 kk[2][8];
+#pragma unroll
+    for (int r = 0; r < 2; r++)
+#pragma unroll
+      for (int m = 0; m < 8; m++) kk[r][m] = sel[(size_t)(2 * ph + r) * (2 * M) + (size_t)team * M + m * T + t];
+    const int row = 2 * ph + team, q = row / l, shift = 64 - (row % l + 1) * Bg_bit;
+    const uint64_t *hq = home + (size_t)q * N;
+    double re[8], im[8];
+#pragma unroll
+    for (int m = 0; m < 8; m++) {
+      const int j = m * T + t;
+      const uint64_t d_lo = (rotate ? rot_coeff<N>(hq, j, a_lo, flip) - hq[j] : hq[j]) + off;
+      const uint64_t d_hi = (rotate ? rot_coeff<N>(hq, j + M, a_lo, flip) - hq[j + M] : hq[j + M]) + off;
+      re[m] = (double)((int)((uint32_t)(d_lo >> shift) & mask) - half_bg);
+      im[m] = (double)((int)((uint32_t)(d_hi >> shift) & mask) - half_bg);
+    }
+    fft.forward(re, im, xch, t);
+#pragma unroll
+    for (int m = 0; m < 8; m++) xch[m * T + t] = d2{re[m], im[m]};
+    workgroup_sync();
+#pragma unroll
+    for (int r = 0; r < 2; r++) {
+      const d2 *__restrict__ dr = xch_all + (size_t)r * F::XCH_SLOTS;
+#pragma unroll
+      for (int m = 0; m < 8; m++) {
+        const d2 d = dr[m * T + t], k = kk[r][m];
+        o_re[m] = __builtin_fma(-d.y, k.y, __builtin_fma(d.x, k.x, o_re[m]));
+        o_im[m] = __builtin_fma(d.y, k.x, __builtin_fma(d.x, k.y, o_im[m]));
+      }
+    }
+    workgroup_sync();   // the transformed digits are consumed: the buffers are free for the next phase's exchanges / the inverse
+  }
+  fft.inverse(o_re, o_im, xch, t);   // (at N = 2048 workgroup barriers inside: both teams walk them)
+}
+
+// Workgroups of two teams (lut_team_product); dynamic LDS: two exchange buffers and [2][N] words (lut_cmux_lds<F>()).
+// mode 0: persistent workgroups over the units (b, j) of one tree level below the first, in place: T[b][j] += sel[b][sel_index] (.) (T[b][j + half] - T[b][j]).
+//         Units touch disjoint rows (j < half <= j + half), so the order of the units does not matter.  The difference waits in LDS.
+// mode 1: workgroup b finishes input b: acc = T[b][0] (the table's row 0 without a tree), `steps` times acc += sel[b][i] (.) ((X^(2N - 2^i) - 1) acc)
+//         (src/bootstrap.c:107-122 with a[i] = int2torus(2N - 2^i, log2(2N)): never zero, no skipped step), then trlwe_extract_tlwe(acc, 0).
+//         Both accumulator components stay in LDS across the steps.
+template <class F>
+constexpr size_t lut_cmux_lds() { return sizeof(d2) * 2 * F::XCH_SLOTS + sizeof(uint64_t) * 2 * F::N; }
+
+template <class F>
+__global__ __launch_bounds__(2 * F::THREADS, 2) void lut_cmux_kernel(LutParams p) {
+  constexpr int N = F::N, M = F::M, T = F::THREADS, WG = 2 * T;
+  extern __shared__ __attribute__((aligned(16))) unsigned char lut_lds[];
+  d2 *xch_all = reinterpret_cast<d2 *>(lut_lds);                                                 // [2][F::XCH_SLOTS]
+  uint64_t *acc = reinterpret_cast<uint64_t *>(lut_lds + sizeof(d2) * 2 * F::XCH_SLOTS);         // [2][N]
+  const int tid = threadIdx.x, team = __builtin_amdgcn_readfirstlane(tid / T), t = tid % T;
+  const int l = p.l, Bg_bit = p.Bg_bit;
+  F fft;
+  fft_setup(fft, p.tw, t);
+  const uint64_t off = lut_gadget_offset(l, Bg_bit);
+  const RoundCtx scale(0x1p-64 / (double)M);
+  const size_t sel_sz = (size_t)2 * l * 2 * M;   // one selector, in complex slots
+  double o_re[8], o_im[8];
+
+  if (p.mode == 0) {
+    const size_t units = (size_t)p.inputs * p.half;
+    for (size_t u = blockIdx.x; u < units; u += gridDim.x) {
+      const size_t b = u / (size_t)p.half, j = u % (size_t)p.half;
+      uint64_t *x = p.work + (b * p.half0 + j) * 2 * N;   // (read and written by this unit alone)
+      const uint64_t *y = x + (size_t)p.half * 2 * N;
+      for (int w = tid; w < 2 * N; w += WG) acc[w] = y[w] - x[w];
+      workgroup_sync();
+      lut_team_product(acc, false, 0, false, p.sel + (((size_t)p.first + b) * p.size + (size_t)p.sel_index) * sel_sz, l, Bg_bit, off, fft, xch_all, team, t, o_re, o_im);
+      uint64_t *xc = x + (size_t)team * N;                // this team's output component
+#pragma unroll
+      for (int m = 0; m < 8; m++) {
+        xc[m * T + t] = add_rounded<true>(xc[m * T + t], o_re[m], scale);
+        xc[M + m * T + t] = add_rounded<true>(xc[M + m * T + t], o_im[m], scale);
+      }
+      workgroup_sync();
+    }
+    return;
+  }
+
+  const size_t b = blockIdx.x;
+  const uint64_t *src = p.half0 ? p.work + b * p.half0 * 2 * N : p.lut;
+  for (int w = tid; w < 2 * N; w += WG) acc[w] = src[w];
+  workgroup_sync();
+  for (int i = 0; i < p.steps; i++) {
+    const int abar = 2 * N - (1 << i);
+    lut_team_product(acc, true, abar & (N - 1), (abar & N) != 0, p.sel + (((size_t)p.first + b) * p.size + (size_t)i) * sel_sz, l, Bg_bit, off, fft, xch_all, team, t,
+                     o_re, o_im);
+    // (every read of the old accumulator stands in front of the last phase's barriers: the update below is this thread's own 16 words)
+    uint64_t *ac = acc + (size_t)team * N;
+#pragma unroll
+    for (int m = 0; m < 8; m++) {
+      ac[m * T + t] = add_rounded<true>(ac[m * T + t], o_re[m], scale);
+      ac[M + m * T + t] = add_rounded<true>(ac[M + m * T + t], o_im[m], scale);
+    }
+    workgroup_sync();
+  }
+  // src/trlwe.c:540-552 at idx = 0: a[0] = acc_a[0], a[j] = -acc_a[N - j]; b = acc_b[0]
+  uint64_t *dst = p.out + ((size_t)p.first + b) * (size_t)(N + 1);
+  for (int j = tid; j < N; j += WG) dst[j] = (j == 0) ? acc[0] : (0 - acc[N - j]);
+  if (tid == 0) dst[N] = acc[N];
+}
+
+}  // namespace mosfhet

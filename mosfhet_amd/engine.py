@@ -86,6 +86,22 @@ def bootstrap_plan(N, l, Bg_bit, count, order="auto", cus=256, rows=1, galois=Fa
     return dict(family=KERNEL_FAMILIES[plan[0]], by_component=bool(plan[1]), rounds=int(plan[2]))
 
 
+LEVELED_LUT_MAX_LEVELS = 10                                                                                     # MOSFHET_HIP_LUT_MAX_LEVELS
+
+
+def leveled_lut_plan(N, l, size, count, cus=256):
+    """What a leveled_lut call will do (no device needed): dict(levels, nodes, chunk, workspace_bytes) -- tree levels, first-level nodes, inputs per chunk and the
+    bytes of the prepared table rows plus one chunk's intermediates.  include/mosfhet_hip.h: mosfhet_hip_leveled_lut_plan."""
+    plan = (C.c_longlong * 4)()
+    _check(lib().mosfhet_hip_leveled_lut_plan(int(N), int(l), int(size), int(count), int(cus), plan))
+    return dict(levels=int(plan[0]), nodes=int(plan[1]), chunk=int(plan[2]), workspace_bytes=int(plan[3]))
+
+
+def set_leveled_lut_workspace(nbytes):
+    """Workspace bound of leveled_lut (0 restores the default of 1 GiB): batches that need more run in chunks of whole inputs; results do not depend on it."""
+    _check(lib().mosfhet_hip_set_leveled_lut_workspace(C.c_longlong(int(nbytes))))
+
+
 class BootstrapKey:
     def __init__(self, engine, handle, n, k, N, l, Bg_bit):
         self.engine, self.h = engine, handle
@@ -552,6 +568,23 @@ class Engine:
             out = self.empty(count, bsk.k + 1, bsk.N)
         _check(lib().mosfhet_hip_cmux_batch(self.h, bsk.h, int(key_index), _ptr(out), _ptr(in0), _ptr(in1), count, self._stream()))
         return out
+
+    def leveled_lut(self, sel_dft, lut, size, l, Bg_bit, out=None):
+        """A shared look-up table evaluated on a batch of independent inputs given bit by bit as TRGSW_DFT selectors (eval_LUT of the reference's leveled
+        application per input).  sel_dft: [count][size][2l][2][N] doubles (trgsw_to_dft of [count][size] TRGSW samples, bit i of input b at [b][i]);
+        lut: [max(1, 2^size / N)][2][N] torus words, read only; returns [count][N + 1]."""
+        count, N = sel_dft.shape[0], lut.shape[-1]
+        assert tuple(sel_dft.shape) == (count, size, 2 * l, 2, N) and sel_dft.dtype == self.torch.float64, tuple(sel_dft.shape)
+        assert tuple(lut.shape) == (max(1, (1 << size) // N), 2, N), tuple(lut.shape)
+        if out is None:
+            out = self.empty(count, N + 1)
+        assert tuple(out.shape) == (count, N + 1)
+        _check(lib().mosfhet_hip_leveled_lut_batch(self.h, _ptr(out), _ptr(sel_dft), _ptr(lut), int(size), int(N), int(l), int(Bg_bit), int(count), self._stream()))
+        return out
+
+    def leveled_lut_plan(self, N, l, size, count):
+        """leveled_lut_plan() at this device's CU count."""
+        return leveled_lut_plan(N, l, size, count, self.torch.cuda.get_device_properties(self.device).multi_processor_count)
 
     def trlwe_eval_automorphism(self, gak, ct, gen, out=None):
         count = ct.shape[0]

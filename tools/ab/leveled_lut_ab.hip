@@ -1,0 +1,19 @@
+// leveled_lut_ab.hip -- the leveled-LUT kernels (mosfhet_amd/csrc/leveled_lut_kernels.h) compiled alone for tools/check_lds_barriers.py: at N = 2048 their transforms'
+// exchanges and the accumulator updates of the finishing kernel stand in front of workgroup barriers of two-wavefront teams.
+//   -DAB_N=1024 | -DAB_N=2048
+#include "../../mosfhet_amd/csrc/leveled_lut_kernels.h"
+
+using namespace mosfhet;
+
+#ifndef AB_N
+#define AB_N 2048
+#endif
+#if AB_N == 1024
+using AbF = Fft1024;
+#else
+using AbF = Fft2048;
+#endif
+
+template __global__ void mosfhet::lut_prepare_kernel<AbF>(LutParams);
+template __global__ void mosfhet::lut_level0_kernel<AbF>(LutParams);
+template __global__ void mosfhet::lut_cmux_kernel<AbF>(LutParams);

@@ -9,8 +9,9 @@ The two-wavefront exchanges (ds_write ; s_barrier ; ds_read ; s_barrier: both wa
 inside one basic block, LDS writes followed by TWO barriers with no LDS read in between mean the reads went behind the barrier that releases the buffer.
 
     python tools/check_lds_barriers.py listing.s [...]        exit status 1 and one line per violation
-    build_and_check()                                          compiles tools/ab/ep_ab.hip in the forms that used to fail, and the one-CU by-component bootstrap
-                                                               kernels (tools/ab/bycomp_ab.hip), and checks them (CPU, seconds)
+    build_and_check()                                          compiles tools/ab/ep_ab.hip in the forms that used to fail, the one-CU by-component bootstrap
+                                                               kernels (tools/ab/bycomp_ab.hip) and the leveled-LUT kernels (tools/ab/leveled_lut_ab.hip), and
+                                                               checks them (CPU, seconds)
 """
 import os
 import re
@@ -69,7 +70,9 @@ FORMS = [("N = 2048, l = 1, pipelined loop (the build that failed)", ["-DAB_N=20
          ("bootstrap by component on one CU, 6 x 2^7", ["-DAB_L=6", "-DAB_BG=7"], "bycomp_ab.hip"),
          ("bootstrap by component on one CU, l = 2, run-time gadget", ["-DAB_L=2", "-DAB_BG=0"], "bycomp_ab.hip"),
          ("Galois bootstrap by component on one CU, 4 x 2^9", ["-DAB_L=4", "-DAB_BG=9", "-DAB_GA"], "bycomp_ab.hip"),
-         ("bootstrap by component, throughput form, 4 x 2^9", ["-DAB_L=4", "-DAB_BG=9", "-DAB_TP"], "bycomp_ab.hip")]
+         ("bootstrap by component, throughput form, 4 x 2^9", ["-DAB_L=4", "-DAB_BG=9", "-DAB_TP"], "bycomp_ab.hip"),
+         # the leveled-LUT kernels (tools/ab/leveled_lut_ab.hip): table preparation, level 0, tree level / finish; two-wavefront teams at N = 2048
+         ("leveled LUT: prepare, level 0, CMUX and finish, N = 2048", ["-DAB_N=2048"], "leveled_lut_ab.hip")]
 
 
 def build_and_check(forms=FORMS):
