@@ -291,6 +291,10 @@ void full_domain_functional_bootstrap_batch(TLWE *out, TRLWE tv, TLWE *in, int c
  * LEFT UNCHANGED (the reference's eval_LUT destroys its table).  Synchronous; aborts on error like the rest of this layer.  N = 1024 or 2048.  Runs on the
  * primary device: it is not cut over the GPUs of mosfhet_set_devices (hence no _batch suffix, which promises that above). */
 void mosfhet_eval_LUT_inputs(TLWE *out, TRGSW_DFT **inputs, int size, TRLWE *LUT, int count);
+/* ... and against `tables` shared tables in one call (new): LUTs[tb] is table tb (an array of max(1, 2^size / N) TRLWEs, LEFT UNCHANGED), out is
+ * an array of `count` arrays of `tables` samples, out[b][tb] bit for bit what eval_LUT gives for input b on a copy of table tb -- one output per (input, table), the selectors
+ * read once for all tables.  1 <= tables <= 64.  Synchronous; aborts on error; primary device; N = 1024 or 2048. */
+void mosfhet_eval_LUTs_inputs(TLWE **out /*[count][tables]*/, TRGSW_DFT **inputs, int size, TRLWE **LUTs /*[tables]*/, int tables, int count);
 
 /* ---- flat helpers used by the Python binding and bench.py (new) ----
  * Generate a whole bootstrap / key-switch key in the flat torus-domain layouts of mosfhet_hip.h. */

@@ -482,6 +482,32 @@ int mosfhet_hip_leveled_lut_batch(mosfhet_hip_ctx_t ctx, uint64_t *d_out, const 
 int mosfhet_hip_leveled_lut_plan(int N, int l, int size, int count, int cus, long long *plan /*[4]*/);
 int mosfhet_hip_set_leveled_lut_workspace(long long bytes);
 
+/* The same evaluation for SEVERAL shared tables over the same selectors: an n-bit -> m-bit function is m tables, more precision than one table carries is
+ * several, and feeding a result back into the leveled pipeline takes one LWE sample per output bit.  One call fetches the selectors -- the expensive operand,
+ * 2l * 2 * N/2 complex per bit of every input -- once for all tables where `tables` calls of mosfhet_hip_leveled_lut_batch fetch them `tables` times.
+ *   d_sel_dft  [count][size][2l][2][N/2] complex: exactly the layout of mosfhet_hip_leveled_lut_batch
+ *   d_luts     [tables][n_luts][2][N], n_luts = max(1, 2^size / N), trivial or encrypted; READ ONLY
+ *   d_out      [count][tables][N + 1], input-major: as [count * tables][N + 1] it is the batch mosfhet_hip_tlwe_keyswitch_batch and then
+ *              mosfhet_hip_circuit_bootstrap_3_batch take as "bit tb of input b", with no repacking
+ * d_out[b][tb] is word for word what mosfhet_hip_leveled_lut_batch writes to d_out[b] when given table tb alone: the same summation order (one chain over rows
+ * 0 .. 2l-1, the reference's, rounded with the reduction mod 1), no key handle consulted, and no word depends on count, on tables or on the passes, chunks and
+ * groups below.  Arguments as for mosfhet_hip_leveled_lut_batch plus 1 <= tables <= MOSFHET_HIP_LUT_MAX_TABLES; anything else MOSFHET_HIP_EINVAL with a message
+ * naming the argument, before any HIP call; count == 0 returns MOSFHET_HIP_OK.
+ * Asynchronous on `stream`.  The workspace comes from the CALLING THREAD's pool, the one mosfhet_hip_leveled_lut_batch draws from: ONE STREAM PER HOST THREAD at a
+ * time for these two calls together -- a thread that queues two of them on two streams that may overlap must wait for the first before it issues the second.
+ * Workspace bound: the one of mosfhet_hip_set_leveled_lut_workspace.  Per table the prepared rows [nodes][2l][N/2] complex and the intermediates
+ * [chunk][nodes][2][N] as in the one-table call; when all tables do not fit beside one input the call runs in passes over groups of tables (each pass reads the
+ * selectors again), within a pass in chunks of whole inputs; it refuses only when one table with one input does not fit.
+ * The finish runs one workgroup per (input, group of G tables) with the G accumulators in LDS; G comes from mosfhet_hip_set_leveled_lut_tables_group (0 = the
+ * default), capped by what the LDS of a CU holds (8 at N = 1024, 3 at N = 2048) and by the tables of a pass.  Results do not depend on it.
+ * mosfhet_hip_leveled_lut_tables_plan says what the launcher will do, as a pure function (no GPU): plan = {tree levels, first-level nodes per table, inputs per
+ * chunk, tables per pass, workspace bytes = tables per pass * (prepared rows + chunk * intermediates), tables per finishing workgroup}; `cus` sizes grids only. */
+#define MOSFHET_HIP_LUT_MAX_TABLES 64
+int mosfhet_hip_leveled_lut_tables_batch(mosfhet_hip_ctx_t ctx, uint64_t *d_out, const double *d_sel_dft, const uint64_t *d_luts, int size, int N, int l, int Bg_bit,
+                                         int tables, int count, void *stream);
+int mosfhet_hip_leveled_lut_tables_plan(int N, int l, int size, int tables, int count, int cus, long long *plan /*[6]*/);
+int mosfhet_hip_set_leveled_lut_tables_group(int group);
+
 /* Key images for the on-disk formats (save_bootstrap_key / load_new_bootstrap_key src/bootstrap.c:63-104, trlwe_save_KS_key /
  * trlwe_load_new_KS_key src/keyswitch.c:122-160, tlwe_save_KS_key / tlwe_load_new_KS_key src/tlwe.c:247-287, trlwe_save_generic_ks_key /
  * trlwe_load_new_generic_ks_key src/keyswitch.c:409-455).  DFT-domain contents are backend-defined in the reference too (src/polynomial.c:336-357):

@@ -315,6 +315,53 @@ void mosfhet_eval_LUT_inputs(TLWE *out, TRGSW_DFT **inputs, int size, TRLWE *LUT
   free(blk);
 }
 
+/* The same for `tables` shared tables over the same inputs (mosfhet_hip_leveled_lut_tables_batch): LUTs[tb] is table tb, an array of max(1, 2^size / N) host
+ * TRLWEs, left unchanged; out[b][tb] receives what eval_LUT gives for input b on table tb.  One call, the selectors fetched once for all tables. */
+void mosfhet_eval_LUTs_inputs(TLWE **out, TRGSW_DFT **inputs, int size, TRLWE **LUTs, int tables, int count) {
+  const char *who = "mosfhet_eval_LUTs_inputs: every input must be `size` TRGSW_DFT samples made by this library (one ring, one gadget)";
+  need(out && inputs && LUTs && size >= 1 && count >= 1 && tables >= 1 && tables <= MOSFHET_HIP_LUT_MAX_TABLES, "mosfhet_eval_LUTs_inputs: bad argument");
+  int l = 0, Bg_bit = 0, N = 0, gathered = 0;
+  double **blk = (double **)mc_xmalloc(sizeof(double *) * (size_t)count);
+  int *owned = (int *)mc_xmalloc(sizeof(int) * (size_t)count);
+  for (int b = 0; b < count; b++) {
+    int lb, Bb, Nb;
+    blk[b] = key_block(inputs[b], size, &lb, &Bb, &Nb, &owned[b], who);
+    if (b == 0) { l = lb; Bg_bit = Bb; N = Nb; }
+    need(lb == l && Bb == Bg_bit && Nb == N, who);
+  }
+  need(N == 1024 || N == 2048, "mosfhet_eval_LUTs_inputs: ring degree must be 1024 or 2048");
+  const size_t in_doubles = trgsw_dft_doubles(l, N) * (size_t)size;
+  double *sel = blk[0];
+  for (int b = 1; b < count; b++)
+    if (blk[b] != blk[0] + (size_t)b * in_doubles) gathered = 1;
+  if (gathered) {
+    sel = (double *)mc_dev_alloc(sizeof(double) * in_doubles * (size_t)count);
+    for (int b = 0; b < count; b++) mc_dev_copy(sel + (size_t)b * in_doubles, blk[b], sizeof(double) * in_doubles, HIP_D2D);
+  }
+  int log_N = 0;
+  while ((1 << log_N) < N) log_N++;
+  const size_t n_luts = size > log_N ? (size_t)1 << (size - log_N) : 1, row = (size_t)2 * N;
+  const size_t lut_w = (size_t)tables * n_luts * row, out_w = (size_t)count * (size_t)tables * ((size_t)N + 1);
+  Torus *h = (Torus *)mc_hstage_alloc(sizeof(Torus) * (lut_w > out_w ? lut_w : out_w)), *d = (Torus *)mc_stage_alloc(sizeof(Torus) * (lut_w + out_w));
+  for (int tb = 0; tb < tables; tb++)
+    for (size_t j = 0; j < n_luts; j++) mc_trlwe_to_flat(h + ((size_t)tb * n_luts + j) * row, LUTs[tb][j]);
+  mc_dev_copy(d, h, sizeof(Torus) * lut_w, HIP_H2D);
+  check_rc(mosfhet_hip_leveled_lut_tables_batch(ectx(), d + lut_w, sel, d, size, N, l, Bg_bit, tables, count, NULL), "mosfhet_eval_LUTs_inputs");
+  mc_dev_copy(h, d + lut_w, sizeof(Torus) * out_w, HIP_D2H);
+  for (int b = 0; b < count; b++)
+    for (int tb = 0; tb < tables; tb++) {
+      const Torus *w = h + ((size_t)b * (size_t)tables + (size_t)tb) * ((size_t)N + 1);
+      memcpy(out[b][tb]->a, w, sizeof(Torus) * (size_t)N);
+      out[b][tb]->b = w[N];
+    }
+  mc_hstage_free(h);
+  if (gathered) hipFree(sel);
+  for (int b = 0; b < count; b++)
+    if (owned[b]) hipFree(blk[b]);
+  free(owned);
+  free(blk);
+}
+
 /* src/trlwe.c:775-781: out = KeySwitch_{ks_key}(in(X^gen)); ks_key switches from key(X^gen) back to key (any entry of a key set) */
 void trlwe_eval_automorphism(TRLWE out, TRLWE in, uint64_t gen, TRLWE_KS_Key ks_key) {
   const int N = in->b->N;

@@ -14,6 +14,12 @@
 // Arithmetic: digits as Digits<L, 0> extracts them (src/polynomial.c:74-89), the transforms of negacyclic_fft.h, the fma chain of cmux_rows over rows
 // 0 .. 2l-1 starting from zero, the inverse transforms, add_rounded<true> (selectors are caller-held DFT content and carry no magnitude bound): the words of
 // external_product_kernel<.., CMUX> and pbs_kernel at the run-time gadget, i.e. the reference's order.
+//
+// Several tables over the SAME selectors (mosfhet_hip_leveled_lut_tables_batch): a table is one more index of the same units -- a grid dimension of the
+// preparation, the slow part of the node index of level 0 (whose intermediates are [input][table][node]) and of a deeper level's units -- and
+//   lut_tables_finish_kernel   one workgroup per (input, group of G tables): the G accumulators in LDS, the rotate steps outermost, so that a selector is
+//                              fetched from memory once per group and re-read from the caches for the other tables of the group; SampleExtract_0 per table
+// The one-table call is the case tables = 1 of the first three kernels and keeps lut_cmux_kernel's mode 1 as its finish.
 #pragma once
 #include "bootstrap_kernels.h"
 
@@ -31,6 +37,11 @@ struct LutParams {
   int first, inputs;                 // the chunk: inputs first .. first + inputs - 1 of the batch
   int mode, half, sel_index;         // lut_cmux_kernel: mode 0 = the tree level with `half` nodes and selector `sel_index`; mode 1 = finish
   int steps;                         // mode 1: min(size, log2 N) rotation steps
+  // several tables over the same selectors (1 and unused strides for the one-table call)
+  int tables;                        // tables of this pass: `lut` and `out` point at the first of them
+  int out_tables;                    // tables of the whole call: out is [count][out_tables][N + 1]
+  int group;                         // lut_tables_finish_kernel: tables per workgroup (the last group of a pass may hold fewer)
+  size_t lut_stride;                 // words from one table to the next: n_luts * 2 * N
 };
 
 // 2^(63 - l Bg) + sum_i 2^(63 - i Bg): the rounding offset of polynomial_decompose_i for all l digits at once (pbs_kernel's `off`)
@@ -40,7 +51,7 @@ __device__ __forceinline__ uint64_t lut_gadget_offset(int l, int Bg_bit) {
   return off;
 }
 
-// Table preparation: block (j, r = q l + lv) writes D[j][r] = DFT(digit lv of (table[j + half0] - table[j]).component q), slot order [m][thread].
+// Table preparation: block (j, r = q l + lv) of table blockIdx.y writes D[table][j][r] = DFT(digit lv of (table[j + half0] - table[j]).component q), slot order [m][thread].
 template <class F>
 __global__ __launch_bounds__(F::THREADS) void lut_prepare_kernel(LutParams p) {
   constexpr int N = F::N, M = F::M, T = F::THREADS;
@@ -51,7 +62,8 @@ __global__ __launch_bounds__(F::THREADS) void lut_prepare_kernel(LutParams p) {
   F fft;
   fft_setup(fft, p.tw, t);
   const uint64_t off = lut_gadget_offset(p.l, p.Bg_bit);
-  const uint64_t *__restrict__ lo = p.lut + ((size_t)j * 2 + q) * N, *__restrict__ hi = p.lut + ((size_t)(j + p.half0) * 2 + q) * N;
+  const uint64_t *__restrict__ lut = p.lut + (size_t)blockIdx.y * p.lut_stride;   // blockIdx.y: the table
+  const uint64_t *__restrict__ lo = lut + ((size_t)j * 2 + q) * N, *__restrict__ hi = lut + ((size_t)(j + p.half0) * 2 + q) * N;
   double re[8], im[8];
 #pragma unroll
   for (int m = 0; m < 8; m++) {
@@ -59,13 +71,14 @@ __global__ __launch_bounds__(F::THREADS) void lut_prepare_kernel(LutParams p) {
     im[m] = Digits<1, 0>::digit(hi[M + m * T + t] - lo[M + m * T + t] + off, 0, 1, lv, p.Bg_bit);
   }
   fft.forward(re, im, xch, t);
-  d2 *dst = p.dtab + ((size_t)j * rows + r) * M;
+  d2 *dst = p.dtab + (((size_t)blockIdx.y * p.half0 + (size_t)j) * rows + r) * M;
 #pragma unroll
   for (int m = 0; m < 8; m++) dst[m * T + t] = d2{re[m], im[m]};
 }
 
-// Level 0: workgroup (slice, b) works for input b and walks the nodes j = slice, slice + slices, ... (every workgroup in the same direction, so the rows of D
-// are shared through the L2s); per node 2l complex multiply-add rows per output component, the inverse pair and the rounded addition onto the table row.
+// Level 0: workgroup (slice, b) works for input b and walks the nodes u = slice, slice + slices, ... of ALL tables, u = table * half0 + j (every workgroup in the
+// same direction, so the rows of D are shared through the L2s; the input is the slow index of the grid, so that the workgroups that read one input's selector run
+// together); per node 2l complex multiply-add rows per output component, the inverse pair and the rounded addition onto the table row.
 template <class F>
 __global__ __launch_bounds__(F::THREADS, 2) void lut_level0_kernel(LutParams p) {
   constexpr int N = F::N, M = F::M, T = F::THREADS;
@@ -77,8 +90,10 @@ __global__ __launch_bounds__(F::THREADS, 2) void lut_level0_kernel(LutParams p) 
   fft_setup(fft, p.tw, t);
   const RoundCtx scale(0x1p-64 / (double)M);
   const d2 *__restrict__ sel = p.sel + (((size_t)p.first + b) * p.size + (size_t)(p.size - 1)) * ((size_t)rows * 2 * M);
-  for (int j = blockIdx.x; j < p.half0; j += gridDim.x) {
-    const d2 *__restrict__ drow = p.dtab + (size_t)j * rows * M;
+  const int nodes = p.tables * p.half0;
+  for (int u = blockIdx.x; u < nodes; u += gridDim.x) {
+    const int tb = u / p.half0, j = u - tb * p.half0;
+    const d2 *__restrict__ drow = p.dtab + (size_t)u * rows * M;
     double o_re[2][8], o_im[2][8];
 #pragma unroll
     for (int c = 0; c < 2; c++)
@@ -106,8 +121,8 @@ __global__ __launch_bounds__(F::THREADS, 2) void lut_level0_kernel(LutParams p) 
       }
     }
     fft.inverse2(o_re[0], o_im[0], o_re[1], o_im[1], xch, t);
-    const uint64_t *__restrict__ base = p.lut + (size_t)j * 2 * N;
-    uint64_t *dst = p.work + (b * p.half0 + (size_t)j) * 2 * N;
+    const uint64_t *__restrict__ base = p.lut + (size_t)tb * p.lut_stride + (size_t)j * 2 * N;
+    uint64_t *dst = p.work + (b * nodes + (size_t)u) * 2 * N;
 #pragma unroll
     for (int c = 0; c < 2; c++)
 #pragma unroll
@@ -171,7 +186,7 @@ __device__ __forceinline__ void lut_team_product(const uint64_t *home, bool rota
 }
 
 // Workgroups of two teams (lut_team_product); dynamic LDS: two exchange buffers and [2][N] words (lut_cmux_lds<F>()).
-// mode 0: persistent workgroups over the units (b, j) of one tree level below the first, in place: T[b][j] += sel[b][sel_index] (.) (T[b][j + half] - T[b][j]).
+// mode 0: persistent workgroups over the units (b, table, j) of one tree level below the first, in place: T[b][tb][j] += sel[b][sel_index] (.) (T[b][tb][j + half] - T[b][tb][j]).
 //         Units touch disjoint rows (j < half <= j + half), so the order of the units does not matter.  The difference waits in LDS.
 // mode 1: workgroup b finishes input b: acc = T[b][0] (the table's row 0 without a tree), `steps` times acc += sel[b][i] (.) ((X^(2N - 2^i) - 1) acc)
 //         (src/bootstrap.c:107-122 with a[i] = int2torus(2N - 2^i, log2(2N)): never zero, no skipped step), then trlwe_extract_tlwe(acc, 0).
@@ -195,10 +210,10 @@ __global__ __launch_bounds__(2 * F::THREADS, 2) void lut_cmux_kernel(LutParams p
   double o_re[8], o_im[8];
 
   if (p.mode == 0) {
-    const size_t units = (size_t)p.inputs * p.half;
+    const size_t units = (size_t)p.inputs * p.tables * p.half;
     for (size_t u = blockIdx.x; u < units; u += gridDim.x) {
-      const size_t b = u / (size_t)p.half, j = u % (size_t)p.half;
-      uint64_t *x = p.work + (b * p.half0 + j) * 2 * N;   // (read and written by this unit alone)
+      const size_t bt = u / (size_t)p.half, j = u % (size_t)p.half, b = bt / (size_t)p.tables;   // bt = b * tables + table: the intermediates are [input][table][node]
+      uint64_t *x = p.work + (bt * p.half0 + j) * 2 * N;   // (read and written by this unit alone)
       const uint64_t *y = x + (size_t)p.half * 2 * N;
       for (int w = tid; w < 2 * N; w += WG) acc[w] = y[w] - x[w];
       workgroup_sync();
@@ -235,6 +250,74 @@ __global__ __launch_bounds__(2 * F::THREADS, 2) void lut_cmux_kernel(LutParams p
   uint64_t *dst = p.out + ((size_t)p.first + b) * (size_t)(N + 1);
   for (int j = tid; j < N; j += WG) dst[j] = (j == 0) ? acc[0] : (0 - acc[N - j]);
   if (tid == 0) dst[N] = acc[N];
+}
+
+// The finish for several tables over the same selectors.  Workgroups of two teams as above; dynamic LDS: the two exchange buffers and `group` accumulators of
+// [2][N] words (lut_tables_finish_lds<F>(group)).  Workgroup (b, g) finishes tables g * group .. of input b: all accumulators are loaded, then the ROTATE STEP
+// is the outer loop and the table the inner one -- selector i of input b comes from memory for the first table and from the caches for the others, and with
+// it every table of the group takes exactly lut_cmux_kernel mode 1's step, so the words are those of the one-table finish whatever the grouping.
+// With more than one group per input the block index is dealt so that the groups of an input -- consecutive units -- run on ONE die's share of the grid (blocks
+// id and id + 8 share an L2): the groups of an input then meet its selectors in that L2.  Speed only; no word depends on the placement.
+template <class F>
+constexpr size_t lut_tables_finish_lds(int group) { return sizeof(d2) * 2 * F::XCH_SLOTS + sizeof(uint64_t) * 2 * F::N * (size_t)group; }
+template <class F>
+constexpr int lut_tables_max_group() { return (int)((160 * 1024 - sizeof(d2) * 2 * F::XCH_SLOTS) / (sizeof(uint64_t) * 2 * F::N)); }
+
+template <class F>
+__global__ __launch_bounds__(2 * F::THREADS, 2) void lut_tables_finish_kernel(LutParams p) {
+  constexpr int N = F::N, M = F::M, T = F::THREADS, WG = 2 * T;
+  extern __shared__ __attribute__((aligned(16))) unsigned char lut_lds[];
+  d2 *xch_all = reinterpret_cast<d2 *>(lut_lds);                                                 // [2][F::XCH_SLOTS]
+  uint64_t *accs = reinterpret_cast<uint64_t *>(lut_lds + sizeof(d2) * 2 * F::XCH_SLOTS);        // [group][2][N]
+  const int tid = threadIdx.x, team = __builtin_amdgcn_readfirstlane(tid / T), t = tid % T;
+  const int l = p.l, Bg_bit = p.Bg_bit;
+  const int groups = (p.tables + p.group - 1) / p.group;
+  const size_t units = (size_t)p.inputs * groups;
+  size_t unit = blockIdx.x;
+  if (groups > 1) {
+    const size_t share = gridDim.x / 8;   // (the launcher rounds the grid up to a multiple of 8)
+    unit = (blockIdx.x % 8) * share + blockIdx.x / 8;
+  }
+  if (unit >= units) return;
+  const size_t b = unit / (size_t)groups;
+  const int tb0 = (int)(unit % (size_t)groups) * p.group;
+  const int nt = p.tables - tb0 < p.group ? p.tables - tb0 : p.group;
+  F fft;
+  fft_setup(fft, p.tw, t);
+  const uint64_t off = lut_gadget_offset(l, Bg_bit);
+  const RoundCtx scale(0x1p-64 / (double)M);
+  const size_t sel_sz = (size_t)2 * l * 2 * M;   // one selector, in complex slots
+  double o_re[8], o_im[8];
+
+  for (int k = 0; k < nt; k++) {
+    const uint64_t *src = p.half0 ? p.work + (b * p.tables + (size_t)(tb0 + k)) * p.half0 * 2 * N : p.lut + (size_t)(tb0 + k) * p.lut_stride;
+    for (int w = tid; w < 2 * N; w += WG) accs[(size_t)k * 2 * N + w] = src[w];
+  }
+  workgroup_sync();
+  for (int i = 0; i < p.steps; i++) {
+    const int abar = 2 * N - (1 << i);
+    const d2 *__restrict__ sel = p.sel + (((size_t)p.first + b) * p.size + (size_t)i) * sel_sz;
+#pragma unroll 1
+    for (int k = 0; k < nt; k++) {
+      uint64_t *acc = accs + (size_t)k * 2 * N;
+      lut_team_product(acc, true, abar & (N - 1), (abar & N) != 0, sel, l, Bg_bit, off, fft, xch_all, team, t, o_re, o_im);
+      // (every read of the old accumulator stands in front of the last phase's barriers: the update below is this thread's own 16 words)
+      uint64_t *ac = acc + (size_t)team * N;
+#pragma unroll
+      for (int m = 0; m < 8; m++) {
+        ac[m * T + t] = add_rounded<true>(ac[m * T + t], o_re[m], scale);
+        ac[M + m * T + t] = add_rounded<true>(ac[M + m * T + t], o_im[m], scale);
+      }
+      workgroup_sync();
+    }
+  }
+  // src/trlwe.c:540-552 at idx = 0, per table: out is [count][out_tables][N + 1]
+  for (int k = 0; k < nt; k++) {
+    const uint64_t *acc = accs + (size_t)k * 2 * N;
+    uint64_t *dst = p.out + (((size_t)p.first + b) * p.out_tables + (size_t)(tb0 + k)) * (size_t)(N + 1);
+    for (int j = tid; j < N; j += WG) dst[j] = (j == 0) ? acc[0] : (0 - acc[N - j]);
+    if (tid == 0) dst[N] = acc[N];
+  }
 }
 
 }  // namespace mosfhet

@@ -97,6 +97,24 @@ def leveled_lut_plan(N, l, size, count, cus=256):
     return dict(levels=int(plan[0]), nodes=int(plan[1]), chunk=int(plan[2]), workspace_bytes=int(plan[3]))
 
 
+LEVELED_LUT_MAX_TABLES = 64                                                                                     # MOSFHET_HIP_LUT_MAX_TABLES
+
+
+def leveled_lut_tables_plan(N, l, size, tables, count, cus=256):
+    """What a leveled_lut_tables call will do (no device needed): dict(levels, nodes, chunk, tables_per_pass, workspace_bytes, group) -- tree levels, first-level
+    nodes per table, inputs per chunk, tables per pass, tables_per_pass * (prepared rows + one chunk's intermediates) and the tables per finishing workgroup.
+    include/mosfhet_hip.h: mosfhet_hip_leveled_lut_tables_plan."""
+    plan = (C.c_longlong * 6)()
+    _check(lib().mosfhet_hip_leveled_lut_tables_plan(int(N), int(l), int(size), int(tables), int(count), int(cus), plan))
+    return dict(levels=int(plan[0]), nodes=int(plan[1]), chunk=int(plan[2]), tables_per_pass=int(plan[3]), workspace_bytes=int(plan[4]), group=int(plan[5]))
+
+
+def set_leveled_lut_tables_group(group):
+    """Tables per finishing workgroup of leveled_lut_tables (0 restores the default); capped by the LDS of a CU and by the tables of a pass.  Results do not
+    depend on it."""
+    _check(lib().mosfhet_hip_set_leveled_lut_tables_group(int(group)))
+
+
 def set_leveled_lut_workspace(nbytes):
     """Workspace bound of leveled_lut (0 restores the default of 1 GiB): batches that need more run in chunks of whole inputs; results do not depend on it."""
     _check(lib().mosfhet_hip_set_leveled_lut_workspace(C.c_longlong(int(nbytes))))
@@ -581,6 +599,24 @@ class Engine:
         assert tuple(out.shape) == (count, N + 1)
         _check(lib().mosfhet_hip_leveled_lut_batch(self.h, _ptr(out), _ptr(sel_dft), _ptr(lut), int(size), int(N), int(l), int(Bg_bit), int(count), self._stream()))
         return out
+
+    def leveled_lut_tables(self, sel_dft, luts, size, l, Bg_bit, out=None):
+        """Several shared look-up tables evaluated on a batch of independent inputs, the selectors fetched once for all of them.  sel_dft as for leveled_lut;
+        luts: [tables][max(1, 2^size / N)][2][N] torus words, read only; returns [count][tables][N + 1] -- out[b][tb] is leveled_lut's out[b] for table tb, and
+        out.view(count * tables, N + 1) is the batch tlwe_keyswitch / circuit_bootstrap_3 take."""
+        count, tables, N = sel_dft.shape[0], luts.shape[0], luts.shape[-1]
+        assert tuple(sel_dft.shape) == (count, size, 2 * l, 2, N) and sel_dft.dtype == self.torch.float64, tuple(sel_dft.shape)
+        assert tuple(luts.shape) == (tables, max(1, (1 << size) // N), 2, N), tuple(luts.shape)
+        if out is None:
+            out = self.empty(count, tables, N + 1)
+        assert tuple(out.shape) == (count, tables, N + 1)
+        _check(lib().mosfhet_hip_leveled_lut_tables_batch(self.h, _ptr(out), _ptr(sel_dft), _ptr(luts), int(size), int(N), int(l), int(Bg_bit), int(tables),
+                                                          int(count), self._stream()))
+        return out
+
+    def leveled_lut_tables_plan(self, N, l, size, tables, count):
+        """leveled_lut_tables_plan() at this device's CU count."""
+        return leveled_lut_tables_plan(N, l, size, tables, count, self.torch.cuda.get_device_properties(self.device).multi_processor_count)
 
     def leveled_lut_plan(self, N, l, size, count):
         """leveled_lut_plan() at this device's CU count."""

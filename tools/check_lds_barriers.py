@@ -10,7 +10,7 @@ inside one basic block, LDS writes followed by TWO barriers with no LDS read in 
 
     python tools/check_lds_barriers.py listing.s [...]        exit status 1 and one line per violation
     build_and_check()                                          compiles tools/ab/ep_ab.hip in the forms that used to fail, the one-CU by-component bootstrap
-                                                               kernels (tools/ab/bycomp_ab.hip) and the leveled-LUT kernels (tools/ab/leveled_lut_ab.hip), and
+                                                               kernels (tools/ab/bycomp_ab.hip) and the leveled-LUT kernels (tools/ab/leveled_lut_ab.hip, leveled_lut_tables_ab.hip), and
                                                                checks them (CPU, seconds)
 """
 import os
@@ -72,7 +72,9 @@ FORMS = [("N = 2048, l = 1, pipelined loop (the build that failed)", ["-DAB_N=20
          ("Galois bootstrap by component on one CU, 4 x 2^9", ["-DAB_L=4", "-DAB_BG=9", "-DAB_GA"], "bycomp_ab.hip"),
          ("bootstrap by component, throughput form, 4 x 2^9", ["-DAB_L=4", "-DAB_BG=9", "-DAB_TP"], "bycomp_ab.hip"),
          # the leveled-LUT kernels (tools/ab/leveled_lut_ab.hip): table preparation, level 0, tree level / finish; two-wavefront teams at N = 2048
-         ("leveled LUT: prepare, level 0, CMUX and finish, N = 2048", ["-DAB_N=2048"], "leveled_lut_ab.hip")]
+         ("leveled LUT: prepare, level 0, CMUX and finish, N = 2048", ["-DAB_N=2048"], "leveled_lut_ab.hip"),
+         # the finish of the several-table call (tools/ab/leveled_lut_tables_ab.hip): grouped accumulators in LDS, the table loop inside the step loop
+         ("leveled LUT, several tables: grouped finish, N = 2048", ["-DAB_N=2048"], "leveled_lut_tables_ab.hip")]
 
 
 def build_and_check(forms=FORMS):
