@@ -295,6 +295,13 @@ void mosfhet_eval_LUT_inputs(TLWE *out, TRGSW_DFT **inputs, int size, TRLWE *LUT
  * an array of `count` arrays of `tables` samples, out[b][tb] bit for bit what eval_LUT gives for input b on a copy of table tb -- one output per (input, table), the selectors
  * read once for all tables.  1 <= tables <= 64.  Synchronous; aborts on error; primary device; N = 1024 or 2048. */
 void mosfhet_eval_LUTs_inputs(TLWE **out /*[count][tables]*/, TRGSW_DFT **inputs, int size, TRLWE **LUTs /*[tables]*/, int tables, int count);
+/* The whole loop of the leveled application in one call (new): circuit_bootstrap_3 + trgsw_to_DFT of every input bit (applications/leveled_lut/main.c,
+ * src/bootstrap.c:346-366, src/trgsw.c:345-349), eval_LUT on a copy of each table (vertical_packing.c:36-52) and, with ksk_out, tlwe_keyswitch N -> n
+ * (src/tlwe.c:289-320) of every output.  in[b][i] is bit i of input b (least significant first, encoded as circuit_bootstrap_3 takes it), out[b][tb] the output of
+ * table tb: a sample of dimension n with ksk_out (the in[b][tb] of the next round when tables == size), of dimension N with ksk_out == NULL.  The selectors stay on
+ * the device in a bounded workspace.  Tables LEFT UNCHANGED.  Synchronous; aborts on error; primary device; N = 1024 or 2048. */
+void mosfhet_eval_LUTs_bits(TLWE **out /*[count][tables]*/, TLWE **in /*[count][size]*/, int size, TRLWE **LUTs /*[tables]*/, int tables, int count,
+                            Bootstrap_Key key, TRLWE_KS_Key *kska, Generic_KS_Key kskb, TLWE_KS_Key ksk_out /* or NULL */);
 
 /* ---- flat helpers used by the Python binding and bench.py (new) ----
  * Generate a whole bootstrap / key-switch key in the flat torus-domain layouts of mosfhet_hip.h. */

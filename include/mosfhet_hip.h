@@ -508,6 +508,42 @@ int mosfhet_hip_leveled_lut_tables_batch(mosfhet_hip_ctx_t ctx, uint64_t *d_out,
 int mosfhet_hip_leveled_lut_tables_plan(int N, int l, int size, int tables, int count, int cus, long long *plan /*[6]*/);
 int mosfhet_hip_set_leveled_lut_tables_group(int group);
 
+/* circuit_bootstrap_3 followed by trgsw_to_DFT (src/bootstrap.c:346-366, src/trgsw.c:345-349) in one call, the TRGSWs never written in the torus domain:
+ * d_out_dft [count][2l][2][N/2] complex is word for word mosfhet_hip_torus_to_dft_batch of mosfhet_hip_circuit_bootstrap_3_batch's [count][2l][2][N]; as
+ * [count / size][size][2l][2][N/2] it is the d_sel_dft of the leveled LUT calls.  Arguments, refusals, bootstrap launch (the key's product order governs it
+ * exactly as there) and the choice between one packing switch for all levels and one per level are those of mosfhet_hip_circuit_bootstrap_3_batch; the private key
+ * switch transforms its result (rows i < l) and its input (rows l + i) itself.  N in {1024, 2048, 4096}.  Asynchronous on `stream`; temporaries in the calling
+ * thread's pool as for mosfhet_hip_circuit_bootstrap_3_batch. */
+int mosfhet_hip_circuit_bootstrap_3_dft_batch(mosfhet_hip_ctx_t ctx, mosfhet_hip_bsk_t bsk, mosfhet_hip_gak_t kska, mosfhet_hip_ksk_t kskb,
+                                              double *d_out_dft /*[count][2l][2][N/2] complex*/, const uint64_t *d_in /*[count][n+1]*/, int count, void *stream);
+
+/* An n-bit -> m-bit function on inputs given as LWE-encrypted bits, LWE-encrypted bits out: circuit bootstrap + vertical packing, the loop of the reference's
+ * leveled application (applications/leveled_lut/main.c: circuit_bootstrap_3 src/bootstrap.c:346-366, trgsw_to_DFT src/trgsw.c:345-349, eval_LUT
+ * vertical_packing.c:36-52, tlwe_keyswitch src/tlwe.c:289-320) for `count` inputs in one call.  An S-box is size = tables = 8.
+ *   d_in     [count][size][n + 1]: bit i of input b, least significant first, encoded as the circuit bootstrap takes it
+ *   d_luts   [tables][n_luts][2][N], n_luts = max(1, 2^size / N), as for mosfhet_hip_leveled_lut_tables_batch; READ ONLY
+ *   ksk_out  an LWE -> LWE key N -> n (mosfhet_hip_ksk_create with n_in = N, n_out = bsk's n), or NULL
+ *   d_out    with ksk_out [count][tables][n + 1] -- exactly the d_in of the next call when tables == size; without it [count][tables][N + 1]
+ * Ring and gadget come from bsk (the selectors a circuit bootstrap makes carry the bootstrap key's l, Bg_bit); kska / kskb as for
+ * mosfhet_hip_circuit_bootstrap_3_batch.  Per chunk of whole inputs: mosfhet_hip_circuit_bootstrap_3_dft_batch on the chunk's chunk * size bits into the selector
+ * workspace, mosfhet_hip_leveled_lut_tables_batch on those selectors, and with ksk_out mosfhet_hip_tlwe_keyswitch_batch of the chunk's [chunk * tables][N + 1].
+ * N in {1024, 2048}; size, tables, l, Bg_bit as in mosfhet_hip_leveled_lut_tables_batch; anything else MOSFHET_HIP_EINVAL with a message naming the argument.  Null
+ * handles and the ranges of size (1 .. 21), tables and count are checked before any handle is read and before any HIP call; count == 0 returns MOSFHET_HIP_OK.
+ * Words: for a key whose product order is MOSFHET_HIP_ORDER_REFERENCE or _BY_COMPONENT no output word depends on count, on the bound below or on the chunking,
+ * and every word equals the four calls above made one after the other on the whole batch.  For an AUTO key the kernel chosen for the launched batch -- here: the
+ * bits of one chunk -- decides, as for every AUTO launch: a caller who wants chunk-independent words sets the order.
+ * Asynchronous on `stream`: no synchronisation, and no allocation from the second call of a shape on.  The selector workspace [chunk][size][2l][2][N/2] complex
+ * (and, with ksk_out, the chunk's [chunk * tables][N + 1]) lives in the CALLING THREAD's pool beside the leveled LUT's: ONE STREAM PER HOST THREAD at a time for
+ * this call and the leveled LUT calls together.  The first call of a larger shape allocates, which synchronises the device and cannot run inside a stream capture.
+ * Bound of the selector workspace: 2 GiB (mosfhet_hip_set_lut_bits_workspace, 0 = default) -- 8192 bits at lvl2's gadget; `chunk` is the largest number of whole
+ * inputs whose selectors fit (at most 2^20 bits per launch), and at least 1: one input always runs.  The LUT call inside a chunk keeps its own bound, passes and
+ * chunks.  mosfhet_hip_lut_bits_plan is the function the launcher uses, pure (no GPU), `cus` sizes grids only: plan = {inputs per chunk, chunks, selector bytes per
+ * chunk, bits per circuit-bootstrap launch, then the six fields of mosfhet_hip_leveled_lut_tables_plan for a chunk}. */
+int mosfhet_hip_lut_bits_batch(mosfhet_hip_ctx_t ctx, mosfhet_hip_bsk_t bsk, mosfhet_hip_gak_t kska, mosfhet_hip_ksk_t kskb, mosfhet_hip_ksk_t ksk_out /* or NULL */,
+                               uint64_t *d_out, const uint64_t *d_luts, const uint64_t *d_in, int size, int tables, int count, void *stream);
+int mosfhet_hip_lut_bits_plan(int N, int l, int size, int tables, int count, int cus, long long *plan /*[10]*/);
+int mosfhet_hip_set_lut_bits_workspace(long long bytes);
+
 /* Key images for the on-disk formats (save_bootstrap_key / load_new_bootstrap_key src/bootstrap.c:63-104, trlwe_save_KS_key /
  * trlwe_load_new_KS_key src/keyswitch.c:122-160, tlwe_save_KS_key / tlwe_load_new_KS_key src/tlwe.c:247-287, trlwe_save_generic_ks_key /
  * trlwe_load_new_generic_ks_key src/keyswitch.c:409-455).  DFT-domain contents are backend-defined in the reference too (src/polynomial.c:336-357):

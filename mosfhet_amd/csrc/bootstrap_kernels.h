@@ -1907,6 +1907,11 @@ __device__ __forceinline__ void ks_rows_rt(const uint64_t (&dd_lo)[8], const uin
 // mode 1: out = trlwe_priv_keyswitch_2(in, {ks0, ks1})         = -as(in.a; ks0) - as(-in.b; ks1)
 // mode 2: out = base - trlwe_keyswitch(in, ks0)                = base - (0, in.b) + as(in.a; ks0)   (relinearisation step of
 //         trlwe_tensor_prod_FFT, src/trlwe.c:758-761)
+// mode 3: mode 1's result and its input as rows of a TRGSW_DFT selector (circuit_bootstrap_3 followed by trgsw_to_DFT, src/bootstrap.c:346-366 and
+//         src/trgsw.c:345-349): sel[blockIdx.x] + row i <- DFT(res), + row l + i <- DFT(in), both exactly as torus_to_dft_kernel transforms the words mode 1 and
+//         the packing switch would have stored; no torus-domain word is written.  `sel` points at row i of ciphertext 0, sel_stride = 2l * 2 * M complex per
+//         ciphertext (row l + i lies half a stride further).  The tail runs when the accumulators are dead: one re / im pair at a time, the same two calls
+//         (torus_to_double, fft.forward) torus_to_dft_kernel makes.
 // One wavefront per SIMD (launch bound 1): the two result pairs, the digit words and the product accumulators are ~330 live registers; with room for
 // the overflow in the accumulation registers there is no scratch (two per SIMD: 388 bytes of it).  The kernel is 0.16 ms of a 38 ms circuit bootstrap.
 template <class F>
@@ -1914,10 +1919,12 @@ __global__ __launch_bounds__(F::THREADS, 1) void trlwe_fft_keyswitch_kernel(cons
                                                                           const d2 *__restrict__ tw, const uint64_t *in,
                                                                           size_t in_stride, uint64_t *out, size_t out_stride,   // in place is relied upon (src/trlwe.c:780): no __restrict__
                                                                           int t, int base_bit, int mode,
-                                                                          const uint64_t *__restrict__ base = nullptr, size_t base_stride = 0) {
+                                                                          const uint64_t *__restrict__ base = nullptr, size_t base_stride = 0,
+                                                                          d2 *__restrict__ sel = nullptr, size_t sel_stride = 0) {
   constexpr int N = F::N, M = F::M, T = F::THREADS;
   __shared__ __attribute__((aligned(16))) d2 xch[F::XCH_SLOTS];
   const int tid = threadIdx.x;
+  const int am = mode == 3 ? 1 : mode;
   const uint64_t *c = in + (size_t)blockIdx.x * in_stride;
   uint64_t *o = out + (size_t)blockIdx.x * out_stride;
   F fft;
@@ -1940,11 +1947,11 @@ __global__ __launch_bounds__(F::THREADS, 1) void trlwe_fft_keyswitch_kernel(cons
       res_b_hi[m] = c[N + M + m * T + tid] - bs[N + M + m * T + tid];
     }
   }
-  const int passes = mode == 1 ? 2 : 1;
+  const int passes = am == 1 ? 2 : 1;
 #pragma unroll 1
   for (int pass = 0; pass < passes; pass++) {
     // pass 0 of mode 1: a' = -in.b with ks1 (src/keyswitch.c:55-57); otherwise a' = in.a with ks0
-    const bool neg_b = (mode == 1 && pass == 0);
+    const bool neg_b = (am == 1 && pass == 0);
     const d2 *__restrict__ entry = neg_b ? ks1 : ks0;
     uint64_t dd_lo[8], dd_hi[8];
 #pragma unroll
@@ -1972,6 +1979,26 @@ __global__ __launch_bounds__(F::THREADS, 1) void trlwe_fft_keyswitch_kernel(cons
       res_b_lo[m] -= round_mod_2_64(o_re[1][m], scale);
       res_b_hi[m] -= round_mod_2_64(o_im[1][m], scale);
     }
+  }
+  if (mode == 3) {
+    d2 *row_a = sel + (size_t)blockIdx.x * sel_stride, *row_b = row_a + sel_stride / 2;
+#pragma unroll 1
+    for (int q = 0; q < 4; q++) {   // res.a, res.b, in.a, in.b -- ONE rolled body: as four unrolled blocks the tail shifts the schedule of the product loop (modes 0 - 2: 2.5 % slower)
+      double re[8], im[8];
+      if (q >= 2) {   // the input, re-read as the passes re-read it
+        const uint64_t *src = c + (q - 2) * N;
+#pragma unroll
+        for (int m = 0; m < 8; m++) { re[m] = torus_to_double(src[m * T + tid]); im[m] = torus_to_double(src[M + m * T + tid]); }
+      } else {
+#pragma unroll
+        for (int m = 0; m < 8; m++) { re[m] = torus_to_double(q ? res_b_lo[m] : res_a_lo[m]); im[m] = torus_to_double(q ? res_b_hi[m] : res_a_hi[m]); }
+      }
+      fft.forward(re, im, xch, tid);
+      d2 *dst = (q < 2 ? row_a : row_b) + (q & 1) * M;
+#pragma unroll
+      for (int m = 0; m < 8; m++) dst[m * T + tid] = d2{re[m], im[m]};
+    }
+    return;
   }
 #pragma unroll
   for (int m = 0; m < 8; m++) {

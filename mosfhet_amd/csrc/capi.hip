@@ -77,7 +77,7 @@ struct DevBuf {
 // handle: handles are read-only after creation, so any number of host threads may share them, as the reference's callers share its keys
 // (re-entrant through thread-local scratch, src/polynomial.c:269-352).  A thread's launches are ordered by the stream it passes; buffers are
 // released at thread exit (hipFree waits for work in flight).
-enum { POOL_BSK = 0, POOL_EXT0 = 1, POOL_EXT1 = 2, POOL_CTX0 = 3, POOL_UNFOLD = 6, POOL_PACK = 7, POOL_VEC = 8, POOL_VEC2 = 9, POOL_VEC3 = 10, POOL_VEC4 = 11, POOL_LUT = 12, POOL_SLOTS = 13 };
+enum { POOL_BSK = 0, POOL_EXT0 = 1, POOL_EXT1 = 2, POOL_CTX0 = 3, POOL_UNFOLD = 6, POOL_PACK = 7, POOL_VEC = 8, POOL_VEC2 = 9, POOL_VEC3 = 10, POOL_VEC4 = 11, POOL_LUT = 12, POOL_BITS = 13, POOL_SLOTS = 14 };
 struct ThreadPool {
   struct Dev {
     int device = -1;
@@ -1566,9 +1566,9 @@ extern "C" int mosfhet_hip_functional_bootstrap_ga_batch(mosfhet_hip_ctx_t ctx, 
 
 // ---- FFT TRLWE key switches with run-time parameters, packing key switch, circuit bootstrap ----
 static int launch_fft_ks(mosfhet_hip_ctx_t ctx, mosfhet_hip_gak_t tks, const d2 *ks0, const d2 *ks1, uint64_t *d_out, size_t out_stride,
-                         const uint64_t *d_in, size_t in_stride, int count, int mode, hipStream_t s) {
+                         const uint64_t *d_in, size_t in_stride, int count, int mode, hipStream_t s, d2 *d_sel = nullptr, size_t sel_stride = 0) {
   RING_DISPATCH(ctx, tks->N, hipLaunchKernelGGL(trlwe_fft_keyswitch_kernel<F>, dim3(count), dim3(F::THREADS), 0, s, ks0, ks1, TW, d_in, in_stride, d_out,
-                                                out_stride, tks->t, tks->base_bit, mode));
+                                                out_stride, tks->t, tks->base_bit, mode, (const uint64_t *)nullptr, (size_t)0, d_sel, sel_stride));
   HIP_TRY(hipGetLastError());
   return MOSFHET_HIP_OK;
 }
@@ -1637,14 +1637,17 @@ __global__ void circuit_bootstrap_lut_kernel(uint64_t *__restrict__ tv, int N, i
   tv[N + i] = slot >= l ? (1ull << (64 - (slot - l + 1) * Bg_bit)) : 0;
 }
 
-extern "C" int mosfhet_hip_circuit_bootstrap_3_batch_ev(mosfhet_hip_ctx_t ctx, mosfhet_hip_bsk_t bsk, mosfhet_hip_gak_t kska, mosfhet_hip_ksk_t kskb,
-                                                        uint64_t *d_out, const uint64_t *d_in, int count, void *stream, void *const *level_done) {
-  TUNED_ONLY(bsk, "circuit_bootstrap_3");
-  if (!ctx || !bsk || !kska || !kskb || (count > 0 && !d_out) || (count > 0 && !d_in) || count < 0) return fail(MOSFHET_HIP_EINVAL, "circuit_bootstrap_3: bad argument");
+// The body of both circuit_bootstrap_3 calls.  d_out: the TRGSWs in the torus domain (private switch in mode 1, rows stored as words, level events); d_sel: the same
+// TRGSWs as DFT-domain selectors [count][2l][2][N/2] complex (capi_bits.inc: the private switch in mode 3 transforms its result and its input itself, no
+// torus-domain word of a TRGSW is written).  Exactly one of the two is given.
+static int circuit_bootstrap_3_run(const char *who, mosfhet_hip_ctx_t ctx, mosfhet_hip_bsk_t bsk, mosfhet_hip_gak_t kska, mosfhet_hip_ksk_t kskb, uint64_t *d_out, d2 *d_sel,
+                                   const uint64_t *d_in, int count, void *stream, void *const *level_done) {
+  TUNED_ONLY(bsk, who);
+  if (!ctx || !bsk || !kska || !kskb || (count > 0 && !d_out && !d_sel) || (count > 0 && !d_in) || count < 0) return fail(MOSFHET_HIP_EINVAL, "%s: bad argument", who);
   const int N = bsk->N, l = bsk->l;
-  if (kska->entries != 2 || kska->N != N) return fail(MOSFHET_HIP_EINVAL, "circuit_bootstrap_3: kska must be the 2-entry private key-switch set for N");
-  if (kskb->row != 2 * N || kskb->b_word != N || kskb->n_in != N) return fail(MOSFHET_HIP_EINVAL, "circuit_bootstrap_3: kskb must be a packing key N -> TRLWE(N)");
-  if (N % (2 * l)) return fail(MOSFHET_HIP_EINVAL, "circuit_bootstrap_3: N not divisible by 2l");
+  if (kska->entries != 2 || kska->N != N) return fail(MOSFHET_HIP_EINVAL, "%s: kska must be the 2-entry private key-switch set for N", who);
+  if (kskb->row != 2 * N || kskb->b_word != N || kskb->n_in != N) return fail(MOSFHET_HIP_EINVAL, "%s: kskb must be a packing key N -> TRLWE(N)", who);
+  if (N % (2 * l)) return fail(MOSFHET_HIP_EINVAL, "%s: N not divisible by 2l", who);
   if (count == 0) return MOSFHET_HIP_OK;
   HIP_TRY(hipSetDevice(ctx->device));
   // Few ciphertexts (fewer than one 512-wide tile of the packing switch): every level's switch would sweep the whole table (3 - 6 GB) for a fraction of a tile, so the
@@ -1653,7 +1656,7 @@ extern "C" int mosfhet_hip_circuit_bootstrap_3_batch_ev(mosfhet_hip_ctx_t ctx, m
   // other (what the level events are for).  Same operations on the same words either way: same bits.
   const bool together = cb_levels_together(count, l);
   const size_t w_tv = (size_t)2 * N, w_acc = (size_t)count * 2 * N, w_ext = ((size_t)count * (N + 1) * (together ? l : 1) + 1) & ~(size_t)1 /* keeps the staging block 16-byte aligned */,
-               w_stage = together ? (size_t)l * count * 2 * N : 0;
+               w_stage = together ? (size_t)l * count * 2 * N : (d_sel ? (size_t)count * 2 * N : 0);   // (selectors: the packing switch of a level lands here too)
   uint64_t *tv = nullptr;
   int rc = bsk_scratch(bsk, w_tv + w_acc + w_ext + w_stage, &tv);
   if (rc) return rc;
@@ -1663,6 +1666,7 @@ extern "C" int mosfhet_hip_circuit_bootstrap_3_batch_ev(mosfhet_hip_ctx_t ctx, m
   if ((rc = mosfhet_hip_functional_bootstrap_wo_extract_batch(ctx, bsk, acc, tv, 1, d_in, count, 2 * l, stream))) return rc;
   const int slot = N / (2 * l);
   const size_t trgsw = (size_t)2 * l * 2 * N, esz = (size_t)kska->t * 2 * (N / 2);
+  const size_t sel_row = (size_t)2 * (N / 2), sel_stride = (size_t)2 * l * sel_row;   // complex per selector row, per selector
   if (together) {
     for (int i = 0; i < l; i++)
       hipLaunchKernelGGL(trlwe_extract_kernel, dim3((N + 255) / 256, count), dim3(256), 0, s, ext + (size_t)i * count * (N + 1), (size_t)N + 1, acc, (size_t)2 * N, N, i * slot);
@@ -1670,6 +1674,10 @@ extern "C" int mosfhet_hip_circuit_bootstrap_3_batch_ev(mosfhet_hip_ctx_t ctx, m
                                   kskb->seed));
     for (int i = 0; i < l; i++) {
       const uint64_t *sw = stage + (size_t)i * count * 2 * N;
+      if (d_sel) {
+        if ((rc = launch_fft_ks(ctx, kska, kska->d_ak, kska->d_ak + esz, nullptr, 0, sw, (size_t)2 * N, count, 3, s, d_sel + (size_t)i * sel_row, sel_stride))) return rc;
+        continue;
+      }
       uint64_t *row_b = d_out + (size_t)(l + i) * 2 * N, *row_a = d_out + (size_t)i * 2 * N;
       HIP_TRY(hipMemcpy2DAsync(row_b, trgsw * sizeof(uint64_t), sw, (size_t)2 * N * sizeof(uint64_t), (size_t)2 * N * sizeof(uint64_t), (size_t)count, hipMemcpyDeviceToDevice, s));
       if ((rc = launch_fft_ks(ctx, kska, kska->d_ak, kska->d_ak + esz, row_a, trgsw, sw, (size_t)2 * N, count, 1, s))) return rc;
@@ -1680,6 +1688,11 @@ extern "C" int mosfhet_hip_circuit_bootstrap_3_batch_ev(mosfhet_hip_ctx_t ctx, m
   }
   for (int i = 0; i < l; i++) {
     hipLaunchKernelGGL(trlwe_extract_kernel, dim3((N + 255) / 256, count), dim3(256), 0, s, ext, (size_t)N + 1, acc, (size_t)2 * N, N, i * slot);
+    if (d_sel) {
+      HIP_TRY(launch_tlwe_keyswitch(kskb->d_ksk, stage, (size_t)2 * N, ext, (size_t)N + 1, count, N, 2 * N, N, kskb->t, kskb->base_bit, tl_ws(ctx->device), s, kskb->compressed, kskb->seed));
+      if ((rc = launch_fft_ks(ctx, kska, kska->d_ak, kska->d_ak + esz, nullptr, 0, stage, (size_t)2 * N, count, 3, s, d_sel + (size_t)i * sel_row, sel_stride))) return rc;
+      continue;
+    }
     uint64_t *row_b = d_out + (size_t)(l + i) * 2 * N, *row_a = d_out + (size_t)i * 2 * N;
     HIP_TRY(launch_tlwe_keyswitch(kskb->d_ksk, row_b, trgsw, ext, (size_t)N + 1, count, N, 2 * N, N, kskb->t, kskb->base_bit, tl_ws(ctx->device), s, kskb->compressed, kskb->seed));
     if ((rc = launch_fft_ks(ctx, kska, kska->d_ak, kska->d_ak + esz, row_a, trgsw, row_b, trgsw, count, 1, s))) return rc;
@@ -1687,6 +1700,11 @@ extern "C" int mosfhet_hip_circuit_bootstrap_3_batch_ev(mosfhet_hip_ctx_t ctx, m
   }
   HIP_TRY(hipGetLastError());
   return MOSFHET_HIP_OK;
+}
+
+extern "C" int mosfhet_hip_circuit_bootstrap_3_batch_ev(mosfhet_hip_ctx_t ctx, mosfhet_hip_bsk_t bsk, mosfhet_hip_gak_t kska, mosfhet_hip_ksk_t kskb,
+                                                        uint64_t *d_out, const uint64_t *d_in, int count, void *stream, void *const *level_done) {
+  return circuit_bootstrap_3_run("circuit_bootstrap_3", ctx, bsk, kska, kskb, d_out, nullptr, d_in, count, stream, level_done);
 }
 
 extern "C" int mosfhet_hip_circuit_bootstrap_3_batch(mosfhet_hip_ctx_t ctx, mosfhet_hip_bsk_t bsk, mosfhet_hip_gak_t kska, mosfhet_hip_ksk_t kskb,
@@ -1723,3 +1741,4 @@ extern "C" int mosfhet_hip_time_programmable_bootstrap(mosfhet_hip_ctx_t ctx, mo
 #include "capi_dft.inc"
 #include "capi_vec.inc"
 #include "capi_lut.inc"
+#include "capi_bits.inc"

@@ -362,6 +362,47 @@ void mosfhet_eval_LUTs_inputs(TLWE **out, TRGSW_DFT **inputs, int size, TRLWE **
   free(blk);
 }
 
+/* The leveled application's loop (applications/leveled_lut/main.c: circuit_bootstrap_3 src/bootstrap.c:346-366, trgsw_to_DFT src/trgsw.c:345-349, eval_LUT
+ * vertical_packing.c:36-52, tlwe_keyswitch src/tlwe.c:289-320) for `count` inputs given as LWE-encrypted bits (mosfhet_hip_lut_bits_batch): in[b][i] is bit i of
+ * input b, LUTs[tb] table tb (an array of max(1, 2^size / N) host TRLWEs, left unchanged); out[b][tb] receives the output of table tb for input b, switched to the
+ * input dimension when ksk_out is given. */
+void mosfhet_eval_LUTs_bits(TLWE **out, TLWE **in, int size, TRLWE **LUTs, int tables, int count, Bootstrap_Key key, TRLWE_KS_Key *kska, Generic_KS_Key kskb,
+                            TLWE_KS_Key ksk_out) {
+  need(out && in && LUTs && key && kska && kska[0] && kskb && size >= 1 && count >= 1 && tables >= 1 && tables <= MOSFHET_HIP_LUT_MAX_TABLES, "mosfhet_eval_LUTs_bits: bad argument");
+  const int n = key->n, N = key->N;
+  need(N == 1024 || N == 2048, "mosfhet_eval_LUTs_bits: ring degree must be 1024 or 2048");
+  int log_N = 0;
+  while ((1 << log_N) < N) log_N++;
+  const int n_res = ksk_out ? out[0][0]->n : N;
+  const size_t n_luts = size > log_N ? (size_t)1 << (size - log_N) : 1, row = (size_t)2 * N;
+  const size_t lut_w = (size_t)tables * n_luts * row, in_w = (size_t)count * (size_t)size * ((size_t)n + 1), out_w = (size_t)count * (size_t)tables * ((size_t)n_res + 1);
+  const size_t up_w = lut_w + in_w;
+  Torus *h = (Torus *)mc_hstage_alloc(sizeof(Torus) * (up_w > out_w ? up_w : out_w)), *d = (Torus *)mc_stage_alloc(sizeof(Torus) * (up_w + out_w));
+  for (int tb = 0; tb < tables; tb++)
+    for (size_t j = 0; j < n_luts; j++) mc_trlwe_to_flat(h + ((size_t)tb * n_luts + j) * row, LUTs[tb][j]);
+  for (int b = 0; b < count; b++)
+    for (int i = 0; i < size; i++) {
+      Torus *w = h + lut_w + ((size_t)b * (size_t)size + (size_t)i) * ((size_t)n + 1);
+      need(in[b][i]->n == n, "mosfhet_eval_LUTs_bits: an input bit is not an LWE sample of the bootstrap key's dimension");
+      memcpy(w, in[b][i]->a, sizeof(Torus) * (size_t)n);
+      w[n] = in[b][i]->b;
+    }
+  mc_dev_copy(d, h, sizeof(Torus) * up_w, HIP_H2D);
+  check_rc(mosfhet_hip_lut_bits_batch(ectx(), (mosfhet_hip_bsk_t)mc_key_here(key->device, MC_KEY_BSK), (mosfhet_hip_gak_t)mc_key_here(kska[0]->device, MC_KEY_GAK),
+                                      (mosfhet_hip_ksk_t)mc_key_here(kskb->device, MC_KEY_KSK), ksk_out ? (mosfhet_hip_ksk_t)mc_key_here(ksk_out->device, MC_KEY_KSK) : NULL,
+                                      d + up_w, d, d + lut_w, size, tables, count, NULL),
+           "mosfhet_eval_LUTs_bits");
+  mc_dev_copy(h, d + up_w, sizeof(Torus) * out_w, HIP_D2H);
+  for (int b = 0; b < count; b++)
+    for (int tb = 0; tb < tables; tb++) {
+      const Torus *w = h + ((size_t)b * (size_t)tables + (size_t)tb) * ((size_t)n_res + 1);
+      need(out[b][tb]->n == n_res, "mosfhet_eval_LUTs_bits: an output sample has the wrong dimension (n with ksk_out, N without)");
+      memcpy(out[b][tb]->a, w, sizeof(Torus) * (size_t)n_res);
+      out[b][tb]->b = w[n_res];
+    }
+  mc_hstage_free(h);
+}
+
 /* src/trlwe.c:775-781: out = KeySwitch_{ks_key}(in(X^gen)); ks_key switches from key(X^gen) back to key (any entry of a key set) */
 void trlwe_eval_automorphism(TRLWE out, TRLWE in, uint64_t gen, TRLWE_KS_Key ks_key) {
   const int N = in->b->N;

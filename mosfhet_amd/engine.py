@@ -120,6 +120,21 @@ def set_leveled_lut_workspace(nbytes):
     _check(lib().mosfhet_hip_set_leveled_lut_workspace(C.c_longlong(int(nbytes))))
 
 
+def lut_bits_plan(N, l, size, tables, count, cus=256):
+    """What a lut_bits call will do (no device needed): dict(chunk, chunks, selector_bytes, cb_bits, lut) -- inputs per chunk, chunks, bytes of one chunk's
+    selectors, bits per circuit-bootstrap launch and leveled_lut_tables_plan's dict for one chunk.  include/mosfhet_hip.h: mosfhet_hip_lut_bits_plan."""
+    plan = (C.c_longlong * 10)()
+    _check(lib().mosfhet_hip_lut_bits_plan(int(N), int(l), int(size), int(tables), int(count), int(cus), plan))
+    return dict(chunk=int(plan[0]), chunks=int(plan[1]), selector_bytes=int(plan[2]), cb_bits=int(plan[3]),
+                lut=dict(levels=int(plan[4]), nodes=int(plan[5]), chunk=int(plan[6]), tables_per_pass=int(plan[7]), workspace_bytes=int(plan[8]), group=int(plan[9])))
+
+
+def set_lut_bits_workspace(nbytes):
+    """Bound of lut_bits' selector workspace (0 restores the default of 2 GiB): batches whose selectors need more run in chunks of whole inputs; with a key whose
+    product order is set, results do not depend on it."""
+    _check(lib().mosfhet_hip_set_lut_bits_workspace(C.c_longlong(int(nbytes))))
+
+
 class BootstrapKey:
     def __init__(self, engine, handle, n, k, N, l, Bg_bit):
         self.engine, self.h = engine, handle
@@ -320,6 +335,36 @@ class Engine:
         ev = self._level_events(level_events, bsk.l)
         _check(lib().mosfhet_hip_circuit_bootstrap_3_batch_ev(self.h, bsk.h, kska.h, kskb.h, _ptr(out), _ptr(ct), count, self._stream(), ev))
         return out
+
+    def circuit_bootstrap_3_dft(self, bsk, kska, kskb, ct, out=None):
+        """circuit_bootstrap_3 followed by trgsw_to_dft in one call, without the torus-domain TRGSWs in between: [count][2l][2][N] doubles, word for word
+        trgsw_to_dft(circuit_bootstrap_3(...)); reshaped to [count / size][size][2l][2][N] it is leveled_lut's sel_dft."""
+        count = ct.shape[0]
+        if out is None:
+            out = self.torch.empty((count, 2 * bsk.l, 2, bsk.N), dtype=self.torch.float64, device=self.device)
+        assert tuple(out.shape) == (count, 2 * bsk.l, 2, bsk.N) and out.dtype == self.torch.float64, tuple(out.shape)
+        _check(lib().mosfhet_hip_circuit_bootstrap_3_dft_batch(self.h, bsk.h, kska.h, kskb.h, _ptr(out), _ptr(ct), count, self._stream()))
+        return out
+
+    def lut_bits(self, bsk, kska, kskb, luts, ct, ksk_out=None, out=None):
+        """A size-bit -> tables-bit function on a batch of inputs given as LWE-encrypted bits: circuit_bootstrap_3 -> trgsw_to_dft -> leveled_lut_tables
+        (-> tlwe_keyswitch with ksk_out) in one call, the selectors a bounded internal workspace.  ct: [count][size][n + 1], bit i of input b at [b][i];
+        luts: [tables][max(1, 2^size / N)][2][N], read only; returns [count][tables][n + 1] with ksk_out (the ct of the next call when tables == size), else
+        [count][tables][N + 1]."""
+        count, size, tables, N = ct.shape[0], ct.shape[1], luts.shape[0], bsk.N
+        assert tuple(ct.shape) == (count, size, bsk.n + 1), tuple(ct.shape)
+        assert tuple(luts.shape) == (tables, max(1, (1 << size) // N), 2, N), tuple(luts.shape)
+        width = (bsk.n if ksk_out is not None else N) + 1
+        if out is None:
+            out = self.empty(count, tables, width)
+        assert tuple(out.shape) == (count, tables, width)
+        _check(lib().mosfhet_hip_lut_bits_batch(self.h, bsk.h, kska.h, kskb.h, ksk_out.h if ksk_out is not None else None, _ptr(out), _ptr(luts), _ptr(ct), int(size),
+                                                int(tables), int(count), self._stream()))
+        return out
+
+    def lut_bits_plan(self, N, l, size, tables, count):
+        """lut_bits_plan() at this device's CU count."""
+        return lut_bits_plan(N, l, size, tables, count, self.torch.cuda.get_device_properties(self.device).multi_processor_count)
 
     def public_mux(self, p0, p1, sel, Bg_bit, out=None):
         count, l, two, N = sel.shape
