@@ -302,6 +302,13 @@ void mosfhet_eval_LUTs_inputs(TLWE **out /*[count][tables]*/, TRGSW_DFT **inputs
  * the device in a bounded workspace.  Tables LEFT UNCHANGED.  Synchronous; aborts on error; primary device; N = 1024 or 2048. */
 void mosfhet_eval_LUTs_bits(TLWE **out /*[count][tables]*/, TLWE **in /*[count][size]*/, int size, TRLWE **LUTs /*[tables]*/, int tables, int count,
                             Bootstrap_Key key, TRLWE_KS_Key *kska, Generic_KS_Key kskb, TLWE_KS_Key ksk_out /* or NULL */);
+/* Several outputs packed into one table (new; mosfhet_hip_leveled_lut_packed_batch): an entry of a table is m = 2^pack_log adjacent coefficients, LUTs[tb] an array
+ * of max(1, 2^(size + pack_log) / N) TRLWEs, LEFT UNCHANGED; out[b][tb * m + t] receives output t of the entry input b selects in table tb (sample extraction at
+ * idx t of the one rotated accumulator).  0 <= pack_log <= log2 N - 1.  Synchronous; aborts on error; primary device; N = 1024 or 2048. */
+void mosfhet_eval_LUTs_packed_inputs(TLWE **out /*[count][tables * m]*/, TRGSW_DFT **inputs, int size, TRLWE **LUTs /*[tables][n_luts]*/, int tables, int pack_log, int count);
+/* ... and the whole loop on LWE-encrypted bits (mosfhet_hip_lut_bits_packed_batch), after the pattern of mosfhet_eval_LUTs_bits: out[b][tb * m + t]. */
+void mosfhet_eval_LUTs_packed_bits(TLWE **out /*[count][tables * m]*/, TLWE **in /*[count][size]*/, int size, TRLWE **LUTs /*[tables][n_luts]*/, int tables, int pack_log,
+                                   int count, Bootstrap_Key key, TRLWE_KS_Key *kska, Generic_KS_Key kskb, TLWE_KS_Key ksk_out /* or NULL */);
 
 /* ---- flat helpers used by the Python binding and bench.py (new) ----
  * Generate a whole bootstrap / key-switch key in the flat torus-domain layouts of mosfhet_hip.h. */

@@ -544,6 +544,35 @@ int mosfhet_hip_lut_bits_batch(mosfhet_hip_ctx_t ctx, mosfhet_hip_bsk_t bsk, mos
 int mosfhet_hip_lut_bits_plan(int N, int l, int size, int tables, int count, int cus, long long *plan /*[10]*/);
 int mosfhet_hip_set_lut_bits_workspace(long long bytes);
 
+/* Several OUTPUTS packed into one table (CGGI's other packing): a table entry occupies m = 2^pack_log adjacent coefficients, the m output bits of that entry, so an
+ * n-bit -> m-bit function is ONE table with ONE rotation chain where the calls above run m tables with m chains.  An S-box at N = 2048 is exactly one TRLWE
+ * (256 entries x 8 bits): no tree, 8 rotate steps, 8 extractions.
+ *   d_sel_dft  [count][size][2l][2][N/2] complex: exactly the layout of mosfhet_hip_leveled_lut_batch
+ *   d_luts     [tables][n_luts][2][N], n_luts = max(1, 2^(size + pack_log) / N): output t of entry x of table tb is coefficient (x m + t) mod N of TRLWE
+ *              (x m + t) / N; trivial or encrypted; READ ONLY.  When 2^(size + pack_log) < N the coefficients behind the table are never selected.
+ *   d_out      [count][tables][m][N + 1]: as [count * tables * m][N + 1] it is "bit tb m + t of input b", the batch mosfhet_hip_tlwe_keyswitch_batch takes next
+ * Per input: tree levels i = 0 .. levels - 1, levels = max(0, size - (log2 N - pack_log)), level i with selector size - i - 1 over 2^(levels - i - 1) nodes; then
+ * blind_rotate of node 0 with a[i] = int2torus(2N - 2^(i + pack_log), log2(2N)) and the first steps = min(size, log2 N - pack_log) selectors; then
+ * trlwe_extract_tlwe(.., t) (src/trlwe.c:540-552) for t < m.  Summation order and rounding are those of the calls above; no key handle is consulted; no word
+ * depends on count, tables, passes, chunks or groups.  pack_log == 0 IS mosfhet_hip_leveled_lut_tables_batch.
+ * Arguments as for mosfhet_hip_leveled_lut_tables_batch, with 0 <= pack_log <= log2 N - 1 and size + pack_log <= log2 N + MOSFHET_HIP_LUT_MAX_LEVELS; anything else
+ * MOSFHET_HIP_EINVAL with a message naming the argument, before any HIP call; count == 0 returns MOSFHET_HIP_OK.  Stream, pool, workspace bound, passes, chunks and
+ * groups are those of mosfhet_hip_leveled_lut_tables_batch at the packed number of levels.
+ * mosfhet_hip_leveled_lut_packed_plan is the function the launcher uses, pure (no GPU), `cus` sizes grids only: plan = {the six fields of
+ * mosfhet_hip_leveled_lut_tables_plan at the packed levels and nodes, rotate steps, outputs per input = tables * m}. */
+int mosfhet_hip_leveled_lut_packed_batch(mosfhet_hip_ctx_t ctx, uint64_t *d_out, const double *d_sel_dft, const uint64_t *d_luts, int size, int N, int l, int Bg_bit,
+                                         int tables, int pack_log, int count, void *stream);
+int mosfhet_hip_leveled_lut_packed_plan(int N, int l, int size, int tables, int pack_log, int count, int cus, long long *plan /*[8]*/);
+/* mosfhet_hip_lut_bits_batch with the packed call as its middle: tables * m output bits per input.  d_luts as above; d_out with ksk_out [count][tables * m][n + 1]
+ * -- the d_in of the next call when tables * m == size -- and without it [count][tables * m][N + 1].  Everything else (keys, chunks, selector workspace of `size`
+ * selectors per input, words, stream) as for mosfhet_hip_lut_bits_batch; the staging in front of the output key switch is [chunk][tables * m][N + 1].  Null handles
+ * and the ranges of size, pack_log (0 .. 10, size + pack_log <= 21), tables and count are checked before any handle is read; pack_log == 0 IS
+ * mosfhet_hip_lut_bits_batch.  A round is still almost all circuit bootstrap: this variant closes the interface, it does not shorten the round.
+ * plan = {the four fields of mosfhet_hip_lut_bits_plan, then the eight of mosfhet_hip_leveled_lut_packed_plan for a chunk}. */
+int mosfhet_hip_lut_bits_packed_batch(mosfhet_hip_ctx_t ctx, mosfhet_hip_bsk_t bsk, mosfhet_hip_gak_t kska, mosfhet_hip_ksk_t kskb, mosfhet_hip_ksk_t ksk_out /* or NULL */,
+                                      uint64_t *d_out, const uint64_t *d_luts, const uint64_t *d_in, int size, int tables, int pack_log, int count, void *stream);
+int mosfhet_hip_lut_bits_packed_plan(int N, int l, int size, int tables, int pack_log, int count, int cus, long long *plan /*[12]*/);
+
 /* Key images for the on-disk formats (save_bootstrap_key / load_new_bootstrap_key src/bootstrap.c:63-104, trlwe_save_KS_key /
  * trlwe_load_new_KS_key src/keyswitch.c:122-160, tlwe_save_KS_key / tlwe_load_new_KS_key src/tlwe.c:247-287, trlwe_save_generic_ks_key /
  * trlwe_load_new_generic_ks_key src/keyswitch.c:409-455).  DFT-domain contents are backend-defined in the reference too (src/polynomial.c:336-357):

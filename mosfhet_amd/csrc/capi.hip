@@ -122,6 +122,7 @@ static int pool_get(int device, int slot, size_t words, uint64_t **out) {
 
 struct mosfhet_hip_bsk {
   mosfhet_hip_ctx_t ctx = nullptr;
+  int device = 0;   // ctx's device, copied at creation: freeing or cloning a key must not read a context that may already be destroyed
   d2 *d_bk = nullptr;  // [n][(k+1)l][k+1][P][lanes]
   int n, k, N, l, Bg_bit;
   int unfolding = 1;          // > 1: d_bk is null and d_su holds the torus-domain samples of new_bootstrap_key (src/bootstrap.c:23-48)
@@ -134,7 +135,7 @@ struct mosfhet_hip_bsk {
   bool owns = true;           // false: d_bk belongs to the caller (mosfhet_hip_bsk_view_create)
   int order = MOSFHET_HIP_ORDER_AUTO;   // summation order of the external products (mosfhet_hip_bsk_set_product_order): read by the launchers through bootstrap_plan
   ~mosfhet_hip_bsk() {
-    if (ctx) (void)hipSetDevice(ctx->device);
+    if (ctx) (void)hipSetDevice(device);
     if (d_bk && owns) (void)hipFree(d_bk);
     if (d_su) (void)hipFree(d_su);
     if (d_su_dft) (void)hipFree(d_su_dft);
@@ -143,6 +144,7 @@ struct mosfhet_hip_bsk {
 
 struct mosfhet_hip_ksk {
   mosfhet_hip_ctx_t ctx = nullptr;
+  int device = 0;   // ctx's device, copied at creation: freeing or cloning a key must not read a context that may already be destroyed
   uint64_t *d_ksk = nullptr;
   int n_in, n_out, t, base_bit;
   int row, b_word;  // output row words and the word that receives in.b (LWE: n_out + 1, n_out; packing -> TRLWE: 2N, N)
@@ -150,18 +152,19 @@ struct mosfhet_hip_ksk {
   uint64_t seed = 0;
   size_t bytes = 0;
   ~mosfhet_hip_ksk() {
-    if (ctx) (void)hipSetDevice(ctx->device);
+    if (ctx) (void)hipSetDevice(device);
     if (d_ksk) (void)hipFree(d_ksk);
   }
 };
 
 struct mosfhet_hip_gak {
   mosfhet_hip_ctx_t ctx = nullptr;
+  int device = 0;   // ctx's device, copied at creation: freeing or cloning a key must not read a context that may already be destroyed
   d2 *d_ak = nullptr;  // [entries][t][2][8][T]
   int N, t, base_bit, entries;
   size_t bytes = 0;
   ~mosfhet_hip_gak() {
-    if (ctx) (void)hipSetDevice(ctx->device);
+    if (ctx) (void)hipSetDevice(device);
     if (d_ak) (void)hipFree(d_ak);
   }
 };
@@ -389,7 +392,7 @@ extern "C" int mosfhet_hip_bsk_create_from_device(mosfhet_hip_ctx_t ctx, mosfhet
   HIP_TRY(hipSetDevice(ctx->device));
   std::unique_ptr<mosfhet_hip_bsk> b_owner(new mosfhet_hip_bsk());
   mosfhet_hip_bsk *b = b_owner.get();
-  b->ctx = ctx; b->n = n; b->k = k; b->N = N; b->l = l; b->Bg_bit = Bg_bit;
+  b->ctx = ctx; b->device = ctx->device; b->n = n; b->k = k; b->N = N; b->l = l; b->Bg_bit = Bg_bit;
   b->general = general_ring(k, N);
   const size_t polys = (size_t)n * (k + 1) * l * (k + 1);
   b->bytes = polys * N * sizeof(double);
@@ -433,7 +436,7 @@ extern "C" size_t mosfhet_hip_bsk_bytes(mosfhet_hip_bsk_t bsk) { return bsk ? bs
 extern "C" int mosfhet_hip_bsk_export_dft(mosfhet_hip_bsk_t bsk, double *h_out) {
   if (!bsk || !h_out) return fail(MOSFHET_HIP_EINVAL, "bsk_export: bad argument");
   if (bsk->unfolding > 1) return fail(MOSFHET_HIP_EINVAL, "bsk_export: an unfolded key has no DFT form");
-  HIP_TRY(hipSetDevice(bsk->ctx->device));
+  HIP_TRY(hipSetDevice(bsk->device));
   std::vector<double> tmp(bsk->bytes / sizeof(double));
   HIP_TRY(hipMemcpy(tmp.data(), bsk->d_bk, bsk->bytes, hipMemcpyDeviceToHost));
   const int M = bsk->N / 2;
@@ -1299,7 +1302,7 @@ extern "C" int mosfhet_hip_ksk_create(mosfhet_hip_ctx_t ctx, mosfhet_hip_ksk_t *
   HIP_TRY(hipSetDevice(ctx->device));
   std::unique_ptr<mosfhet_hip_ksk> k_owner(new mosfhet_hip_ksk());
   mosfhet_hip_ksk *k = k_owner.get();
-  k->ctx = ctx; k->n_in = n_in; k->n_out = n_out; k->t = t; k->base_bit = base_bit;
+  k->ctx = ctx; k->device = ctx->device; k->n_in = n_in; k->n_out = n_out; k->t = t; k->base_bit = base_bit;
   k->row = n_out + 1; k->b_word = n_out;
   k->bytes = (size_t)n_in * t * ((1u << base_bit) - 1) * (n_out + 1) * sizeof(uint64_t);
   HIP_TRY(hipMalloc((void **)&k->d_ksk, k->bytes + ksw_slack_bytes(k->row)));   // (+ slack: the word-lane key switch reads past the last row, keyswitch_words_kernels.h)
@@ -1358,7 +1361,7 @@ extern "C" int mosfhet_hip_tlwe_addto_batch(mosfhet_hip_ctx_t ctx, uint64_t *d_o
   return MOSFHET_HIP_OK;
 }
 
-static int bsk_scratch(mosfhet_hip_bsk_t bsk, size_t words, uint64_t **out) { return pool_get(bsk->ctx->device, POOL_BSK, words, out); }
+static int bsk_scratch(mosfhet_hip_bsk_t bsk, size_t words, uint64_t **out) { return pool_get(bsk->device, POOL_BSK, words, out); }
 
 extern "C" int mosfhet_hip_full_domain_functional_bootstrap_batch(mosfhet_hip_ctx_t ctx, mosfhet_hip_bsk_t bsk, mosfhet_hip_ksk_t ksk,
                                                                   uint64_t *d_out, const uint64_t *d_tv, int tv_count,
@@ -1373,7 +1376,7 @@ extern "C" int mosfhet_hip_full_domain_functional_bootstrap_batch(mosfhet_hip_ct
   const size_t w_tv = (size_t)(k + 1) * N, w_sign = (size_t)count * (k * N + 1), w_in2 = (size_t)count * (n + 1);
   // (general keys keep their accumulators in the POOL_BSK slot: this composition's temporaries take another one)
   uint64_t *tv_sign = nullptr;
-  int rc = bsk->general ? pool_get(bsk->ctx->device, POOL_EXT0, w_tv + w_sign + w_in2, &tv_sign) : bsk_scratch(bsk, w_tv + w_sign + w_in2, &tv_sign);
+  int rc = bsk->general ? pool_get(bsk->device, POOL_EXT0, w_tv + w_sign + w_in2, &tv_sign) : bsk_scratch(bsk, w_tv + w_sign + w_in2, &tv_sign);
   if (rc) return rc;
   uint64_t *ct_sign = tv_sign + w_tv, *in2 = ct_sign + w_sign;
   hipStream_t s = pick(ctx, stream);
@@ -1426,7 +1429,7 @@ extern "C" int mosfhet_hip_trlwe_ksk_create(mosfhet_hip_ctx_t ctx, mosfhet_hip_g
   HIP_TRY(hipSetDevice(ctx->device));
   std::unique_ptr<mosfhet_hip_gak> g_owner(new mosfhet_hip_gak());
   mosfhet_hip_gak *g = g_owner.get();
-  g->ctx = ctx; g->N = N; g->t = t; g->base_bit = base_bit; g->entries = entries;
+  g->ctx = ctx; g->device = ctx->device; g->N = N; g->t = t; g->base_bit = base_bit; g->entries = entries;
   const size_t polys = (size_t)entries * t * 2;
   g->bytes = polys * N * sizeof(double);
   DevBuf tmp;                                      // torus-domain rows, released on every way out

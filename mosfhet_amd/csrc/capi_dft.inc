@@ -11,7 +11,7 @@ extern "C" int mosfhet_hip_bsk_view_create(mosfhet_hip_ctx_t ctx, mosfhet_hip_bs
   int rc = check_params("bsk_view_create", k, N, l, Bg_bit);
   if (rc) return rc;
   std::unique_ptr<mosfhet_hip_bsk> b(new mosfhet_hip_bsk());
-  b->ctx = ctx; b->n = n; b->k = k; b->N = N; b->l = l; b->Bg_bit = Bg_bit;
+  b->ctx = ctx; b->device = ctx->device; b->n = n; b->k = k; b->N = N; b->l = l; b->Bg_bit = Bg_bit;
   b->d_bk = (d2 *)d_dft;
   b->owns = false;
   b->bytes = (size_t)n * (k + 1) * l * (k + 1) * N * sizeof(double);

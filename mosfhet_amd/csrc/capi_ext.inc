@@ -3,7 +3,7 @@
 // one stream; temporaries live in the calling thread's pool (capi.hip: ThreadPool), grown on demand.
 
 static int ctx_scratch(mosfhet_hip_ctx_t ctx, int slot, size_t words, uint64_t **out) { return pool_get(ctx->device, POOL_CTX0 + slot, words, out); }
-static int ext_scratch(mosfhet_hip_bsk_t bsk, int slot, size_t words, uint64_t **out) { return pool_get(bsk->ctx->device, POOL_EXT0 + slot, words, out); }
+static int ext_scratch(mosfhet_hip_bsk_t bsk, int slot, size_t words, uint64_t **out) { return pool_get(bsk->device, POOL_EXT0 + slot, words, out); }
 
 // ---- secret of the on-device key generators (csrc/keygen_kernels.h): the ChaCha20 key of the NOISE terms.  Independent of the public mask seeds the
 // generate calls take; drawn from the operating system at first use unless the caller installs one (the host layer hands over 32 bytes of its own
@@ -475,7 +475,7 @@ static int unfold2_ready(mosfhet_hip_ctx_t ctx, mosfhet_hip_bsk *b) {
   int caller_dev = -1;
   (void)hipGetDevice(&caller_dev);
   struct Restore { int d; ~Restore() { if (d >= 0) (void)hipSetDevice(d); } } restore{caller_dev};   // the caller's current device stays what it was
-  HIP_TRY(hipSetDevice(b->ctx->device));
+  HIP_TRY(hipSetDevice(b->device));
   d2 *dft = nullptr;
   HIP_TRY(hipMalloc((void **)&dft, b->bytes));
   const size_t polys = (size_t)b->n / 2 * 4 * 2 * b->l * 2;
@@ -517,7 +517,7 @@ extern "C" int mosfhet_hip_bsk_unfolded_create(mosfhet_hip_ctx_t ctx, mosfhet_hi
   HIP_TRY(hipSetDevice(ctx->device));
   std::unique_ptr<mosfhet_hip_bsk> b_owner(new mosfhet_hip_bsk());
   mosfhet_hip_bsk *b = b_owner.get();
-  b->ctx = ctx; b->d_bk = nullptr; b->n = n; b->k = 1; b->N = N; b->l = l; b->Bg_bit = Bg_bit; b->unfolding = unfolding;
+  b->ctx = ctx; b->device = ctx->device; b->d_bk = nullptr; b->n = n; b->k = 1; b->N = N; b->l = l; b->Bg_bit = Bg_bit; b->unfolding = unfolding;
   b->bytes = (size_t)n * ((size_t)1 << unfolding) / unfolding * 2 * l * 2 * N * sizeof(uint64_t);
   HIP_TRY(hipMalloc((void **)&b->d_su, b->bytes));
   HIP_TRY(hipMemcpy(b->d_su, h_su, b->bytes, hipMemcpyHostToDevice));
@@ -754,7 +754,7 @@ static int table_ksk_generate(mosfhet_hip_ctx_t ctx, mosfhet_hip_ksk_t *out, int
   const size_t n_rows = (size_t)entries * t * cands;
   std::unique_ptr<mosfhet_hip_ksk> k_owner(new mosfhet_hip_ksk());
   mosfhet_hip_ksk *k = k_owner.get();
-  k->ctx = ctx; k->n_in = entries; k->n_out = 2 * N - 1; k->t = t; k->base_bit = base_bit;
+  k->ctx = ctx; k->device = ctx->device; k->n_in = entries; k->n_out = 2 * N - 1; k->t = t; k->base_bit = base_bit;
   k->row = 2 * N; k->b_word = kind == 0 ? N : -1;
   k->compressed = compressed != 0; k->seed = seed;
   k->bytes = n_rows * (compressed ? 1 : 2) * N * sizeof(uint64_t);
@@ -934,7 +934,7 @@ extern "C" int mosfhet_hip_bsk_unfolded_generate(mosfhet_hip_ctx_t ctx, mosfhet_
     }
   std::unique_ptr<mosfhet_hip_bsk> b_owner(new mosfhet_hip_bsk());
   mosfhet_hip_bsk *b = b_owner.get();
-  b->ctx = ctx; b->d_bk = nullptr; b->n = n; b->k = 1; b->N = N; b->l = l; b->Bg_bit = Bg_bit; b->unfolding = unfolding;
+  b->ctx = ctx; b->device = ctx->device; b->d_bk = nullptr; b->n = n; b->k = 1; b->N = N; b->l = l; b->Bg_bit = Bg_bit; b->unfolding = unfolding;
   const size_t n_rows = entries * 2 * l;
   b->bytes = n_rows * 2 * N * sizeof(uint64_t);
   HIP_TRY(hipMalloc((void **)&b->d_su, b->bytes));
@@ -966,7 +966,7 @@ extern "C" int mosfhet_hip_trlwe_ksk_generate(mosfhet_hip_ctx_t ctx, mosfhet_hip
   HIP_TRY(hipSetDevice(ctx->device));
   std::unique_ptr<mosfhet_hip_gak> g_owner(new mosfhet_hip_gak());
   mosfhet_hip_gak *g = g_owner.get();
-  g->ctx = ctx; g->N = N; g->t = t; g->base_bit = base_bit; g->entries = entries;
+  g->ctx = ctx; g->device = ctx->device; g->N = N; g->t = t; g->base_bit = base_bit; g->entries = entries;
   const size_t n_rows = (size_t)entries * t, polys = n_rows * 2;
   g->bytes = polys * N * sizeof(double);
   DevBuf rows, keys;
@@ -995,7 +995,7 @@ extern "C" int mosfhet_hip_tlwe_ksk_generate(mosfhet_hip_ctx_t ctx, mosfhet_hip_
   const size_t n_rows = (size_t)n_in * t * ((1u << base_bit) - 1);
   std::unique_ptr<mosfhet_hip_ksk> k_owner(new mosfhet_hip_ksk());
   mosfhet_hip_ksk *k = k_owner.get();
-  k->ctx = ctx; k->n_in = n_in; k->n_out = n_out; k->t = t; k->base_bit = base_bit;
+  k->ctx = ctx; k->device = ctx->device; k->n_in = n_in; k->n_out = n_out; k->t = t; k->base_bit = base_bit;
   k->row = n_out + 1; k->b_word = n_out;
   k->compressed = compressed != 0; k->seed = seed;
   k->bytes = n_rows * (compressed ? 1 : (size_t)n_out + 1) * sizeof(uint64_t);
@@ -1025,7 +1025,7 @@ extern "C" int mosfhet_hip_ksk_export_rows(mosfhet_hip_ksk_t ksk, size_t first_r
     const int mask_words = ksk->b_word == ksk->row - 1 ? ksk->row - 1 : ksk->row / 2;     // LWE rows keep one b word, TRLWE rows their b polynomial
     if ((first_row + count) * (size_t)(ksk->row - mask_words) * sizeof(uint64_t) > ksk->bytes) return fail(MOSFHET_HIP_EINVAL, "ksk_export_rows: out of range");
     if (count == 0) return MOSFHET_HIP_OK;
-    HIP_TRY(hipSetDevice(ksk->ctx->device));
+    HIP_TRY(hipSetDevice(ksk->device));
     uint64_t *tmp = nullptr;
     HIP_TRY(hipMalloc((void **)&tmp, count * row_bytes));
     hipLaunchKernelGGL(table_expand_kernel, dim3((unsigned)count), dim3(256), 0, nullptr, tmp, ksk->d_ksk, ksk->row, mask_words, ksk->seed, first_row);
@@ -1035,7 +1035,7 @@ extern "C" int mosfhet_hip_ksk_export_rows(mosfhet_hip_ksk_t ksk, size_t first_r
     return MOSFHET_HIP_OK;
   }
   if ((first_row + count) * row_bytes > ksk->bytes) return fail(MOSFHET_HIP_EINVAL, "ksk_export_rows: out of range");
-  HIP_TRY(hipSetDevice(ksk->ctx->device));
+  HIP_TRY(hipSetDevice(ksk->device));
   HIP_TRY(hipMemcpy(h_out, (const char *)ksk->d_ksk + first_row * row_bytes, count * row_bytes, hipMemcpyDeviceToHost));
   return MOSFHET_HIP_OK;
 }
@@ -1091,7 +1091,7 @@ extern "C" int mosfhet_hip_bsk_info(mosfhet_hip_bsk_t bsk, int *out6) {
 
 extern "C" int mosfhet_hip_bsk_export(mosfhet_hip_bsk_t bsk, void *h_out) {
   if (!bsk || !h_out) return fail(MOSFHET_HIP_EINVAL, "bsk_export: bad argument");
-  HIP_TRY(hipSetDevice(bsk->ctx->device));
+  HIP_TRY(hipSetDevice(bsk->device));
   HIP_TRY(hipMemcpy(h_out, bsk->unfolding > 1 ? (const void *)bsk->d_su : (const void *)bsk->d_bk, bsk->bytes, hipMemcpyDeviceToHost));
   return MOSFHET_HIP_OK;
 }
@@ -1107,7 +1107,7 @@ extern "C" int mosfhet_hip_bsk_import(mosfhet_hip_ctx_t ctx, mosfhet_hip_bsk_t *
   HIP_TRY(hipSetDevice(ctx->device));
   std::unique_ptr<mosfhet_hip_bsk> b_owner(new mosfhet_hip_bsk());
   mosfhet_hip_bsk *b = b_owner.get();
-  b->ctx = ctx; b->n = n; b->k = k; b->N = N; b->l = l; b->Bg_bit = Bg_bit;
+  b->ctx = ctx; b->device = ctx->device; b->n = n; b->k = k; b->N = N; b->l = l; b->Bg_bit = Bg_bit;
   b->general = general_ring(k, N);
   b->bytes = (size_t)n * (k + 1) * l * (k + 1) * N * sizeof(double);
   hipError_t e = hipMalloc((void **)&b->d_bk, b->bytes);
@@ -1127,7 +1127,7 @@ extern "C" size_t mosfhet_hip_trlwe_ksk_bytes(mosfhet_hip_gak_t tks) { return tk
 
 extern "C" int mosfhet_hip_trlwe_ksk_export(mosfhet_hip_gak_t tks, void *h_out) {
   if (!tks || !h_out) return fail(MOSFHET_HIP_EINVAL, "trlwe_ksk_export: bad argument");
-  HIP_TRY(hipSetDevice(tks->ctx->device));
+  HIP_TRY(hipSetDevice(tks->device));
   HIP_TRY(hipMemcpy(h_out, tks->d_ak, tks->bytes, hipMemcpyDeviceToHost));
   return MOSFHET_HIP_OK;
 }
@@ -1139,7 +1139,7 @@ extern "C" int mosfhet_hip_trlwe_ksk_import(mosfhet_hip_ctx_t ctx, mosfhet_hip_g
   HIP_TRY(hipSetDevice(ctx->device));
   std::unique_ptr<mosfhet_hip_gak> g_owner(new mosfhet_hip_gak());
   mosfhet_hip_gak *g = g_owner.get();
-  g->ctx = ctx; g->N = N; g->t = t; g->base_bit = base_bit; g->entries = entries;
+  g->ctx = ctx; g->device = ctx->device; g->N = N; g->t = t; g->base_bit = base_bit; g->entries = entries;
   g->bytes = (size_t)entries * t * 2 * N * sizeof(double);
   hipError_t e = hipMalloc((void **)&g->d_ak, g->bytes);
   if (e == hipSuccess) e = hipMemcpy(g->d_ak, h_image, g->bytes, hipMemcpyHostToDevice);
@@ -1164,7 +1164,7 @@ extern "C" int mosfhet_hip_ksk_alloc(mosfhet_hip_ctx_t ctx, mosfhet_hip_ksk_t *o
   HIP_TRY(hipSetDevice(ctx->device));
   std::unique_ptr<mosfhet_hip_ksk> k_owner(new mosfhet_hip_ksk());
   mosfhet_hip_ksk *k = k_owner.get();
-  k->ctx = ctx; k->t = t; k->base_bit = base_bit;
+  k->ctx = ctx; k->device = ctx->device; k->t = t; k->base_bit = base_bit;
   k->n_in = n + (kind == 2);
   k->n_out = kind == 0 ? n_out_or_N : 2 * n_out_or_N - 1;
   k->row = k->n_out + 1;
@@ -1181,7 +1181,7 @@ extern "C" int mosfhet_hip_ksk_import_rows(mosfhet_hip_ksk_t ksk, size_t first_r
   if (ksk->compressed) return fail(MOSFHET_HIP_EINVAL, "ksk_import_rows: a seed-compressed key has no mask rows to import");
   const size_t row_bytes = (size_t)ksk->row * sizeof(uint64_t);
   if ((first_row + count) * row_bytes > ksk->bytes) return fail(MOSFHET_HIP_EINVAL, "ksk_import_rows: out of range");
-  HIP_TRY(hipSetDevice(ksk->ctx->device));
+  HIP_TRY(hipSetDevice(ksk->device));
   HIP_TRY(hipMemcpy((char *)ksk->d_ksk + first_row * row_bytes, h_in, count * row_bytes, hipMemcpyHostToDevice));
   return MOSFHET_HIP_OK;
 }
@@ -1241,22 +1241,22 @@ static int copy_across(void *dst, int dst_dev, const void *src, int src_dev, siz
 extern "C" int mosfhet_hip_bsk_clone(mosfhet_hip_ctx_t dst_ctx, mosfhet_hip_bsk_t *out, mosfhet_hip_bsk_t src) {
   if (!dst_ctx || !out || !src) return fail(MOSFHET_HIP_EINVAL, "bsk_clone: bad argument");
   if (!src->owns) return fail(MOSFHET_HIP_EINVAL, "bsk_clone: a key view does not own its entries");
-  HIP_TRY(hipSetDevice(src->ctx->device));
+  HIP_TRY(hipSetDevice(src->device));
   HIP_TRY(hipDeviceSynchronize());   // the key may still be in the making on a stream of its own device
   HIP_TRY(hipSetDevice(dst_ctx->device));
   std::unique_ptr<mosfhet_hip_bsk> b_owner(new mosfhet_hip_bsk());
   mosfhet_hip_bsk *b = b_owner.get();
-  b->ctx = dst_ctx; b->n = src->n; b->k = src->k; b->N = src->N; b->l = src->l; b->Bg_bit = src->Bg_bit;
+  b->ctx = dst_ctx; b->device = dst_ctx->device; b->n = src->n; b->k = src->k; b->N = src->N; b->l = src->l; b->Bg_bit = src->Bg_bit;
   b->unfolding = src->unfolding; b->bytes = src->bytes; b->general = src->general;
   b->order = src->order;   // replicas sum alike (mosfhet_hip_bsk_set_product_order)
   int rc;
   if (src->unfolding > 1) {
     HIP_TRY(hipMalloc((void **)&b->d_su, b->bytes));
-    if ((rc = copy_across(b->d_su, dst_ctx->device, src->d_su, src->ctx->device, b->bytes))) return rc;
+    if ((rc = copy_across(b->d_su, dst_ctx->device, src->d_su, src->device, b->bytes))) return rc;
     if (unfold2_capable(b) && unfold2_dft_enabled() && (rc = unfold2_ready(dst_ctx, b))) return rc;   // the replica transforms its own samples, now
   } else {
     HIP_TRY(hipMalloc((void **)&b->d_bk, b->bytes));
-    if ((rc = copy_across(b->d_bk, dst_ctx->device, src->d_bk, src->ctx->device, b->bytes))) return rc;
+    if ((rc = copy_across(b->d_bk, dst_ctx->device, src->d_bk, src->device, b->bytes))) return rc;
   }
   *out = b_owner.release();
   return MOSFHET_HIP_OK;
@@ -1264,15 +1264,15 @@ extern "C" int mosfhet_hip_bsk_clone(mosfhet_hip_ctx_t dst_ctx, mosfhet_hip_bsk_
 
 extern "C" int mosfhet_hip_ksk_clone(mosfhet_hip_ctx_t dst_ctx, mosfhet_hip_ksk_t *out, mosfhet_hip_ksk_t src) {
   if (!dst_ctx || !out || !src) return fail(MOSFHET_HIP_EINVAL, "ksk_clone: bad argument");
-  HIP_TRY(hipSetDevice(src->ctx->device));
+  HIP_TRY(hipSetDevice(src->device));
   HIP_TRY(hipDeviceSynchronize());
   HIP_TRY(hipSetDevice(dst_ctx->device));
   std::unique_ptr<mosfhet_hip_ksk> k_owner(new mosfhet_hip_ksk());
   mosfhet_hip_ksk *k = k_owner.get();
-  k->ctx = dst_ctx; k->n_in = src->n_in; k->n_out = src->n_out; k->t = src->t; k->base_bit = src->base_bit; k->row = src->row; k->b_word = src->b_word;
+  k->ctx = dst_ctx; k->device = dst_ctx->device; k->n_in = src->n_in; k->n_out = src->n_out; k->t = src->t; k->base_bit = src->base_bit; k->row = src->row; k->b_word = src->b_word;
   k->compressed = src->compressed; k->seed = src->seed; k->bytes = src->bytes;
   HIP_TRY(hipMalloc((void **)&k->d_ksk, k->bytes + ksw_slack_bytes(k->row)));   // (+ slack: the word-lane key switch reads past the last row, keyswitch_words_kernels.h)
-  const int rc = copy_across(k->d_ksk, dst_ctx->device, src->d_ksk, src->ctx->device, k->bytes);
+  const int rc = copy_across(k->d_ksk, dst_ctx->device, src->d_ksk, src->device, k->bytes);
   if (rc) return rc;
   *out = k_owner.release();
   return MOSFHET_HIP_OK;
@@ -1280,14 +1280,14 @@ extern "C" int mosfhet_hip_ksk_clone(mosfhet_hip_ctx_t dst_ctx, mosfhet_hip_ksk_
 
 extern "C" int mosfhet_hip_gak_clone(mosfhet_hip_ctx_t dst_ctx, mosfhet_hip_gak_t *out, mosfhet_hip_gak_t src) {
   if (!dst_ctx || !out || !src) return fail(MOSFHET_HIP_EINVAL, "gak_clone: bad argument");
-  HIP_TRY(hipSetDevice(src->ctx->device));
+  HIP_TRY(hipSetDevice(src->device));
   HIP_TRY(hipDeviceSynchronize());
   HIP_TRY(hipSetDevice(dst_ctx->device));
   std::unique_ptr<mosfhet_hip_gak> g_owner(new mosfhet_hip_gak());
   mosfhet_hip_gak *g = g_owner.get();
-  g->ctx = dst_ctx; g->N = src->N; g->t = src->t; g->base_bit = src->base_bit; g->entries = src->entries; g->bytes = src->bytes;
+  g->ctx = dst_ctx; g->device = dst_ctx->device; g->N = src->N; g->t = src->t; g->base_bit = src->base_bit; g->entries = src->entries; g->bytes = src->bytes;
   HIP_TRY(hipMalloc((void **)&g->d_ak, g->bytes));
-  const int rc = copy_across(g->d_ak, dst_ctx->device, src->d_ak, src->ctx->device, g->bytes);
+  const int rc = copy_across(g->d_ak, dst_ctx->device, src->d_ak, src->device, g->bytes);
   if (rc) return rc;
   *out = g_owner.release();
   return MOSFHET_HIP_OK;

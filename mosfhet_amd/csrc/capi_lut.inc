@@ -111,7 +111,7 @@ extern "C" int mosfhet_hip_leveled_lut_batch(mosfhet_hip_ctx_t ctx, uint64_t *d_
   p.half0 = plan.nodes;
   p.first = 0; p.inputs = 0; p.mode = 1; p.half = 0; p.sel_index = 0;
   p.steps = size < ilog2(N) ? size : ilog2(N);
-  p.tables = 1; p.out_tables = 1; p.group = 1; p.lut_stride = 0;
+  p.tables = 1; p.out_tables = 1; p.group = 1; p.lut_stride = 0; p.pack_log = 0;
   hipStream_t s = pick(ctx, stream);
   if (N == 1024) { p.tw = ctx->tw1024; return launch_leveled_lut<Fft1024>(plan, p, count, cus, s); }
   p.tw = ctx->tw2048;
@@ -139,13 +139,19 @@ struct LutTablesPlan { int levels, nodes, chunk, pass, group; long long table_by
 
 // The one place that decides the shape of a several-table call: for the launcher and for mosfhet_hip_leveled_lut_tables_plan.  All tables in one pass when one input
 // fits beside them (a pass re-reads every selector, a chunk does not); else as many tables per pass as hold one input each, and then the largest chunk.
-static int lut_tables_plan(const char *who, int N, int l, int size, int tables, int count, int cus, LutTablesPlan *r) {
-  if (tables < 1 || tables > MOSFHET_HIP_LUT_MAX_TABLES) return fail(MOSFHET_HIP_EINVAL, "%s: tables = %d (1 .. %d)", who, tables, MOSFHET_HIP_LUT_MAX_TABLES);
-  LutPlan one;
+// The arithmetic of a several-table shape at a given number of tree levels (shared with the packed call, whose levels are not those of `size` alone).
+// nodes, table_bytes, input_bytes and the refusal are lut_plan's formulas at `levels` and MUST stay equal to them: lut_tables_plan runs lut_plan first (its
+// checks and its refusal, which therefore never fires here on that path) and then this with lut_plan's levels; test_tables_plan_sweep and test_packed_plan_sweep
+// (pack_log = 0 against leveled_lut_tables_plan, tables = 1 against leveled_lut_plan) hold the two together.  The refusal here is the packed call's.
+static int lut_tables_shape(const char *who, int N, int l, int levels, int tables, int count, LutTablesPlan *r) {
   const long long bound = g_lut_workspace.load(std::memory_order_relaxed);
-  int rc = lut_plan(who, N, l, size, count, cus, &one);   // the argument checks, and the refusal when one table with one input does not fit
-  if (rc) return rc;
-  r->levels = one.levels; r->nodes = one.nodes; r->table_bytes = one.table_bytes; r->input_bytes = one.input_bytes;
+  r->levels = levels;
+  r->nodes = levels ? 1 << (levels - 1) : 0;
+  r->table_bytes = (long long)r->nodes * 2 * l * (N / 2) * (long long)sizeof(d2);
+  r->input_bytes = (long long)r->nodes * 2 * N * (long long)sizeof(uint64_t);
+  if (levels && r->table_bytes + r->input_bytes > bound)
+    return fail(MOSFHET_HIP_EINVAL, "%s: the workspace bound of %lld bytes does not hold the prepared table (%lld) and one input's intermediates (%lld)", who, bound,
+                r->table_bytes, r->input_bytes);
   r->chunk = count < LUT_MAX_CHUNK ? count : LUT_MAX_CHUNK;
   r->pass = tables;
   if (r->levels) {
@@ -161,6 +167,14 @@ static int lut_tables_plan(const char *who, int N, int l, int size, int tables, 
   if (r->group > fits) r->group = fits;
   if (r->group > r->pass) r->group = r->pass;
   return MOSFHET_HIP_OK;
+}
+
+static int lut_tables_plan(const char *who, int N, int l, int size, int tables, int count, int cus, LutTablesPlan *r) {
+  if (tables < 1 || tables > MOSFHET_HIP_LUT_MAX_TABLES) return fail(MOSFHET_HIP_EINVAL, "%s: tables = %d (1 .. %d)", who, tables, MOSFHET_HIP_LUT_MAX_TABLES);
+  LutPlan one;
+  int rc = lut_plan(who, N, l, size, count, cus, &one);   // the argument checks, and the refusal when one table with one input does not fit
+  if (rc) return rc;
+  return lut_tables_shape(who, N, l, one.levels, tables, count, r);
 }
 
 extern "C" int mosfhet_hip_leveled_lut_tables_plan(int N, int l, int size, int tables, int count, int cus, long long *plan) {
@@ -182,7 +196,7 @@ static int launch_leveled_lut_tables(const LutTablesPlan &plan, LutParams p, uin
     p.tables = tables - tb0 < plan.pass ? tables - tb0 : plan.pass;
     p.group = plan.group < p.tables ? plan.group : p.tables;
     p.lut = luts + (size_t)tb0 * p.lut_stride;
-    p.out = out + (size_t)tb0 * (size_t)(F::N + 1);
+    p.out = out + ((size_t)tb0 << p.pack_log) * (size_t)(F::N + 1);
     p.dtab = reinterpret_cast<d2 *>(ws);
     p.work = ws ? ws + (size_t)p.tables * (size_t)(plan.table_bytes / (long long)sizeof(uint64_t)) : nullptr;
     const int nodes = p.tables * plan.nodes;
@@ -242,8 +256,79 @@ extern "C" int mosfhet_hip_leveled_lut_tables_batch(mosfhet_hip_ctx_t ctx, uint6
   p.steps = size < log_N ? size : log_N;
   p.tables = tables; p.out_tables = tables; p.group = plan.group;
   p.lut_stride = (size_t)(size > log_N ? 1 << (size - log_N) : 1) * 2 * (size_t)N;
+  p.pack_log = 0;
   hipStream_t s = pick(ctx, stream);
   if (N == 1024) { p.tw = ctx->tw1024; return launch_leveled_lut_tables<Fft1024>(plan, p, ws, tables, count, cus, s); }
   p.tw = ctx->tw2048;
   return launch_leveled_lut_tables<Fft2048>(plan, p, ws, tables, count, cus, s);
+}
+
+// ---------------------------------------------------------------- several outputs packed into one table ----------------------------------------------------------------
+// mosfhet_hip_leveled_lut_packed_batch: an entry of a table is m = 2^pack_log adjacent coefficients, the m output bits of that entry (CGGI's other packing;
+// the reference's vertical_packing.c:4 points at it).  A table of 2^size entries is max(1, 2^(size + pack_log) / N) TRLWEs: the tree has
+// max(0, size + pack_log - log2 N) levels over the TOP selectors, the finish rotates by m 2^i with selector i for min(size, log2 N - pack_log) steps and extracts
+// coefficients 0 .. m-1.  The launches are those of the several-table call with this plan; d_out is [count][tables][m][N + 1].
+
+struct LutPackedPlan { LutTablesPlan t; int steps, outputs; };
+
+// The one place that decides the shape of a packed call: for the launcher and for mosfhet_hip_leveled_lut_packed_plan.
+static int lut_packed_plan(const char *who, int N, int l, int size, int tables, int pack_log, int count, int cus, LutPackedPlan *r) {
+  if (tables < 1 || tables > MOSFHET_HIP_LUT_MAX_TABLES) return fail(MOSFHET_HIP_EINVAL, "%s: tables = %d (1 .. %d)", who, tables, MOSFHET_HIP_LUT_MAX_TABLES);
+  if (N != 1024 && N != 2048) return fail(MOSFHET_HIP_EINVAL, "%s: ring degree N = %d not supported here (1024, 2048)", who, N);
+  if (l < 1 || l > 6) return fail(MOSFHET_HIP_EINVAL, "%s: l = %d (1 .. 6)", who, l);
+  const int log_N = ilog2(N);
+  if (pack_log < 0 || pack_log > log_N - 1) return fail(MOSFHET_HIP_EINVAL, "%s: pack_log = %d (0 .. log2 N - 1 = %d)", who, pack_log, log_N - 1);
+  if (size < 1 || size + pack_log > log_N + MOSFHET_HIP_LUT_MAX_LEVELS)
+    return fail(MOSFHET_HIP_EINVAL, "%s: size = %d with pack_log = %d (size >= 1, size + pack_log <= log2 N + %d = %d)", who, size, pack_log, MOSFHET_HIP_LUT_MAX_LEVELS,
+                log_N + MOSFHET_HIP_LUT_MAX_LEVELS);
+  if (count < 1) return fail(MOSFHET_HIP_EINVAL, "%s: count = %d", who, count);
+  if (cus < 1) return fail(MOSFHET_HIP_EINVAL, "%s: cus = %d", who, cus);
+  const int rot = log_N - pack_log;
+  r->steps = size < rot ? size : rot;
+  r->outputs = tables << pack_log;
+  return lut_tables_shape(who, N, l, size > rot ? size - rot : 0, tables, count, &r->t);
+}
+
+extern "C" int mosfhet_hip_leveled_lut_packed_plan(int N, int l, int size, int tables, int pack_log, int count, int cus, long long *plan) {
+  if (!plan) return fail(MOSFHET_HIP_EINVAL, "leveled_lut_packed_plan: null plan");
+  LutPackedPlan r;
+  const int rc = lut_packed_plan("leveled_lut_packed_plan", N, l, size, tables, pack_log, count, cus, &r);
+  if (rc) return rc;
+  plan[0] = r.t.levels; plan[1] = r.t.nodes; plan[2] = r.t.chunk; plan[3] = r.t.pass; plan[4] = r.t.bytes; plan[5] = r.t.group;
+  plan[6] = r.steps; plan[7] = r.outputs;
+  return MOSFHET_HIP_OK;
+}
+
+extern "C" int mosfhet_hip_leveled_lut_packed_batch(mosfhet_hip_ctx_t ctx, uint64_t *d_out, const double *d_sel_dft, const uint64_t *d_luts, int size, int N, int l,
+                                                    int Bg_bit, int tables, int pack_log, int count, void *stream) {
+  // (argument checks come before any HIP call)
+  if (!ctx) return fail(MOSFHET_HIP_EINVAL, "leveled_lut_packed: null ctx");
+  if (count < 0) return fail(MOSFHET_HIP_EINVAL, "leveled_lut_packed: count = %d", count);
+  if (l < 1 || Bg_bit < 1 || Bg_bit > 31 || l * Bg_bit >= 64) return fail(MOSFHET_HIP_EINVAL, "leveled_lut_packed: bad gadget l=%d Bg_bit=%d (Bg_bit <= 31, l*Bg_bit < 64)", l, Bg_bit);
+  LutPackedPlan plan;
+  int rc = lut_packed_plan("leveled_lut_packed", N, l, size, tables, pack_log, count ? count : 1, 256, &plan);
+  if (rc) return rc;
+  if (pack_log == 0) return mosfhet_hip_leveled_lut_tables_batch(ctx, d_out, d_sel_dft, d_luts, size, N, l, Bg_bit, tables, count, stream);   // one output per entry: that call
+  if (count == 0) return MOSFHET_HIP_OK;
+  if (!d_out || !d_sel_dft || !d_luts) return fail(MOSFHET_HIP_EINVAL, "leveled_lut_packed: null buffer");
+  HIP_TRY(hipSetDevice(ctx->device));
+  const int cus = device_cus() > 0 ? device_cus() : 256;
+  uint64_t *ws = nullptr;
+  if (plan.t.levels && (rc = pool_get(ctx->device, POOL_LUT, (size_t)(plan.t.bytes / (long long)sizeof(uint64_t)), &ws))) return rc;
+  LutParams p;
+  p.sel = reinterpret_cast<const d2 *>(d_sel_dft);
+  p.lut = d_luts;
+  p.dtab = nullptr; p.work = nullptr;
+  p.out = d_out;
+  p.size = size; p.l = l; p.Bg_bit = Bg_bit;
+  p.half0 = plan.t.nodes;
+  p.first = 0; p.inputs = 0; p.mode = 1; p.half = 0; p.sel_index = 0;
+  p.steps = plan.steps;
+  p.tables = tables; p.out_tables = tables; p.group = plan.t.group;
+  p.lut_stride = ((size_t)1 << plan.t.levels) * 2 * (size_t)N;
+  p.pack_log = pack_log;
+  hipStream_t s = pick(ctx, stream);
+  if (N == 1024) { p.tw = ctx->tw1024; return launch_leveled_lut_tables<Fft1024>(plan.t, p, ws, tables, count, cus, s); }
+  p.tw = ctx->tw2048;
+  return launch_leveled_lut_tables<Fft2048>(plan.t, p, ws, tables, count, cus, s);
 }

@@ -403,6 +403,102 @@ void mosfhet_eval_LUTs_bits(TLWE **out, TLWE **in, int size, TRLWE **LUTs, int t
   mc_hstage_free(h);
 }
 
+/* Several outputs packed into one table (mosfhet_hip_leveled_lut_packed_batch): an entry is m = 2^pack_log adjacent coefficients; LUTs[tb] is an array of
+ * max(1, 2^(size + pack_log) / N) host TRLWEs, left unchanged; out[b][tb * m + t] receives output t of the entry input b selects in table tb. */
+void mosfhet_eval_LUTs_packed_inputs(TLWE **out, TRGSW_DFT **inputs, int size, TRLWE **LUTs, int tables, int pack_log, int count) {
+  const char *who = "mosfhet_eval_LUTs_packed_inputs: every input must be `size` TRGSW_DFT samples made by this library (one ring, one gadget)";
+  need(out && inputs && LUTs && size >= 1 && count >= 1 && tables >= 1 && tables <= MOSFHET_HIP_LUT_MAX_TABLES && pack_log >= 0 && pack_log <= 10 &&
+           size + pack_log <= 11 + MOSFHET_HIP_LUT_MAX_LEVELS,
+       "mosfhet_eval_LUTs_packed_inputs: bad argument");
+  int l = 0, Bg_bit = 0, N = 0, gathered = 0;
+  double **blk = (double **)mc_xmalloc(sizeof(double *) * (size_t)count);
+  int *owned = (int *)mc_xmalloc(sizeof(int) * (size_t)count);
+  for (int b = 0; b < count; b++) {
+    int lb, Bb, Nb;
+    blk[b] = key_block(inputs[b], size, &lb, &Bb, &Nb, &owned[b], who);
+    if (b == 0) { l = lb; Bg_bit = Bb; N = Nb; }
+    need(lb == l && Bb == Bg_bit && Nb == N, who);
+  }
+  need(N == 1024 || N == 2048, "mosfhet_eval_LUTs_packed_inputs: ring degree must be 1024 or 2048");
+  const size_t in_doubles = trgsw_dft_doubles(l, N) * (size_t)size;
+  double *sel = blk[0];
+  for (int b = 1; b < count; b++)
+    if (blk[b] != blk[0] + (size_t)b * in_doubles) gathered = 1;
+  if (gathered) {
+    sel = (double *)mc_dev_alloc(sizeof(double) * in_doubles * (size_t)count);
+    for (int b = 0; b < count; b++) mc_dev_copy(sel + (size_t)b * in_doubles, blk[b], sizeof(double) * in_doubles, HIP_D2D);
+  }
+  int log_N = 0;
+  while ((1 << log_N) < N) log_N++;
+  need(pack_log <= log_N - 1, "mosfhet_eval_LUTs_packed_inputs: pack_log must be at most log2 N - 1");
+  need(size + pack_log <= log_N + MOSFHET_HIP_LUT_MAX_LEVELS, "mosfhet_eval_LUTs_packed_inputs: size + pack_log must be at most log2 N + MOSFHET_HIP_LUT_MAX_LEVELS");
+  const int outs = tables << pack_log;
+  const size_t n_luts = size + pack_log > log_N ? (size_t)1 << (size + pack_log - log_N) : 1, row = (size_t)2 * N;
+  const size_t lut_w = (size_t)tables * n_luts * row, out_w = (size_t)count * (size_t)outs * ((size_t)N + 1);
+  Torus *h = (Torus *)mc_hstage_alloc(sizeof(Torus) * (lut_w > out_w ? lut_w : out_w)), *d = (Torus *)mc_stage_alloc(sizeof(Torus) * (lut_w + out_w));
+  for (int tb = 0; tb < tables; tb++)
+    for (size_t j = 0; j < n_luts; j++) mc_trlwe_to_flat(h + ((size_t)tb * n_luts + j) * row, LUTs[tb][j]);
+  mc_dev_copy(d, h, sizeof(Torus) * lut_w, HIP_H2D);
+  check_rc(mosfhet_hip_leveled_lut_packed_batch(ectx(), d + lut_w, sel, d, size, N, l, Bg_bit, tables, pack_log, count, NULL), "mosfhet_eval_LUTs_packed_inputs");
+  mc_dev_copy(h, d + lut_w, sizeof(Torus) * out_w, HIP_D2H);
+  for (int b = 0; b < count; b++)
+    for (int o = 0; o < outs; o++) {
+      const Torus *w = h + ((size_t)b * (size_t)outs + (size_t)o) * ((size_t)N + 1);
+      memcpy(out[b][o]->a, w, sizeof(Torus) * (size_t)N);
+      out[b][o]->b = w[N];
+    }
+  mc_hstage_free(h);
+  if (gathered) hipFree(sel);
+  for (int b = 0; b < count; b++)
+    if (owned[b]) hipFree(blk[b]);
+  free(owned);
+  free(blk);
+}
+
+/* mosfhet_eval_LUTs_bits with packed tables (mosfhet_hip_lut_bits_packed_batch): out[b][tb * m + t], switched to the input dimension when ksk_out is given. */
+void mosfhet_eval_LUTs_packed_bits(TLWE **out, TLWE **in, int size, TRLWE **LUTs, int tables, int pack_log, int count, Bootstrap_Key key, TRLWE_KS_Key *kska,
+                                   Generic_KS_Key kskb, TLWE_KS_Key ksk_out) {
+  need(out && in && LUTs && key && kska && kska[0] && kskb && size >= 1 && count >= 1 && tables >= 1 && tables <= MOSFHET_HIP_LUT_MAX_TABLES && pack_log >= 0 && pack_log <= 10 &&
+           size + pack_log <= 11 + MOSFHET_HIP_LUT_MAX_LEVELS,
+       "mosfhet_eval_LUTs_packed_bits: bad argument");
+  const int n = key->n, N = key->N;
+  need(N == 1024 || N == 2048, "mosfhet_eval_LUTs_packed_bits: ring degree must be 1024 or 2048");
+  int log_N = 0;
+  while ((1 << log_N) < N) log_N++;
+  need(pack_log <= log_N - 1, "mosfhet_eval_LUTs_packed_bits: pack_log must be at most log2 N - 1");
+  need(size + pack_log <= log_N + MOSFHET_HIP_LUT_MAX_LEVELS, "mosfhet_eval_LUTs_packed_bits: size + pack_log must be at most log2 N + MOSFHET_HIP_LUT_MAX_LEVELS");
+  const int outs = tables << pack_log;
+  const int n_res = ksk_out ? out[0][0]->n : N;
+  const size_t n_luts = size + pack_log > log_N ? (size_t)1 << (size + pack_log - log_N) : 1, row = (size_t)2 * N;
+  const size_t lut_w = (size_t)tables * n_luts * row, in_w = (size_t)count * (size_t)size * ((size_t)n + 1), out_w = (size_t)count * (size_t)outs * ((size_t)n_res + 1);
+  const size_t up_w = lut_w + in_w;
+  Torus *h = (Torus *)mc_hstage_alloc(sizeof(Torus) * (up_w > out_w ? up_w : out_w)), *d = (Torus *)mc_stage_alloc(sizeof(Torus) * (up_w + out_w));
+  for (int tb = 0; tb < tables; tb++)
+    for (size_t j = 0; j < n_luts; j++) mc_trlwe_to_flat(h + ((size_t)tb * n_luts + j) * row, LUTs[tb][j]);
+  for (int b = 0; b < count; b++)
+    for (int i = 0; i < size; i++) {
+      Torus *w = h + lut_w + ((size_t)b * (size_t)size + (size_t)i) * ((size_t)n + 1);
+      need(in[b][i]->n == n, "mosfhet_eval_LUTs_packed_bits: an input bit is not an LWE sample of the bootstrap key's dimension");
+      memcpy(w, in[b][i]->a, sizeof(Torus) * (size_t)n);
+      w[n] = in[b][i]->b;
+    }
+  mc_dev_copy(d, h, sizeof(Torus) * up_w, HIP_H2D);
+  check_rc(mosfhet_hip_lut_bits_packed_batch(ectx(), (mosfhet_hip_bsk_t)mc_key_here(key->device, MC_KEY_BSK), (mosfhet_hip_gak_t)mc_key_here(kska[0]->device, MC_KEY_GAK),
+                                             (mosfhet_hip_ksk_t)mc_key_here(kskb->device, MC_KEY_KSK),
+                                             ksk_out ? (mosfhet_hip_ksk_t)mc_key_here(ksk_out->device, MC_KEY_KSK) : NULL, d + up_w, d, d + lut_w, size, tables, pack_log, count,
+                                             NULL),
+           "mosfhet_eval_LUTs_packed_bits");
+  mc_dev_copy(h, d + up_w, sizeof(Torus) * out_w, HIP_D2H);
+  for (int b = 0; b < count; b++)
+    for (int o = 0; o < outs; o++) {
+      const Torus *w = h + ((size_t)b * (size_t)outs + (size_t)o) * ((size_t)n_res + 1);
+      need(out[b][o]->n == n_res, "mosfhet_eval_LUTs_packed_bits: an output sample has the wrong dimension (n with ksk_out, N without)");
+      memcpy(out[b][o]->a, w, sizeof(Torus) * (size_t)n_res);
+      out[b][o]->b = w[n_res];
+    }
+  mc_hstage_free(h);
+}
+
 /* src/trlwe.c:775-781: out = KeySwitch_{ks_key}(in(X^gen)); ks_key switches from key(X^gen) back to key (any entry of a key set) */
 void trlwe_eval_automorphism(TRLWE out, TRLWE in, uint64_t gen, TRLWE_KS_Key ks_key) {
   const int N = in->b->N;

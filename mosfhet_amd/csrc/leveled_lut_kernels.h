@@ -20,6 +20,11 @@
 //   lut_tables_finish_kernel   one workgroup per (input, group of G tables): the G accumulators in LDS, the rotate steps outermost, so that a selector is
 //                              fetched from memory once per group and re-read from the caches for the other tables of the group; SampleExtract_0 per table
 // The one-table call is the case tables = 1 of the first three kernels and keeps lut_cmux_kernel's mode 1 as its finish.
+//
+// Several outputs packed into one table (mosfhet_hip_leveled_lut_packed_batch): an entry occupies m = 2^pack_log adjacent coefficients, so a table of 2^size entries
+// is 2^(size + pack_log) / N TRLWEs.  The tree kernels do not know: they take their node count and table stride from the launcher.  The finish -- always
+// lut_tables_finish_kernel, also at one table -- rotates by m 2^i in step i, for log2 N - pack_log steps at most, and extracts the m coefficients 0 .. m-1 of the
+// rotated accumulator; both are run-time arguments (LutParams::pack_log, 0 for every other call, where they reduce to the words above).
 #pragma once
 #include "bootstrap_kernels.h"
 
@@ -42,6 +47,8 @@ struct LutParams {
   int out_tables;                    // tables of the whole call: out is [count][out_tables][N + 1]
   int group;                         // lut_tables_finish_kernel: tables per workgroup (the last group of a pass may hold fewer)
   size_t lut_stride;                 // words from one table to the next: n_luts * 2 * N
+  // several outputs packed into one table (0 everywhere but in mosfhet_hip_leveled_lut_packed_batch)
+  int pack_log;                      // lut_tables_finish_kernel: an entry is m = 2^pack_log adjacent coefficients; step i rotates by m 2^i, m extractions; out is [count][out_tables][m][N + 1]
 };
 
 // 2^(63 - l Bg) + sum_i 2^(63 - i Bg): the rounding offset of polynomial_decompose_i for all l digits at once (pbs_kernel's `off`)
@@ -295,7 +302,7 @@ __global__ __launch_bounds__(2 * F::THREADS, 2) void lut_tables_finish_kernel(Lu
   }
   workgroup_sync();
   for (int i = 0; i < p.steps; i++) {
-    const int abar = 2 * N - (1 << i);
+    const int abar = 2 * N - (1 << (i + p.pack_log));   // (the launcher keeps i + pack_log < log2 N)
     const d2 *__restrict__ sel = p.sel + (((size_t)p.first + b) * p.size + (size_t)i) * sel_sz;
 #pragma unroll 1
     for (int k = 0; k < nt; k++) {
@@ -311,12 +318,20 @@ __global__ __launch_bounds__(2 * F::THREADS, 2) void lut_tables_finish_kernel(Lu
       workgroup_sync();
     }
   }
-  // src/trlwe.c:540-552 at idx = 0, per table: out is [count][out_tables][N + 1]
+  // src/trlwe.c:540-552 at idx = e for the m = 2^pack_log outputs e of the selected entry, per table: a[j] = acc_a[e - j] for j <= e, else -acc_a[N + e - j];
+  // b = acc_b[e].  out is [count][out_tables][m][N + 1].  Consecutive threads read consecutive LDS words downwards (no bank conflict) and write consecutive
+  // global words.  (e - j) & (N - 1) is e - j for j <= e and N + e - j behind it; at m = 1 this is the extraction at idx 0.
+  const int m_out = 1 << p.pack_log;
   for (int k = 0; k < nt; k++) {
     const uint64_t *acc = accs + (size_t)k * 2 * N;
-    uint64_t *dst = p.out + (((size_t)p.first + b) * p.out_tables + (size_t)(tb0 + k)) * (size_t)(N + 1);
-    for (int j = tid; j < N; j += WG) dst[j] = (j == 0) ? acc[0] : (0 - acc[N - j]);
-    if (tid == 0) dst[N] = acc[N];
+    uint64_t *dst = p.out + ((((size_t)p.first + b) * p.out_tables + (size_t)(tb0 + k)) << p.pack_log) * (size_t)(N + 1);
+    for (int e = 0; e < m_out; e++, dst += N + 1) {
+      for (int j = tid; j < N; j += WG) {
+        const uint64_t w = acc[(e - j) & (N - 1)];
+        dst[j] = (j <= e) ? w : (0 - w);
+      }
+      if (tid == 0) dst[N] = acc[N + e];
+    }
   }
 }
 

@@ -129,6 +129,25 @@ def lut_bits_plan(N, l, size, tables, count, cus=256):
                 lut=dict(levels=int(plan[4]), nodes=int(plan[5]), chunk=int(plan[6]), tables_per_pass=int(plan[7]), workspace_bytes=int(plan[8]), group=int(plan[9])))
 
 
+def leveled_lut_packed_plan(N, l, size, tables, pack_log, count, cus=256):
+    """What a leveled_lut_packed call will do (no device needed): leveled_lut_tables_plan's dict at the packed levels and nodes, plus steps (rotate steps of the
+    finish) and outputs (per input, tables * 2^pack_log).  include/mosfhet_hip.h: mosfhet_hip_leveled_lut_packed_plan."""
+    plan = (C.c_longlong * 8)()
+    _check(lib().mosfhet_hip_leveled_lut_packed_plan(int(N), int(l), int(size), int(tables), int(pack_log), int(count), int(cus), plan))
+    return dict(levels=int(plan[0]), nodes=int(plan[1]), chunk=int(plan[2]), tables_per_pass=int(plan[3]), workspace_bytes=int(plan[4]), group=int(plan[5]),
+                steps=int(plan[6]), outputs=int(plan[7]))
+
+
+def lut_bits_packed_plan(N, l, size, tables, pack_log, count, cus=256):
+    """What a lut_bits_packed call will do (no device needed): lut_bits_plan's dict with leveled_lut_packed_plan's dict for one chunk as `lut`.
+    include/mosfhet_hip.h: mosfhet_hip_lut_bits_packed_plan."""
+    plan = (C.c_longlong * 12)()
+    _check(lib().mosfhet_hip_lut_bits_packed_plan(int(N), int(l), int(size), int(tables), int(pack_log), int(count), int(cus), plan))
+    return dict(chunk=int(plan[0]), chunks=int(plan[1]), selector_bytes=int(plan[2]), cb_bits=int(plan[3]),
+                lut=dict(levels=int(plan[4]), nodes=int(plan[5]), chunk=int(plan[6]), tables_per_pass=int(plan[7]), workspace_bytes=int(plan[8]), group=int(plan[9]),
+                         steps=int(plan[10]), outputs=int(plan[11])))
+
+
 def set_lut_bits_workspace(nbytes):
     """Bound of lut_bits' selector workspace (0 restores the default of 2 GiB): batches whose selectors need more run in chunks of whole inputs; with a key whose
     product order is set, results do not depend on it."""
@@ -365,6 +384,25 @@ class Engine:
     def lut_bits_plan(self, N, l, size, tables, count):
         """lut_bits_plan() at this device's CU count."""
         return lut_bits_plan(N, l, size, tables, count, self.torch.cuda.get_device_properties(self.device).multi_processor_count)
+
+    def lut_bits_packed(self, bsk, kska, kskb, luts, ct, pack_log, ksk_out=None, out=None):
+        """lut_bits with m = 2^pack_log output bits packed into every table entry (leveled_lut_packed in the middle).  ct: [count][size][n + 1];
+        luts: [tables][max(1, 2^(size + pack_log) / N)][2][N], read only; returns [count][tables * m][n + 1] with ksk_out (the ct of the next call when
+        tables * m == size), else [count][tables * m][N + 1]."""
+        count, size, tables, N = ct.shape[0], ct.shape[1], luts.shape[0], bsk.N
+        assert tuple(ct.shape) == (count, size, bsk.n + 1), tuple(ct.shape)
+        assert tuple(luts.shape) == (tables, max(1, (1 << (size + pack_log)) // N), 2, N), tuple(luts.shape)
+        width = (bsk.n if ksk_out is not None else N) + 1
+        if out is None:
+            out = self.empty(count, tables << pack_log, width)
+        assert tuple(out.shape) == (count, tables << pack_log, width)
+        _check(lib().mosfhet_hip_lut_bits_packed_batch(self.h, bsk.h, kska.h, kskb.h, ksk_out.h if ksk_out is not None else None, _ptr(out), _ptr(luts), _ptr(ct),
+                                                       int(size), int(tables), int(pack_log), int(count), self._stream()))
+        return out
+
+    def lut_bits_packed_plan(self, N, l, size, tables, pack_log, count):
+        """lut_bits_packed_plan() at this device's CU count."""
+        return lut_bits_packed_plan(N, l, size, tables, pack_log, count, self.torch.cuda.get_device_properties(self.device).multi_processor_count)
 
     def public_mux(self, p0, p1, sel, Bg_bit, out=None):
         count, l, two, N = sel.shape
@@ -658,6 +696,26 @@ class Engine:
         _check(lib().mosfhet_hip_leveled_lut_tables_batch(self.h, _ptr(out), _ptr(sel_dft), _ptr(luts), int(size), int(N), int(l), int(Bg_bit), int(tables),
                                                           int(count), self._stream()))
         return out
+
+    def leveled_lut_packed(self, sel_dft, luts, size, l, Bg_bit, pack_log, out=None):
+        """Shared tables whose entries hold m = 2^pack_log output bits in adjacent coefficients, evaluated on a batch of independent inputs: one rotation chain per
+        table, m sample extractions.  sel_dft as for leveled_lut; luts: [tables][max(1, 2^(size + pack_log) / N)][2][N] torus words, output t of entry x at
+        coefficient (x m + t) mod N of TRLWE (x m + t) / N, read only; returns [count][tables][m][N + 1] -- out.view(count * tables * m, N + 1) is the batch
+        tlwe_keyswitch takes.  pack_log = 0 is leveled_lut_tables."""
+        count, tables, N = sel_dft.shape[0], luts.shape[0], luts.shape[-1]
+        m = 1 << pack_log
+        assert tuple(sel_dft.shape) == (count, size, 2 * l, 2, N) and sel_dft.dtype == self.torch.float64, tuple(sel_dft.shape)
+        assert tuple(luts.shape) == (tables, max(1, (1 << (size + pack_log)) // N), 2, N), tuple(luts.shape)
+        if out is None:
+            out = self.empty(count, tables, m, N + 1)
+        assert tuple(out.shape) == (count, tables, m, N + 1)
+        _check(lib().mosfhet_hip_leveled_lut_packed_batch(self.h, _ptr(out), _ptr(sel_dft), _ptr(luts), int(size), int(N), int(l), int(Bg_bit), int(tables),
+                                                          int(pack_log), int(count), self._stream()))
+        return out
+
+    def leveled_lut_packed_plan(self, N, l, size, tables, pack_log, count):
+        """leveled_lut_packed_plan() at this device's CU count."""
+        return leveled_lut_packed_plan(N, l, size, tables, pack_log, count, self.torch.cuda.get_device_properties(self.device).multi_processor_count)
 
     def leveled_lut_tables_plan(self, N, l, size, tables, count):
         """leveled_lut_tables_plan() at this device's CU count."""
