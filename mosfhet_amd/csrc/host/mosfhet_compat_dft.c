@@ -270,189 +270,157 @@ void blind_rotate_ga(TRLWE tv, Torus *a, TRGSW_DFT *s, TRLWE_KS_Key *ak, int siz
   if (owned) hipFree(blk);
 }
 
-/* eval_LUT (applications/leveled_lut/vertical_packing.c:36-52) for `count` independent inputs against one shared table (mosfhet_hip_leveled_lut_batch):
- * inputs[b] is an array of `size` TRGSW_DFT selectors (bit i of input b's index at inputs[b][i]), LUT the array of max(1, 2^size / N) host TRLWEs, left
- * unchanged.  The inputs' device blocks are used where they are when they follow each other in memory, else gathered into one block first. */
-void mosfhet_eval_LUT_inputs(TLWE *out, TRGSW_DFT **inputs, int size, TRLWE *LUT, int count) {
-  const char *who = "mosfhet_eval_LUT_inputs: every input must be `size` TRGSW_DFT samples made by this library (one ring, one gadget)";
-  need(out && inputs && LUT && size >= 1 && count >= 1, "mosfhet_eval_LUT_inputs: bad argument");
-  int l = 0, Bg_bit = 0, N = 0, gathered = 0;
-  double **blk = (double **)mc_xmalloc(sizeof(double *) * (size_t)count);
-  int *owned = (int *)mc_xmalloc(sizeof(int) * (size_t)count);
-  for (int b = 0; b < count; b++) {
-    int lb, Bb, Nb;
-    blk[b] = key_block(inputs[b], size, &lb, &Bb, &Nb, &owned[b], who);
-    if (b == 0) { l = lb; Bg_bit = Bb; N = Nb; }
-    need(lb == l && Bb == Bg_bit && Nb == N, who);
-  }
-  need(N == 1024 || N == 2048, "mosfhet_eval_LUT_inputs: ring degree must be 1024 or 2048");
-  const size_t in_doubles = trgsw_dft_doubles(l, N) * (size_t)size;
-  double *sel = blk[0];
-  for (int b = 1; b < count; b++)
-    if (blk[b] != blk[0] + (size_t)b * in_doubles) gathered = 1;
-  if (gathered) {
-    sel = (double *)mc_dev_alloc(sizeof(double) * in_doubles * (size_t)count);
-    for (int b = 0; b < count; b++) mc_dev_copy(sel + (size_t)b * in_doubles, blk[b], sizeof(double) * in_doubles, HIP_D2D);
-  }
-  int log_N = 0;
-  while ((1 << log_N) < N) log_N++;
-  const size_t n_luts = size > log_N ? (size_t)1 << (size - log_N) : 1, row = (size_t)2 * N;
-  const size_t lut_w = n_luts * row, out_w = (size_t)count * ((size_t)N + 1);
-  Torus *h = (Torus *)mc_hstage_alloc(sizeof(Torus) * (lut_w > out_w ? lut_w : out_w)), *d = (Torus *)mc_stage_alloc(sizeof(Torus) * (lut_w + out_w));
-  for (size_t j = 0; j < n_luts; j++) mc_trlwe_to_flat(h + j * row, LUT[j]);
-  mc_dev_copy(d, h, sizeof(Torus) * lut_w, HIP_H2D);
-  check_rc(mosfhet_hip_leveled_lut_batch(ectx(), d + lut_w, sel, d, size, N, l, Bg_bit, count, NULL), "mosfhet_eval_LUT_inputs");
-  mc_dev_copy(h, d + lut_w, sizeof(Torus) * out_w, HIP_D2H);
-  for (int b = 0; b < count; b++) {
-    memcpy(out[b]->a, h + (size_t)b * ((size_t)N + 1), sizeof(Torus) * (size_t)N);
-    out[b]->b = h[(size_t)b * ((size_t)N + 1) + N];
-  }
-  mc_hstage_free(h);
-  if (gathered) hipFree(sel);
-  for (int b = 0; b < count; b++)
-    if (owned[b]) hipFree(blk[b]);
-  free(owned);
-  free(blk);
+/* ------------------------------------------------------------------ leveled LUT evaluation on host structs: the shared pieces of the five calls below */
+static void need_of(int cond, const char *name, const char *what) {
+  if (cond) return;
+  fprintf(stderr, "mosfhet_amd: %s: %s\n", name, what);
+  abort();
 }
 
-/* The same for `tables` shared tables over the same inputs (mosfhet_hip_leveled_lut_tables_batch): LUTs[tb] is table tb, an array of max(1, 2^size / N) host
- * TRLWEs, left unchanged; out[b][tb] receives what eval_LUT gives for input b on table tb.  One call, the selectors fetched once for all tables. */
-void mosfhet_eval_LUTs_inputs(TLWE **out, TRGSW_DFT **inputs, int size, TRLWE **LUTs, int tables, int count) {
-  const char *who = "mosfhet_eval_LUTs_inputs: every input must be `size` TRGSW_DFT samples made by this library (one ring, one gadget)";
-  need(out && inputs && LUTs && size >= 1 && count >= 1 && tables >= 1 && tables <= MOSFHET_HIP_LUT_MAX_TABLES, "mosfhet_eval_LUTs_inputs: bad argument");
-  int l = 0, Bg_bit = 0, N = 0, gathered = 0;
+/* The selectors of `count` inputs as one device block [count][size] of TRGSW_DFT: the inputs' own blocks where they are when they follow each other in memory, else
+ * gathered into one block first (*gathered is set and the caller frees it). */
+static double *lut_selectors(TRGSW_DFT **inputs, int size, int count, int *l, int *Bg_bit, int *N, int *gathered, const char *name) {
+  char who[192];
+  snprintf(who, sizeof who, "%s: every input must be `size` TRGSW_DFT samples made by this library (one ring, one gadget)", name);
   double **blk = (double **)mc_xmalloc(sizeof(double *) * (size_t)count);
   int *owned = (int *)mc_xmalloc(sizeof(int) * (size_t)count);
+  *gathered = 0;
   for (int b = 0; b < count; b++) {
     int lb, Bb, Nb;
     blk[b] = key_block(inputs[b], size, &lb, &Bb, &Nb, &owned[b], who);
-    if (b == 0) { l = lb; Bg_bit = Bb; N = Nb; }
-    need(lb == l && Bb == Bg_bit && Nb == N, who);
+    if (b == 0) { *l = lb; *Bg_bit = Bb; *N = Nb; }
+    need(lb == *l && Bb == *Bg_bit && Nb == *N, who);
+    if (owned[b]) *gathered = 1;   /* a copy key_block made: it moves into the block and is released here */
   }
-  need(N == 1024 || N == 2048, "mosfhet_eval_LUTs_inputs: ring degree must be 1024 or 2048");
-  const size_t in_doubles = trgsw_dft_doubles(l, N) * (size_t)size;
-  double *sel = blk[0];
+  const size_t in_doubles = trgsw_dft_doubles(*l, *N) * (size_t)size;
   for (int b = 1; b < count; b++)
-    if (blk[b] != blk[0] + (size_t)b * in_doubles) gathered = 1;
-  if (gathered) {
+    if (blk[b] != blk[0] + (size_t)b * in_doubles) *gathered = 1;
+  double *sel = blk[0];
+  if (*gathered) {
     sel = (double *)mc_dev_alloc(sizeof(double) * in_doubles * (size_t)count);
-    for (int b = 0; b < count; b++) mc_dev_copy(sel + (size_t)b * in_doubles, blk[b], sizeof(double) * in_doubles, HIP_D2D);
-  }
-  int log_N = 0;
-  while ((1 << log_N) < N) log_N++;
-  const size_t n_luts = size > log_N ? (size_t)1 << (size - log_N) : 1, row = (size_t)2 * N;
-  const size_t lut_w = (size_t)tables * n_luts * row, out_w = (size_t)count * (size_t)tables * ((size_t)N + 1);
-  Torus *h = (Torus *)mc_hstage_alloc(sizeof(Torus) * (lut_w > out_w ? lut_w : out_w)), *d = (Torus *)mc_stage_alloc(sizeof(Torus) * (lut_w + out_w));
-  for (int tb = 0; tb < tables; tb++)
-    for (size_t j = 0; j < n_luts; j++) mc_trlwe_to_flat(h + ((size_t)tb * n_luts + j) * row, LUTs[tb][j]);
-  mc_dev_copy(d, h, sizeof(Torus) * lut_w, HIP_H2D);
-  check_rc(mosfhet_hip_leveled_lut_tables_batch(ectx(), d + lut_w, sel, d, size, N, l, Bg_bit, tables, count, NULL), "mosfhet_eval_LUTs_inputs");
-  mc_dev_copy(h, d + lut_w, sizeof(Torus) * out_w, HIP_D2H);
-  for (int b = 0; b < count; b++)
-    for (int tb = 0; tb < tables; tb++) {
-      const Torus *w = h + ((size_t)b * (size_t)tables + (size_t)tb) * ((size_t)N + 1);
-      memcpy(out[b][tb]->a, w, sizeof(Torus) * (size_t)N);
-      out[b][tb]->b = w[N];
+    for (int b = 0; b < count; b++) {
+      mc_dev_copy(sel + (size_t)b * in_doubles, blk[b], sizeof(double) * in_doubles, HIP_D2D);
+      if (owned[b]) hipFree(blk[b]);
     }
-  mc_hstage_free(h);
-  if (gathered) hipFree(sel);
-  for (int b = 0; b < count; b++)
-    if (owned[b]) hipFree(blk[b]);
+  }
   free(owned);
   free(blk);
+  return sel;
 }
 
-/* The leveled application's loop (applications/leveled_lut/main.c: circuit_bootstrap_3 src/bootstrap.c:346-366, trgsw_to_DFT src/trgsw.c:345-349, eval_LUT
- * vertical_packing.c:36-52, tlwe_keyswitch src/tlwe.c:289-320) for `count` inputs given as LWE-encrypted bits (mosfhet_hip_lut_bits_batch): in[b][i] is bit i of
- * input b, LUTs[tb] table tb (an array of max(1, 2^size / N) host TRLWEs, left unchanged); out[b][tb] receives the output of table tb for input b, switched to the
- * input dimension when ksk_out is given. */
-void mosfhet_eval_LUTs_bits(TLWE **out, TLWE **in, int size, TRLWE **LUTs, int tables, int count, Bootstrap_Key key, TRLWE_KS_Key *kska, Generic_KS_Key kskb,
-                            TLWE_KS_Key ksk_out) {
-  need(out && in && LUTs && key && kska && kska[0] && kskb && size >= 1 && count >= 1 && tables >= 1 && tables <= MOSFHET_HIP_LUT_MAX_TABLES, "mosfhet_eval_LUTs_bits: bad argument");
-  const int n = key->n, N = key->N;
-  need(N == 1024 || N == 2048, "mosfhet_eval_LUTs_bits: ring degree must be 1024 or 2048");
+/* TRLWEs per table: max(1, 2^(size + pack_log) / N), after the checks on the ring and on what it holds */
+static size_t lut_rows_per_table(int N, int size, int pack_log, const char *name) {
+  need_of(N == 1024 || N == 2048, name, "ring degree must be 1024 or 2048");
   int log_N = 0;
   while ((1 << log_N) < N) log_N++;
-  const int n_res = ksk_out ? out[0][0]->n : N;
-  const size_t n_luts = size > log_N ? (size_t)1 << (size - log_N) : 1, row = (size_t)2 * N;
-  const size_t lut_w = (size_t)tables * n_luts * row, in_w = (size_t)count * (size_t)size * ((size_t)n + 1), out_w = (size_t)count * (size_t)tables * ((size_t)n_res + 1);
-  const size_t up_w = lut_w + in_w;
-  Torus *h = (Torus *)mc_hstage_alloc(sizeof(Torus) * (up_w > out_w ? up_w : out_w)), *d = (Torus *)mc_stage_alloc(sizeof(Torus) * (up_w + out_w));
+  need_of(pack_log <= log_N - 1, name, "pack_log must be at most log2 N - 1");
+  need_of(size + pack_log <= log_N + MOSFHET_HIP_LUT_MAX_LEVELS, name, "size + pack_log must be at most log2 N + MOSFHET_HIP_LUT_MAX_LEVELS");
+  return size + pack_log > log_N ? (size_t)1 << (size + pack_log - log_N) : 1;
+}
+
+static void lut_stage_tables(Torus *h, TRLWE **LUTs, int tables, size_t n_luts, int N) {
   for (int tb = 0; tb < tables; tb++)
-    for (size_t j = 0; j < n_luts; j++) mc_trlwe_to_flat(h + ((size_t)tb * n_luts + j) * row, LUTs[tb][j]);
+    for (size_t j = 0; j < n_luts; j++) mc_trlwe_to_flat(h + ((size_t)tb * n_luts + j) * 2 * (size_t)N, LUTs[tb][j]);
+}
+
+static void lut_stage_bits(Torus *h, TLWE **in, int size, int count, int n, const char *name) {
   for (int b = 0; b < count; b++)
     for (int i = 0; i < size; i++) {
-      Torus *w = h + lut_w + ((size_t)b * (size_t)size + (size_t)i) * ((size_t)n + 1);
-      need(in[b][i]->n == n, "mosfhet_eval_LUTs_bits: an input bit is not an LWE sample of the bootstrap key's dimension");
+      Torus *w = h + ((size_t)b * (size_t)size + (size_t)i) * ((size_t)n + 1);
+      need_of(in[b][i]->n == n, name, "an input bit is not an LWE sample of the bootstrap key's dimension");
       memcpy(w, in[b][i]->a, sizeof(Torus) * (size_t)n);
       w[n] = in[b][i]->b;
     }
-  mc_dev_copy(d, h, sizeof(Torus) * up_w, HIP_H2D);
-  check_rc(mosfhet_hip_lut_bits_batch(ectx(), (mosfhet_hip_bsk_t)mc_key_here(key->device, MC_KEY_BSK), (mosfhet_hip_gak_t)mc_key_here(kska[0]->device, MC_KEY_GAK),
-                                      (mosfhet_hip_ksk_t)mc_key_here(kskb->device, MC_KEY_KSK), ksk_out ? (mosfhet_hip_ksk_t)mc_key_here(ksk_out->device, MC_KEY_KSK) : NULL,
-                                      d + up_w, d, d + lut_w, size, tables, count, NULL),
-           "mosfhet_eval_LUTs_bits");
-  mc_dev_copy(h, d + up_w, sizeof(Torus) * out_w, HIP_D2H);
+}
+
+/* out[b][o] <- sample b * outs + o of h, samples of dimension n_res */
+static void lut_unstage_outputs(TLWE **out, const Torus *h, int count, int outs, int n_res, const char *name, const char *what) {
   for (int b = 0; b < count; b++)
-    for (int tb = 0; tb < tables; tb++) {
-      const Torus *w = h + ((size_t)b * (size_t)tables + (size_t)tb) * ((size_t)n_res + 1);
-      need(out[b][tb]->n == n_res, "mosfhet_eval_LUTs_bits: an output sample has the wrong dimension (n with ksk_out, N without)");
-      memcpy(out[b][tb]->a, w, sizeof(Torus) * (size_t)n_res);
-      out[b][tb]->b = w[n_res];
+    for (int o = 0; o < outs; o++) {
+      const Torus *w = h + ((size_t)b * (size_t)outs + (size_t)o) * ((size_t)n_res + 1);
+      need_of(out[b][o]->n == n_res, name, what);
+      memcpy(out[b][o]->a, w, sizeof(Torus) * (size_t)n_res);
+      out[b][o]->b = w[n_res];
     }
+}
+
+/* The three calls on TRGSW_DFT inputs: out[b][tb * m + t], LUTs[tb] an array of max(1, 2^(size + pack_log) / N) host TRLWEs.  `one`: the one-table entry point. */
+static void eval_LUTs_inputs(const char *name, TLWE **out, TRGSW_DFT **inputs, int size, TRLWE **LUTs, int tables, int pack_log, int one, int count) {
+  int l, Bg_bit, N, gathered;
+  double *sel = lut_selectors(inputs, size, count, &l, &Bg_bit, &N, &gathered, name);
+  const int outs = tables << pack_log;
+  const size_t n_luts = lut_rows_per_table(N, size, pack_log, name);
+  const size_t lut_w = (size_t)tables * n_luts * 2 * (size_t)N, out_w = (size_t)count * (size_t)outs * ((size_t)N + 1);
+  Torus *h = (Torus *)mc_hstage_alloc(sizeof(Torus) * (lut_w > out_w ? lut_w : out_w)), *d = (Torus *)mc_stage_alloc(sizeof(Torus) * (lut_w + out_w));
+  lut_stage_tables(h, LUTs, tables, n_luts, N);
+  mc_dev_copy(d, h, sizeof(Torus) * lut_w, HIP_H2D);
+  check_rc(one ? mosfhet_hip_leveled_lut_batch(ectx(), d + lut_w, sel, d, size, N, l, Bg_bit, count, NULL)
+               : mosfhet_hip_leveled_lut_packed_batch(ectx(), d + lut_w, sel, d, size, N, l, Bg_bit, tables, pack_log, count, NULL),
+           name);
+  mc_dev_copy(h, d + lut_w, sizeof(Torus) * out_w, HIP_D2H);
+  lut_unstage_outputs(out, h, count, outs, N, name, "an output sample has the wrong dimension (the ring degree N)");
   mc_hstage_free(h);
+  if (gathered) hipFree(sel);
+}
+
+/* The two calls on LWE-encrypted bits: in[b][i] is bit i of input b; out[b][tb * m + t], switched to the input dimension when ksk_out is given. */
+static void eval_LUTs_bits(const char *name, TLWE **out, TLWE **in, int size, TRLWE **LUTs, int tables, int pack_log, int count, Bootstrap_Key key, TRLWE_KS_Key *kska,
+                           Generic_KS_Key kskb, TLWE_KS_Key ksk_out) {
+  const int n = key->n, N = key->N, outs = tables << pack_log;
+  const size_t n_luts = lut_rows_per_table(N, size, pack_log, name);
+  const int n_res = ksk_out ? out[0][0]->n : N;
+  const size_t lut_w = (size_t)tables * n_luts * 2 * (size_t)N, in_w = (size_t)count * (size_t)size * ((size_t)n + 1), out_w = (size_t)count * (size_t)outs * ((size_t)n_res + 1);
+  const size_t up_w = lut_w + in_w;
+  Torus *h = (Torus *)mc_hstage_alloc(sizeof(Torus) * (up_w > out_w ? up_w : out_w)), *d = (Torus *)mc_stage_alloc(sizeof(Torus) * (up_w + out_w));
+  lut_stage_tables(h, LUTs, tables, n_luts, N);
+  lut_stage_bits(h + lut_w, in, size, count, n, name);
+  mc_dev_copy(d, h, sizeof(Torus) * up_w, HIP_H2D);
+  check_rc(mosfhet_hip_lut_bits_packed_batch(ectx(), (mosfhet_hip_bsk_t)mc_key_here(key->device, MC_KEY_BSK), (mosfhet_hip_gak_t)mc_key_here(kska[0]->device, MC_KEY_GAK),
+                                             (mosfhet_hip_ksk_t)mc_key_here(kskb->device, MC_KEY_KSK),
+                                             ksk_out ? (mosfhet_hip_ksk_t)mc_key_here(ksk_out->device, MC_KEY_KSK) : NULL, d + up_w, d, d + lut_w, size, tables, pack_log, count,
+                                             NULL),
+           name);
+  mc_dev_copy(h, d + up_w, sizeof(Torus) * out_w, HIP_D2H);
+  lut_unstage_outputs(out, h, count, outs, n_res, name, "an output sample has the wrong dimension (n with ksk_out, N without)");
+  mc_hstage_free(h);
+}
+
+/* eval_LUT (applications/leveled_lut/vertical_packing.c:36-52) for `count` independent inputs against one shared table (mosfhet_hip_leveled_lut_batch):
+ * inputs[b] is an array of `size` TRGSW_DFT selectors (bit i of input b's index at inputs[b][i]), LUT the array of max(1, 2^size / N) host TRLWEs, left
+ * unchanged.  (out[b] is row b's only output, LUT the only table.) */
+void mosfhet_eval_LUT_inputs(TLWE *out, TRGSW_DFT **inputs, int size, TRLWE *LUT, int count) {
+  need(out && inputs && LUT && size >= 1 && count >= 1, "mosfhet_eval_LUT_inputs: bad argument");
+  TLWE **rows = (TLWE **)mc_xmalloc(sizeof(TLWE *) * (size_t)count);
+  for (int b = 0; b < count; b++) rows[b] = out + b;
+  eval_LUTs_inputs("mosfhet_eval_LUT_inputs", rows, inputs, size, &LUT, 1, 0, 1, count);
+  free(rows);
+}
+
+/* The same for `tables` shared tables over the same inputs (mosfhet_hip_leveled_lut_tables_batch, here as the packed call at pack_log = 0): LUTs[tb] is table tb,
+ * an array of max(1, 2^size / N) host TRLWEs, left unchanged; out[b][tb] receives what eval_LUT gives for input b on table tb.  One call, the selectors fetched once
+ * for all tables. */
+void mosfhet_eval_LUTs_inputs(TLWE **out, TRGSW_DFT **inputs, int size, TRLWE **LUTs, int tables, int count) {
+  need(out && inputs && LUTs && size >= 1 && count >= 1 && tables >= 1 && tables <= MOSFHET_HIP_LUT_MAX_TABLES, "mosfhet_eval_LUTs_inputs: bad argument");
+  eval_LUTs_inputs("mosfhet_eval_LUTs_inputs", out, inputs, size, LUTs, tables, 0, 0, count);
 }
 
 /* Several outputs packed into one table (mosfhet_hip_leveled_lut_packed_batch): an entry is m = 2^pack_log adjacent coefficients; LUTs[tb] is an array of
  * max(1, 2^(size + pack_log) / N) host TRLWEs, left unchanged; out[b][tb * m + t] receives output t of the entry input b selects in table tb. */
 void mosfhet_eval_LUTs_packed_inputs(TLWE **out, TRGSW_DFT **inputs, int size, TRLWE **LUTs, int tables, int pack_log, int count) {
-  const char *who = "mosfhet_eval_LUTs_packed_inputs: every input must be `size` TRGSW_DFT samples made by this library (one ring, one gadget)";
   need(out && inputs && LUTs && size >= 1 && count >= 1 && tables >= 1 && tables <= MOSFHET_HIP_LUT_MAX_TABLES && pack_log >= 0 && pack_log <= 10 &&
            size + pack_log <= 11 + MOSFHET_HIP_LUT_MAX_LEVELS,
        "mosfhet_eval_LUTs_packed_inputs: bad argument");
-  int l = 0, Bg_bit = 0, N = 0, gathered = 0;
-  double **blk = (double **)mc_xmalloc(sizeof(double *) * (size_t)count);
-  int *owned = (int *)mc_xmalloc(sizeof(int) * (size_t)count);
-  for (int b = 0; b < count; b++) {
-    int lb, Bb, Nb;
-    blk[b] = key_block(inputs[b], size, &lb, &Bb, &Nb, &owned[b], who);
-    if (b == 0) { l = lb; Bg_bit = Bb; N = Nb; }
-    need(lb == l && Bb == Bg_bit && Nb == N, who);
-  }
-  need(N == 1024 || N == 2048, "mosfhet_eval_LUTs_packed_inputs: ring degree must be 1024 or 2048");
-  const size_t in_doubles = trgsw_dft_doubles(l, N) * (size_t)size;
-  double *sel = blk[0];
-  for (int b = 1; b < count; b++)
-    if (blk[b] != blk[0] + (size_t)b * in_doubles) gathered = 1;
-  if (gathered) {
-    sel = (double *)mc_dev_alloc(sizeof(double) * in_doubles * (size_t)count);
-    for (int b = 0; b < count; b++) mc_dev_copy(sel + (size_t)b * in_doubles, blk[b], sizeof(double) * in_doubles, HIP_D2D);
-  }
-  int log_N = 0;
-  while ((1 << log_N) < N) log_N++;
-  need(pack_log <= log_N - 1, "mosfhet_eval_LUTs_packed_inputs: pack_log must be at most log2 N - 1");
-  need(size + pack_log <= log_N + MOSFHET_HIP_LUT_MAX_LEVELS, "mosfhet_eval_LUTs_packed_inputs: size + pack_log must be at most log2 N + MOSFHET_HIP_LUT_MAX_LEVELS");
-  const int outs = tables << pack_log;
-  const size_t n_luts = size + pack_log > log_N ? (size_t)1 << (size + pack_log - log_N) : 1, row = (size_t)2 * N;
-  const size_t lut_w = (size_t)tables * n_luts * row, out_w = (size_t)count * (size_t)outs * ((size_t)N + 1);
-  Torus *h = (Torus *)mc_hstage_alloc(sizeof(Torus) * (lut_w > out_w ? lut_w : out_w)), *d = (Torus *)mc_stage_alloc(sizeof(Torus) * (lut_w + out_w));
-  for (int tb = 0; tb < tables; tb++)
-    for (size_t j = 0; j < n_luts; j++) mc_trlwe_to_flat(h + ((size_t)tb * n_luts + j) * row, LUTs[tb][j]);
-  mc_dev_copy(d, h, sizeof(Torus) * lut_w, HIP_H2D);
-  check_rc(mosfhet_hip_leveled_lut_packed_batch(ectx(), d + lut_w, sel, d, size, N, l, Bg_bit, tables, pack_log, count, NULL), "mosfhet_eval_LUTs_packed_inputs");
-  mc_dev_copy(h, d + lut_w, sizeof(Torus) * out_w, HIP_D2H);
-  for (int b = 0; b < count; b++)
-    for (int o = 0; o < outs; o++) {
-      const Torus *w = h + ((size_t)b * (size_t)outs + (size_t)o) * ((size_t)N + 1);
-      memcpy(out[b][o]->a, w, sizeof(Torus) * (size_t)N);
-      out[b][o]->b = w[N];
-    }
-  mc_hstage_free(h);
-  if (gathered) hipFree(sel);
-  for (int b = 0; b < count; b++)
-    if (owned[b]) hipFree(blk[b]);
-  free(owned);
-  free(blk);
+  eval_LUTs_inputs("mosfhet_eval_LUTs_packed_inputs", out, inputs, size, LUTs, tables, pack_log, 0, count);
+}
+
+/* The leveled application's loop (applications/leveled_lut/main.c: circuit_bootstrap_3 src/bootstrap.c:346-366, trgsw_to_DFT src/trgsw.c:345-349, eval_LUT
+ * vertical_packing.c:36-52, tlwe_keyswitch src/tlwe.c:289-320) for `count` inputs given as LWE-encrypted bits (mosfhet_hip_lut_bits_batch, here as the packed call
+ * at pack_log = 0): in[b][i] is bit i of input b, LUTs[tb] table tb (an array of max(1, 2^size / N) host TRLWEs, left unchanged); out[b][tb] receives the output of
+ * table tb for input b, switched to the input dimension when ksk_out is given. */
+void mosfhet_eval_LUTs_bits(TLWE **out, TLWE **in, int size, TRLWE **LUTs, int tables, int count, Bootstrap_Key key, TRLWE_KS_Key *kska, Generic_KS_Key kskb,
+                            TLWE_KS_Key ksk_out) {
+  need(out && in && LUTs && key && kska && kska[0] && kskb && size >= 1 && count >= 1 && tables >= 1 && tables <= MOSFHET_HIP_LUT_MAX_TABLES, "mosfhet_eval_LUTs_bits: bad argument");
+  eval_LUTs_bits("mosfhet_eval_LUTs_bits", out, in, size, LUTs, tables, 0, count, key, kska, kskb, ksk_out);
 }
 
 /* mosfhet_eval_LUTs_bits with packed tables (mosfhet_hip_lut_bits_packed_batch): out[b][tb * m + t], switched to the input dimension when ksk_out is given. */
@@ -461,42 +429,7 @@ void mosfhet_eval_LUTs_packed_bits(TLWE **out, TLWE **in, int size, TRLWE **LUTs
   need(out && in && LUTs && key && kska && kska[0] && kskb && size >= 1 && count >= 1 && tables >= 1 && tables <= MOSFHET_HIP_LUT_MAX_TABLES && pack_log >= 0 && pack_log <= 10 &&
            size + pack_log <= 11 + MOSFHET_HIP_LUT_MAX_LEVELS,
        "mosfhet_eval_LUTs_packed_bits: bad argument");
-  const int n = key->n, N = key->N;
-  need(N == 1024 || N == 2048, "mosfhet_eval_LUTs_packed_bits: ring degree must be 1024 or 2048");
-  int log_N = 0;
-  while ((1 << log_N) < N) log_N++;
-  need(pack_log <= log_N - 1, "mosfhet_eval_LUTs_packed_bits: pack_log must be at most log2 N - 1");
-  need(size + pack_log <= log_N + MOSFHET_HIP_LUT_MAX_LEVELS, "mosfhet_eval_LUTs_packed_bits: size + pack_log must be at most log2 N + MOSFHET_HIP_LUT_MAX_LEVELS");
-  const int outs = tables << pack_log;
-  const int n_res = ksk_out ? out[0][0]->n : N;
-  const size_t n_luts = size + pack_log > log_N ? (size_t)1 << (size + pack_log - log_N) : 1, row = (size_t)2 * N;
-  const size_t lut_w = (size_t)tables * n_luts * row, in_w = (size_t)count * (size_t)size * ((size_t)n + 1), out_w = (size_t)count * (size_t)outs * ((size_t)n_res + 1);
-  const size_t up_w = lut_w + in_w;
-  Torus *h = (Torus *)mc_hstage_alloc(sizeof(Torus) * (up_w > out_w ? up_w : out_w)), *d = (Torus *)mc_stage_alloc(sizeof(Torus) * (up_w + out_w));
-  for (int tb = 0; tb < tables; tb++)
-    for (size_t j = 0; j < n_luts; j++) mc_trlwe_to_flat(h + ((size_t)tb * n_luts + j) * row, LUTs[tb][j]);
-  for (int b = 0; b < count; b++)
-    for (int i = 0; i < size; i++) {
-      Torus *w = h + lut_w + ((size_t)b * (size_t)size + (size_t)i) * ((size_t)n + 1);
-      need(in[b][i]->n == n, "mosfhet_eval_LUTs_packed_bits: an input bit is not an LWE sample of the bootstrap key's dimension");
-      memcpy(w, in[b][i]->a, sizeof(Torus) * (size_t)n);
-      w[n] = in[b][i]->b;
-    }
-  mc_dev_copy(d, h, sizeof(Torus) * up_w, HIP_H2D);
-  check_rc(mosfhet_hip_lut_bits_packed_batch(ectx(), (mosfhet_hip_bsk_t)mc_key_here(key->device, MC_KEY_BSK), (mosfhet_hip_gak_t)mc_key_here(kska[0]->device, MC_KEY_GAK),
-                                             (mosfhet_hip_ksk_t)mc_key_here(kskb->device, MC_KEY_KSK),
-                                             ksk_out ? (mosfhet_hip_ksk_t)mc_key_here(ksk_out->device, MC_KEY_KSK) : NULL, d + up_w, d, d + lut_w, size, tables, pack_log, count,
-                                             NULL),
-           "mosfhet_eval_LUTs_packed_bits");
-  mc_dev_copy(h, d + up_w, sizeof(Torus) * out_w, HIP_D2H);
-  for (int b = 0; b < count; b++)
-    for (int o = 0; o < outs; o++) {
-      const Torus *w = h + ((size_t)b * (size_t)outs + (size_t)o) * ((size_t)n_res + 1);
-      need(out[b][o]->n == n_res, "mosfhet_eval_LUTs_packed_bits: an output sample has the wrong dimension (n with ksk_out, N without)");
-      memcpy(out[b][o]->a, w, sizeof(Torus) * (size_t)n_res);
-      out[b][o]->b = w[n_res];
-    }
-  mc_hstage_free(h);
+  eval_LUTs_bits("mosfhet_eval_LUTs_packed_bits", out, in, size, LUTs, tables, pack_log, count, key, kska, kskb, ksk_out);
 }
 
 /* src/trlwe.c:775-781: out = KeySwitch_{ks_key}(in(X^gen)); ks_key switches from key(X^gen) back to key (any entry of a key set) */

@@ -477,7 +477,9 @@ def test_lut_bits_two_rounds_decrypt(eng, oracle):
 @pytest.mark.gpu
 def test_eval_LUTs_bits_through_the_host_structs(native_lib, tmp_path):
     """tests/c/lut_bits.c: mosfhet_eval_LUTs_bits on 2 inputs equals the same loop written against include/mosfhet.h (circuit_bootstrap_3, trgsw_to_DFT, the
-    reference's eval_LUT on a copy of each table, tlwe_keyswitch), word for word, with and without the output key; the tables are left as they were."""
+    reference's eval_LUT on a copy of each table, tlwe_keyswitch), word for word, with and without the output key; the tables are left as they were.
+    mosfhet_eval_LUTs_packed_bits gives the same words at pack_log = 0, and at pack_log = 1 on one packed table (two output bits per entry, no tree) the words of
+    the same loop with the rotation masks of the packed entries and the extractions at 0 and 1."""
     exe = str(tmp_path / "lut_bits")
     libdir = os.path.join(ROOT, "mosfhet_amd")
     subprocess.check_call(["gcc", "-O2", "-std=gnu11", "-Wall", "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "c", "lut_bits.c"),
