@@ -619,7 +619,18 @@ int mosfhet_hip_time_programmable_bootstrap(mosfhet_hip_ctx_t ctx, mosfhet_hip_b
  * Every generate call draws its noise under a ChaCha20 nonce no other call under this secret gets (a call counter and the generator kind), so the
  * `seed` arguments need NOT be unique: two keys made with the same seed share their masks, never their noise.  Setting the secret restarts that
  * sequence -- the same secret followed by the same generate calls reproduces the same keys (reproducible test runs; the host layer does this under
- * mosfhet_seed).  Never install one secret twice for keys that go to different parties. */
+ * mosfhet_seed).  Never install one secret twice for keys that go to different parties.
+ * The contract (known answers: tests/test_keygen_known_answers.py):
+ *   - MASKS are a file format and STABLE: word idx of row `row` under `seed` (mask polynomial m of a k > 1 row: stream m, else 0) is
+ *       z = seed + 0x9E3779B97F4A7C15 * (row * 0x100000001B3 + idx * 4 + stream + 1);  z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9;
+ *       z = (z ^ z >> 27) * 0x94D049BB133111EB;  word = z ^ z >> 31          (all mod 2^64)
+ *     Stored seed-compressed keys regenerate their masks with it, so it does not change between releases.
+ *   - NOISE is reproducible under an installed secret WITHIN a release, not across releases.  Today: the ChaCha20 block function of RFC 8439 with a
+ *     64-bit block counter (state words 12 - 13) and a 64-bit nonce (words 14 - 15), key = the 32 bytes as eight little-endian words,
+ *     counter = (row << 16) | coefficient, nonce = (call index << 8) | kind -- the call index counts generate calls from 1 after the secret was installed;
+ *     kind 1: table keys (packing, private, LUT packing), 2: bootstrap keys, 3: unfolded bootstrap keys, 4: FFT key-switch key sets, 5: LWE tables.
+ *     Output words 0 - 3 are two 64-bit uniforms (low word first), u = ((w >> 11) + 0.5) 2^-53, the term is cos(2 pi u1) sqrt(-2 ln u2) sigma 2^64
+ *     truncated towards zero (evaluated in double: within 2^-48 sigma of the exact value). */
 int mosfhet_hip_set_keygen_secret(const void *key32);
 
 /* ---- DFT-level entry points behind the reference's legacy signatures (mosfhet.h:179-182,263-264,342-344,454,296 of the reference; csrc/capi_dft.inc).

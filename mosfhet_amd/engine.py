@@ -303,6 +303,20 @@ class Engine:
                                                     msgs.shape[0], t, base_bit, C.c_double(sigma), C.c_uint64(seed)))
         return AutomorphismKeys(self, h, s_out.size, t, base_bit)
 
+    def export_trlwe_ks_keys(self, tks):
+        """The engine's image of an FFT key-switch key set (mosfhet_hip_trlwe_ksk_export): float64 [entries][t][2][N], DFT domain, the engine's slot order
+        (slot_order_to_oracle brings a polynomial into the oracle's)."""
+        info = (C.c_int * 4)()
+        _check(lib().mosfhet_hip_trlwe_ksk_info(tks.h, info))
+        entries, N, t, _ = info
+        out = np.empty((entries, t, 2, N), dtype=np.float64)
+        lib().mosfhet_hip_trlwe_ksk_bytes.restype = C.c_size_t
+        lib().mosfhet_hip_trlwe_ksk_bytes.argtypes = [C.c_void_p]
+        if lib().mosfhet_hip_trlwe_ksk_bytes(tks.h) != out.nbytes:
+            raise MosfhetHipError("key-switch key set of %d bytes, %d expected" % (lib().mosfhet_hip_trlwe_ksk_bytes(tks.h), out.nbytes))
+        _check(lib().mosfhet_hip_trlwe_ksk_export(tks.h, out.ctypes.data_as(C.c_void_p)))
+        return out
+
     def load_packing1_key(self, rows, base_bit):
         """rows: numpy uint64 [n][t][2^bb-1][2][N] -> device LWE -> TRLWE packing key."""
         rows = np.ascontiguousarray(rows, dtype=np.uint64)
