@@ -334,6 +334,12 @@ int mosfhet_hip_tlwe_ksk_generate(mosfhet_hip_ctx_t ctx, mosfhet_hip_ksk_t *out,
  * of 2l wavefronts per ciphertext, ~1/3 of the latency), larger ones the throughput kernel (one wavefront per ciphertext).  Results are
  * bit-identical.  Default 512 (or env MOSFHET_HIP_TEAM_MAX); 0 disables the latency kernel. */
 int mosfhet_hip_set_team_max_batch(int max_batch);
+/* The throughput kernel at N = 1024 with the 2 x 2^8 gadget (SET_1): workgroups of four ciphertexts whose wavefronts stay within a key row of each other and share the
+ * bootstrap-key lines in the CU's vector L1, instead of one ciphertext per workgroup.  Results are bit-identical.  mode 0 = never, 1 = for batches of at least one
+ * residency round of the device (8 per CU), 4 = at any batch size, also in place of the latency kernel (for tests).  -1 = back to the default: env MOSFHET_HIP_PBS_GROUP, else the built-in choice (capi.hip: PBS_GROUP_DEFAULT; docs/SWITCHES.md). */
+int mosfhet_hip_set_pbs_group(int mode);
+/* ciphertexts per workgroup (1 or 4) of the throughput-kernel launch the calling thread's most recent bootstrap call made; 0 if it made none.  For tests. */
+int mosfhet_hip_last_pbs_group(void);
 /* the same switch-over for N = 2048 and, at half the value, N = 4096 (one workgroup of two transform teams per ciphertext; default 512, MOSFHET_HIP_WIDE_TEAM_MAX; 0 disables) */
 int mosfhet_hip_set_wide_team_max_batch(int max_batch);
 /* N = 2048, l = 2, 4 or 6 (l = 4: the TFHEpp lvl2 set of BASELINE.json configs[2..4]; l = 6: the radix-integer application's): batches of at most `max_batch` bootstraps take TWO CUs each (pbs_split_kernel: one workgroup per

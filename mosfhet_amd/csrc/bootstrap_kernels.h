@@ -50,6 +50,8 @@ struct PbsParams {
   unsigned int *pace = nullptr;      // != nullptr: the teams of the launch re-align every `pace_every` CMUX steps (pace_teams(): a bounded wait on a device-wide
   int pace_every = 0, pace_limit = 4000;   // counter, {arrivals, give-up flag}, zeroed by the launcher) so that they keep walking the bootstrap key TOGETHER when one
                                      // step's rows are a sizeable part of an L2 (N >= 2048); purely a matter of timing -- results do not depend on it
+  int group_count = 0;               // pbs_group_kernel (G ciphertexts per workgroup): ciphertexts of this launch (the last workgroup may be ragged)
+  int phase_every = 0;               // ... and its teams meet at a workgroup barrier every `phase_every` CMUX steps (0: never) -- timing only
 };
 
 // Re-alignment of the teams of one launch (all of them resident: the launcher sends one residency round per launch).  What has to stay together is
@@ -380,143 +382,26 @@ __device__ __forceinline__ void cmux_rows2(const typename Digits<L, BG>::word_t 
 // (BYC = false) take an empty struct there.
 template <bool BYC> struct ParkArg {};
 template <> struct ParkArg<true> { double *park; };
+// G > 1 (one-wavefront rings only, rows = 1): a workgroup of G independent one-wavefront teams, team g on ciphertext blockIdx.x * G + g with its own slice of xch and
+// acc1 (17 KiB per team; G = 4: one team per SIMD, two workgroups per CU -- the residency of G = 1).  The teams share no data; what they share is the PHASE of their
+// walk over the bootstrap key: they meet at one workgroup barrier every p.phase_every steps, so that a 128-byte line of a key row one team has brought into the
+// CU's vector L1 is still there (or on its way) when the others ask for it.  Every team passes every barrier: the step count is launch-uniform, the barrier stands
+// in front of the per-team skip of a step, and the teams of a ragged last workgroup past p.group_count do not leave -- they run on the last ciphertext's input and
+// store nothing.  Same arithmetic per ciphertext in the same order: same bits as G = 1.
+// (the body is one text for both kernels -- pbs_body.inc, included into each: as an inlined function taking the parameters by reference it compiles pbs_kernel to
+// different, if equivalent, code)
 template <class F, int L, int BG, bool BYC = false>
 __global__ __launch_bounds__(F::THREADS, 2) void pbs_kernel(PbsParams p, ParkArg<BYC> parked) {
-  static_assert(!BYC || (F::N == 2048 && L % 2 == 0), "the by-component order exists where pbs_split_kernel does");
-  constexpr int N = F::N, M = F::M, T = F::THREADS, LOG2N2 = F::LOGM + 2;
-  // Every output of the external product is a sum of 2L * N products digit * key coefficient with |digit| <= 2^(BG-1) and |key| <= 2^63
-  // (the key is (double)(int64_t) of torus words): |sum| <= 2^(ceil log2(2L) + log2 N + BG - 1 + 63).  Below 2^83 the rounding needs no
-  // reduction mod 1 in front (add_rounded); that holds for SET_1's 2 x 2^8 gadget at N = 1024 (2^82) and is decided at compile time.
-  constexpr bool kReduce = !(BG > 0 && kCeilLog2<2 * L>::value + (F::LOGM + 1) + BG - 1 + 63 < 83);
-  __shared__ __attribute__((aligned(16))) d2 xch[F::XCH_SLOTS];
-  __shared__ __attribute__((aligned(16))) uint64_t acc1[N];
-  const int t = threadIdx.x;
-  const size_t b = blockIdx.x;
-  const uint64_t *__restrict__ ct = p.in + (p.rows > 1 ? b / (size_t)p.rows : b) * (size_t)(p.n + 1);
-  const int Bg_bit = BG > 0 ? BG : p.Bg_bit;
-
-  F fft;
-  fft_setup(fft, p.tw, t);
-
-  uint64_t al[8], ah[8];
-  if (p.skip_init) {
-    const uint64_t *src = p.out + b * (size_t)(2 * N);
-#pragma unroll
-    for (int m = 0; m < 8; m++) {
-      al[m] = src[m * T + t];
-      ah[m] = src[M + m * T + t];
-      acc1[m * T + t] = src[N + m * T + t];
-      acc1[M + m * T + t] = src[N + M + m * T + t];
-    }
-  } else {
-    // src/bootstrap.c:194-195: acc = tv * X^(2N - bbar), gathered straight from global memory
-    const uint64_t *__restrict__ tv = p.rows > 1 ? p.tv + (b % (size_t)p.rows) * (size_t)(2 * N) : p.tv + b * (size_t)p.tv_stride;
-    const uint32_t bbar = modswitch<LOG2N2>(pbs_pre(ct[p.n], p, LOG2N2) + p.prec_offset);
-    const int rot = (2 * N - (int)bbar) & (2 * N - 1);
-    const int a_lo = rot & (N - 1);
-    const bool flip = (rot & N) != 0;
-#pragma unroll
-    for (int m = 0; m < 8; m++) {
-      al[m] = rot_coeff<N>(tv, m * T + t, a_lo, flip);
-      ah[m] = rot_coeff<N>(tv, M + m * T + t, a_lo, flip);
-      acc1[m * T + t] = rot_coeff<N>(tv + N, m * T + t, a_lo, flip);
-      acc1[M + m * T + t] = rot_coeff<N>(tv + N, M + m * T + t, a_lo, flip);
-    }
-  }
-  F::sync();
-
-  uint64_t off = 1ull << (63 - L * Bg_bit);
-#pragma unroll
-  for (int i = 0; i < L; i++) off += 1ull << (63 - i * Bg_bit);
-  const RoundCtx scale(0x1p-64 / (double)M);
-  const size_t row_sz = (size_t)2 * L * 2 * M;
-
-  for (int i = 0; i < p.n; i++) {
-    if (T > 64 && p.pace && i > 0 && i % p.pace_every == 0) pace_teams(p.pace, (unsigned)(i / p.pace_every), t, p.pace_limit);   // (before the skip: every team counts every step)
-    const int abar = (int)modswitch<LOG2N2>(pbs_pre(ct[i], p, LOG2N2));
-    if (abar == 0) continue;  // src/bootstrap.c:114
-    const d2 *__restrict__ bkrow = p.bk + (size_t)i * row_sz;
-    const int a_lo = abar & (N - 1);
-    const bool flip = (abar & N) != 0;
-    double o_re[2][8], o_im[2][8];
-#pragma unroll
-    for (int c = 0; c < 2; c++)
-#pragma unroll
-      for (int m = 0; m < 8; m++) { o_re[c][m] = 0.0; o_im[c][m] = 0.0; }
-    {
-      constexpr int kUnrollQ = L == 1 ? 2 : 1;
-#pragma unroll kUnrollQ
-      for (int q = 0; q < 2; q++) {
-        typename Digits<L, BG>::word_t w_lo[8], w_hi[8];
-        uint32_t ext[8];
-        cmux_digits<F, L, BG>(w_lo, w_hi, ext, al, ah, q ? acc1 : nullptr, xch, a_lo, flip, off, t);
-        // rows two at a time where the transform keeps its pass twiddles in LDS (tools/ab/pbs_ab.hip -DAB_LTW instantiates that) -- at two wavefronts per SIMD
-        // the pairs gain nothing here (experiments/README.md round 4): production instantiates pbs_kernel on the register-twiddle transforms
-        if constexpr (F::kLtw && F::kForward2 && L % 2 == 0) cmux_rows2<F, L, BG>(w_lo, w_hi, ext, q, o_re, o_im, xch, fft, bkrow, Bg_bit, t);
-        else cmux_rows<F, L, BG>(w_lo, w_hi, ext, q, o_re, o_im, xch, fft, bkrow, Bg_bit, t);
-        if constexpr (BYC) {
-          // (the slot addresses are made inside the step: hoisted out of the loop over the key they would hold 32 registers and spill, like cmux_digits' rotated addresses)
-          int here = 0;
-          asm volatile("" : "+s"(here));
-          d2 *__restrict__ mine = reinterpret_cast<d2 *>(parked.park) + (size_t)blockIdx.x * (16 * T) + here + t;
-          if (q == 0) {   // S_0 is parked; S_1 starts from zero
-#pragma unroll
-            for (int c = 0; c < 2; c++)
-#pragma unroll
-              for (int m = 0; m < 8; m++) {
-                mine[(c * 8 + m) * T] = d2{o_re[c][m], o_im[c][m]};
-                o_re[c][m] = 0.0;
-                o_im[c][m] = 0.0;
-              }
-          } else {        // S_0 + S_1
-#pragma unroll
-            for (int c = 0; c < 2; c++)
-#pragma unroll
-              for (int m = 0; m < 8; m++) {
-                const d2 s0 = mine[(c * 8 + m) * T];
-                o_re[c][m] = s0.x + o_re[c][m];
-                o_im[c][m] = s0.y + o_im[c][m];
-              }
-          }
-        }
-      }
-    }
-    fft.inverse2(o_re[0], o_im[0], o_re[1], o_im[1], xch, t);
-#pragma unroll
-    for (int m = 0; m < 8; m++) {
-      al[m] = add_rounded<kReduce>(al[m], o_re[0][m], scale);
-      ah[m] = add_rounded<kReduce>(ah[m], o_im[0][m], scale);
-    }
-#pragma unroll
-    for (int m = 0; m < 8; m++) {
-      acc1[m * T + t] = add_rounded<kReduce>(acc1[m * T + t], o_re[1][m], scale);
-      acc1[M + m * T + t] = add_rounded<kReduce>(acc1[M + m * T + t], o_im[1][m], scale);
-    }
-    F::sync();
-  }
-
-  if (p.extract) {
-    // src/trlwe.c:540-552 at idx = 0: a[0] = acc_a[0], a[j] = -acc_a[N - j]; b = acc_b[0]
-    uint64_t *st = reinterpret_cast<uint64_t *>(xch);
-#pragma unroll
-    for (int m = 0; m < 8; m++) {
-      st[m * T + t] = al[m];
-      st[M + m * T + t] = ah[m];
-    }
-    F::sync();
-    uint64_t *dst = p.out + b * (size_t)(N + 1);
-    for (int j = t; j < N; j += T) dst[j] = (j == 0) ? st[0] : (0 - st[N - j]);
-    if (t == 0) dst[N] = acc1[0];
-  } else {
-    uint64_t *dst = p.out + b * (size_t)(2 * N);
-#pragma unroll
-    for (int m = 0; m < 8; m++) {
-      dst[m * T + t] = al[m];
-      dst[M + m * T + t] = ah[m];
-      dst[N + m * T + t] = acc1[m * T + t];
-      dst[N + M + m * T + t] = acc1[M + m * T + t];
-    }
-  }
+  constexpr int G = 1;
+#include "pbs_body.inc"
+}
+// G one-wavefront teams per workgroup
+template <class F, int L, int BG, int G>
+__global__ __launch_bounds__(F::THREADS * G, 2) void pbs_group_kernel(PbsParams p) {
+  static_assert(G > 1, "one team per workgroup is pbs_kernel");
+  constexpr bool BYC = G < 1;   // (false, and dependent: the by-component branch of the body is not instantiated)
+  const ParkArg<BYC> parked{};
+#include "pbs_body.inc"
 }
 
 // ------------------------------------------------------------------------------------------------------------

@@ -681,9 +681,56 @@ static void launch_rounds(K kernel, int threads, const P &prm, int count, int st
   }
 }
 
+// ---- pbs_group_kernel: pbs_kernel with four ciphertexts per workgroup (bootstrap_kernels.h: pbs_body, G) ----
+// Four one-wavefront teams per workgroup, one per SIMD, that meet at a workgroup barrier every PBS_PHASE_EVERY steps and so walk the bootstrap key within a row of
+// each other: what one of them brings into the CU's vector L1 the others find there.  Same bits as one team per workgroup.  Instantiated for SET_1's compile-time
+// gadget (N = 1024, 2 x 2^8); everything else -- other gadgets, N >= 2048, TRGSW accumulator rows, the by-component order -- stays on G = 1.
+// MOSFHET_HIP_PBS_GROUP / mosfhet_hip_set_pbs_group: 0 = never; 1 = from one residency round of the chip on (8 wavefronts per CU: below that, single wavefronts
+// spread over more CUs); 4 = at any count (tests reach ragged workgroups with a handful of ciphertexts) -- then also in place of the small-batch team kernel.
+constexpr int PBS_GROUP_DEFAULT = 1;
+static std::atomic<int> g_pbs_group{-1};
+static int pbs_group_setting() {
+  int v = g_pbs_group.load(std::memory_order_relaxed);
+  if (v < 0) {
+    const char *e = getenv("MOSFHET_HIP_PBS_GROUP");
+    v = e ? atoi(e) : PBS_GROUP_DEFAULT;
+    if (v != 0 && v != 1 && v != 4) v = PBS_GROUP_DEFAULT;
+    g_pbs_group.store(v, std::memory_order_relaxed);
+  }
+  return v;
+}
+extern "C" int mosfhet_hip_set_pbs_group(int mode) {
+  if (mode != 0 && mode != 1 && mode != 4 && mode != -1) return fail(MOSFHET_HIP_EINVAL, "set_pbs_group: mode %d (0 never, 1 from one residency round on, 4 always, -1 default)", mode);
+  g_pbs_group.store(mode, std::memory_order_relaxed);
+  return MOSFHET_HIP_OK;
+}
+// CMUX steps between two meetings of a workgroup's teams (swept with tools/ab/pbs_ab.hip -DAB_PHASE: DESIGN.md section 4.1)
+constexpr int PBS_PHASE_EVERY = 16;
+constexpr bool pbs_group_gadgets(int N, int L, int BG) { return N == 1024 && L == 2 && BG == 8; }
+// does a throughput launch of `count` ciphertexts take the grouped kernel?  (rows: TRGSW accumulator rows; bounded: see gadget_dispatch)
+static bool pbs_group_takes(int N, int l, int Bg_bit, bool bounded, int rows, int count) {
+  if (!pbs_group_gadgets(N, l, Bg_bit) || !bounded || rows > 1) return false;
+  const int mode = pbs_group_setting();
+  return mode == 4 || (mode == 1 && count >= resident_teams(64));
+}
+// ciphertexts per workgroup of the calling thread's most recent pbs_kernel launch (0: none yet); for tests
+static thread_local int t_last_pbs_group = 0;
+extern "C" int mosfhet_hip_last_pbs_group(void) { return t_last_pbs_group; }
+
 template <class F, int L, int BG>
 static void launch_pbs(const PbsParams &p_in, int count, hipStream_t s) {
   PbsParams p = p_in;
+  if constexpr (pbs_group_gadgets(F::N, L, BG)) {
+    if (pbs_group_takes(F::N, L, BG, true, p.rows, count)) {   // (this instantiation is reached with a bounded key only)
+      constexpr int G = 4;
+      p.group_count = count;
+      p.phase_every = PBS_PHASE_EVERY;
+      t_last_pbs_group = G;
+      hipLaunchKernelGGL((pbs_group_kernel<F, L, BG, G>), dim3((unsigned)((count + G - 1) / G)), dim3(F::THREADS * G), 0, s, p);
+      return;
+    }
+  }
+  t_last_pbs_group = 1;
   const int chunk = F::THREADS > 64 && p.count < 0 ? round_chunk(F::THREADS) : 0;   // p.count < 0: key larger than the L2s
   const bool pace = F::THREADS > 64 && pace_every() > 0 && chunk > 0 && count >= 64;   // (all teams of a launch of <= chunk are resident)
   p.pace_every = pace ? pace_every() : 0;
@@ -1097,8 +1144,8 @@ static int launch_wide_team_f(int l, int Bg, const PbsParams &p, int count, hipS
   });
 }
 
-// pbs_team_kernel (N = 1024): the reference gadgets; run-time gadgets l = 1 .. 4 (1 x 23 takes 1 x 0)
-constexpr bool team_gadgets(int N, int L, int BG) { return BG == 0 ? L <= 4 : reference_gadget(N, L, BG); }
+// pbs_team_kernel (N = 1024): 2 x 2^8 (SET_1); run-time gadgets l = 1 .. 4 (1 x 23 takes 1 x 0; 4 x 2^9, which no parameter set runs at N = 1024, takes 4 x 0: same bits)
+constexpr bool team_gadgets(int, int L, int BG) { return BG == 0 ? L <= 4 : (L == 2 && BG == 8); }
 
 static int bootstrap_unfolded(const char *who, mosfhet_hip_ctx_t ctx, mosfhet_hip_bsk_t bsk, uint64_t *d_out, const uint64_t *d_tv, int tv_count,
                               const uint64_t *d_in, int count, int pre, int kappa, int theta, int torus_base, int extract, int skip_init, void *stream, int rows);
@@ -1118,6 +1165,7 @@ static int bootstrap_common(const char *who, mosfhet_hip_ctx_t ctx, mosfhet_hip_
     return fail(MOSFHET_HIP_EINVAL, "%s: theta = %d out of range at N = %d (0 .. %d)", who, theta, bsk->N, ilog2(2 * bsk->N) - 1);
   if (count == 0) return MOSFHET_HIP_OK;
   HIP_TRY(hipSetDevice(ctx->device));
+  t_last_pbs_group = 0;   // (mosfhet_hip_last_pbs_group: 0 while this call has launched no pbs_kernel)
   if (bsk->unfolding > 1) return bootstrap_unfolded(who, ctx, bsk, d_out, d_tv, tv_count, d_in, count, pre, kappa, theta, torus_base, extract, skip_init, stream, rows);
   if (bsk->general) {
     if (rows != 1) return fail(MOSFHET_HIP_EINVAL, "%s: TRGSW accumulators need a tuned ring (k = 1, N in 1024 / 2048 / 4096)", who);
@@ -1161,6 +1209,14 @@ static int bootstrap_common(const char *who, mosfhet_hip_ctx_t ctx, mosfhet_hip_
   p.rows = rows;
   const BootstrapPlan plan = bootstrap_plan(bsk->N, bsk->l, count, rows, false, bsk->order, device_cus(), p.count < 0);
   const bool latency = plan.family != MOSFHET_HIP_FAMILY_THROUGHPUT && plan.family != MOSFHET_HIP_FAMILY_THROUGHPUT_BY_COMPONENT;
+  // (the grouped throughput kernel forced at any count: mosfhet_hip_set_pbs_group(4))
+  const bool grouped = pbs_group_setting() == 4 && plan.family != MOSFHET_HIP_FAMILY_THROUGHPUT_BY_COMPONENT &&
+                       pbs_group_takes(bsk->N, bsk->l, bsk->Bg_bit, bsk->owns, rows, count);
+  if (grouped) {
+    int rc_grp = MOSFHET_HIP_OK;
+    RING_DISPATCH(ctx, bsk->N, rc_grp = launch_pbs_f<F>(bsk->l, bsk->Bg_bit, p, count, pick(ctx, stream), bsk->owns));
+    return rc_grp;
+  }
   // small batches: the latency-oriented team kernel (one workgroup of 2l wavefronts per ciphertext), N = 1024
   if (bsk->N == 1024 && rows == 1 && latency && team_gadgets(bsk->N, bsk->l, 0)) {
     hipStream_t s = pick(ctx, stream);

@@ -954,6 +954,16 @@ def set_team_max_batch(max_batch):
     _check(lib().mosfhet_hip_set_team_max_batch(int(max_batch)))
 
 
+def set_pbs_group(mode):
+    """SET_1's throughput bootstrap kernel with four ciphertexts per workgroup: 0 = never, 1 = from one residency round of the device on, 4 = at any batch size (same bits)."""
+    _check(lib().mosfhet_hip_set_pbs_group(int(mode)))
+
+
+def last_pbs_group():
+    """ciphertexts per workgroup of the throughput-kernel launch of this thread's most recent bootstrap call (0: it launched none)"""
+    return int(lib().mosfhet_hip_last_pbs_group())
+
+
 def set_wide_team_max_batch(max_batch):
     """Batches up to this size use the latency-oriented bootstrap kernel at N = 2048 (0 disables it)."""
     _check(lib().mosfhet_hip_set_wide_team_max_batch(int(max_batch)))

@@ -28,6 +28,12 @@ using ABF = Fft4096T<AB_WIDE>;
 #ifndef AB_BG
 #define AB_BG 8
 #endif
+#ifndef AB_G
+#define AB_G 1      // one-wavefront teams per workgroup (pbs_kernel: G)
+#endif
+#ifndef AB_PHASE
+#define AB_PHASE 0  // the teams of a workgroup meet every AB_PHASE steps (0: never)
+#endif
 
 extern "C" int ab_pbs(const double *d_bk, const double *d_tw, const uint64_t *d_in, const uint64_t *d_tv, uint64_t *d_out, int n, int count, int precision, int reps,
                       float *ms_per_launch) {
@@ -46,6 +52,8 @@ extern "C" int ab_pbs(const double *d_bk, const double *d_tw, const uint64_t *d_
   p.prec_offset = (uint64_t)((int64_t)(18446744073709551616.0 * (1. / (4 * (double)(1 << (precision - 1))))));
   p.extract = 1;
   p.skip_init = 0;
+  p.group_count = count;
+  p.phase_every = AB_PHASE;
 #ifdef AB_PACE
   static unsigned int *d_pace = nullptr;
   if (!d_pace && hipMalloc((void **)&d_pace, 288 * 4) != hipSuccess) return -4;   // pace_teams' block: 8 per-XCD counters + flag
@@ -66,7 +74,11 @@ extern "C" int ab_pbs(const double *d_bk, const double *d_tw, const uint64_t *d_
 #ifdef AB_PACE
     (void)hipMemsetAsync(d_pace, 0, 288 * 4, nullptr);
 #endif
+#if AB_G > 1
+    hipLaunchKernelGGL((pbs_group_kernel<ABF, AB_L, AB_BG, AB_G>), dim3((unsigned)((count + AB_G - 1) / AB_G)), dim3(ABF::THREADS * AB_G), 0, nullptr, p);
+#else
     hipLaunchKernelGGL((pbs_kernel<ABF, AB_L, AB_BG>), dim3((unsigned)count), dim3(ABF::THREADS), 0, nullptr, p, ParkArg<false>());
+#endif
   }
   hipEventRecord(e1, nullptr);
   if (hipEventSynchronize(e1) != hipSuccess) return -2;

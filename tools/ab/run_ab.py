@@ -77,9 +77,14 @@ def run(pset, B, rounds):
                     err = np.abs((ph - lut[np.arange(B) % 4]).astype(np.int64).astype(np.float64)).max()
                     exact[name] = "DIFFERS (max phase error 2^%.1f, %d of %d words differ)" % (np.log2(err + 1), int((got != want).sum()), got.size)
     base = min(times["base"]) if "base" in times else None
+    med = lambda t: sorted(t)[len(t) // 2]
     for name in libs:
         t = times[name]
-        print("%-28s min %.3f  med %.3f ms  %s  bit-exact-vs-production=%s" % (name, min(t), sorted(t)[len(t) // 2], ("(%+.1f %% vs base)" % (100 * (min(t) / base - 1))) if base else "", exact[name]))
+        # spread: half the distance between the quartiles of this variant's own rounds, in % of its median
+        q = sorted(t)
+        spread = 50.0 * (q[(3 * len(q)) // 4] - q[len(q) // 4]) / med(t)
+        print("%-28s min %.3f  med %.3f  max %.3f ms  spread +-%.2f %%  %s  bit-exact-vs-production=%s" % (
+            name, min(t), med(t), max(t), spread, ("(min %+.1f %%, med %+.1f %% vs base)" % (100 * (min(t) / base - 1), 100 * (med(t) / med(times["base"]) - 1))) if base else "", exact[name]))
 
 
 def run_ep(B, rounds, grids, pset="set1", names=None):

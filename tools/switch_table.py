@@ -57,7 +57,9 @@ SWITCHES = {
     "MOSFHET_HIP_MARSHAL_THREADS": ("min(cores, 8)", "drop-in API: host threads that pack / unpack sample structs around the batched calls", "-", "`tests/c/compat_suite.c` case `big_batch`"),
     "MOSFHET_HIP_PIPE_CHUNK": ("1024", "drop-in API: ciphertexts per chunk of the two-stream upload / bootstrap / download pipeline of `*_batch`", "-", "`tools/compat_latency.c` (timing)"),
     "MOSFHET_HIP_PIPE_PIECE": ("256", "drop-in API: ciphertexts per download piece of the last chunk (unpacked while the next piece is in flight)", "-", "`tools/pipe_ab.sh` (timing)"),
-    "MOSFHET_COMPAT_TLWE_PIECE": ("auto", "drop-in API: outputs per download piece of the generic TLWE batch path; 0 = one copy, then unpack", "-", "`tests/c/compat_suite.c`"),
+    "MOSFHET_HIP_PBS_GROUP": ("1", "N = 1024, 2 x 2^8 gadget (SET_1), throughput kernel: workgroups of four ciphertexts that walk the bootstrap key together and share its lines in the CU's vector L1 "
+                              "(`pbs_kernel` with G = 4); 0 = never, 1 = from one residency round of the device on (8 per CU), 4 = at any batch size", "`mosfhet_hip_set_pbs_group`",
+                              "`tests/test_pbs_groups.py`"),
 }
 # not library switches: the build's extra compiler flags and bench.py's test hooks (documented where they are read)
 OTHER = {"MOSFHET_HIPCC_EXTRA": "mosfhet_amd/build.py: extra hipcc flags (part of the source hash)", "MOSFHET_BENCH_BACKEND": "bench.py test hook: process-group backend",
