@@ -693,8 +693,12 @@ static int pbs_group_setting() {
   int v = g_pbs_group.load(std::memory_order_relaxed);
   if (v < 0) {
     const char *e = getenv("MOSFHET_HIP_PBS_GROUP");
-    v = e ? atoi(e) : PBS_GROUP_DEFAULT;
-    if (v != 0 && v != 1 && v != 4) v = PBS_GROUP_DEFAULT;
+    v = PBS_GROUP_DEFAULT;
+    if (e) {   // (anything but a plain 0, 1 or 4 is the default: atoi alone would read "x" or "" as 0 = never)
+      char *end = nullptr;
+      const long w = strtol(e, &end, 10);
+      if (end != e && *end == '\0' && (w == 0 || w == 1 || w == 4)) v = (int)w;
+    }
     g_pbs_group.store(v, std::memory_order_relaxed);
   }
   return v;
