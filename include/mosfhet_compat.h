@@ -310,6 +310,16 @@ void mosfhet_eval_LUTs_packed_inputs(TLWE **out /*[count][tables * m]*/, TRGSW_D
 void mosfhet_eval_LUTs_packed_bits(TLWE **out /*[count][tables * m]*/, TLWE **in /*[count][size]*/, int size, TRLWE **LUTs /*[tables][n_luts]*/, int tables, int pack_log,
                                    int count, Bootstrap_Key key, TRLWE_KS_Key *kska, Generic_KS_Key kskb, TLWE_KS_Key ksk_out /* or NULL */);
 
+/* A cleartext-weight layer on `count` independent inputs in one call (new; mosfhet_hip_tlwe_linear_batch): out[b][j] = (0, bias[j]) + sum_i W[j][i] in[b][i], the
+ * loop of tlwe_scale_addto (src/tlwe.c:143-191) over the rows of W [rows_out][rows_in]; W[j][i] is the multiplier tlwe_scale takes, bias [rows_out] torus words or
+ * NULL.  out[b][j] has the inputs' dimension.  Synchronous; aborts on error; primary device. */
+void mosfhet_tlwe_linear_inputs(TLWE **out /*[count][rows_out]*/, TLWE **in /*[count][rows_in]*/, const int64_t *W, const Torus *bias /* or NULL */, int rows_out,
+                                int rows_in, int count);
+/* ... followed by tlwe_keyswitch (ksk: the inputs' dimension kN -> n) and functional_bootstrap with the one test vector tv
+ * (mosfhet_hip_linear_keyswitch_functional_bootstrap_batch): a layer and its activation.  out[b][j] has dimension N. */
+void mosfhet_tlwe_linear_bootstrap_inputs(TLWE **out /*[count][rows_out]*/, TLWE **in /*[count][rows_in]*/, const int64_t *W, const Torus *bias /* or NULL */,
+                                          int rows_out, int rows_in, int count, TRLWE tv, Bootstrap_Key key, TLWE_KS_Key ksk, int torus_base);
+
 /* ---- flat helpers used by the Python binding and bench.py (new) ----
  * Generate a whole bootstrap / key-switch key in the flat torus-domain layouts of mosfhet_hip.h. */
 void mosfhet_gen_bootstrap_key_flat(Torus *out /*[n][(k+1)l][k+1][N]*/, TRGSW_Key out_key, TLWE_Key in_key);

@@ -451,6 +451,41 @@ int mosfhet_hip_keyswitch_functional_bootstrap_batch(mosfhet_hip_ctx_t ctx, mosf
                                                      const uint64_t *d_tv, int tv_count, const uint64_t *d_in /*[count][kN+1]*/, int count,
                                                      int torus_base, int extract, void *stream);
 
+/* ---- cleartext-weight linear layers on LWE batches, y = W x + bias (capi_linear.inc, linear_kernels.h) ----
+ * The reference's tlwe_scale, tlwe_scale_addto, tlwe_scale_subto, tlwe_add and tlwe_sub (src/tlwe.c:143-191) with cleartext weights, for `count` independent
+ * inferences or circuit instances at once.  Samples are n + 1 torus words, the b word last, any 1 <= n <= 65535:
+ *     out[b][j][c] = (c == n ? bias[j] : 0) + sum_i W[j][i] in[b][i][c]   (mod 2^64);   d_in [count][rows_in][n+1], d_out [count][rows_out][n+1]
+ * W[j][i] is the multiplier tlwe_scale takes, read as a signed 64-bit number, shared by the whole batch; bias[j] is a torus word (a trivially encrypted constant).
+ * Exact integer arithmetic: no word depends on count, tiling, form (dense / sparse) or path.
+ * A handle holds the weights on the device and is read-only after creation.  `narrow` (info[3], set at creation iff every weight lies in [-2^31, 2^31)) selects
+ * the cheaper multiply sequence and changes no word. */
+typedef struct mosfhet_hip_linear *mosfhet_hip_linear_t;
+/* src/tlwe.c:143-191 as a dense layer: h_W [rows_out][rows_in], h_bias [rows_out] or NULL */
+int mosfhet_hip_linear_create_dense(mosfhet_hip_ctx_t ctx, mosfhet_hip_linear_t *out, const int64_t *h_W, const uint64_t *h_bias, int rows_out, int rows_in);
+/* src/tlwe.c:143-191 as a sparse map (a netlist level, a convolution, a gather): CSR, h_row_ptr [rows_out+1] (row_ptr[0] = 0, monotone), h_col / h_val [nnz];
+ * columns may be unsorted and may repeat within a row (they add), rows may be empty (bias alone); columns outside [0, rows_in) are refused. */
+int mosfhet_hip_linear_create_sparse(mosfhet_hip_ctx_t ctx, mosfhet_hip_linear_t *out, const int *h_row_ptr, const int *h_col, const int64_t *h_val,
+                                     const uint64_t *h_bias, int rows_out, int rows_in);
+int mosfhet_hip_linear_destroy(mosfhet_hip_linear_t lin);
+/* info: rows_out, rows_in, nnz (-1 dense), narrow, device bytes, form (0 dense, 1 sparse) */
+int mosfhet_hip_linear_info(mosfhet_hip_linear_t lin, long long info[6]);
+/* a copy for another context (device), after the pattern of mosfhet_hip_ksk_clone; a handle serves the context it was made or cloned for */
+int mosfhet_hip_linear_clone(mosfhet_hip_ctx_t ctx_other, mosfhet_hip_linear_t lin, mosfhet_hip_linear_t *out);
+/* src/tlwe.c:143-191 over a batch: d_out = W d_in + bias.  d_out must not overlap d_in.  Queues on `stream`, never synchronises; temporaries (sparse rows of
+ * more than 64 entries only) live in the calling thread's pool, so the call is capturable once a call of the same size has run. */
+int mosfhet_hip_tlwe_linear_batch(mosfhet_hip_ctx_t ctx, mosfhet_hip_linear_t lin, uint64_t *d_out, const uint64_t *d_in, int n, int count, void *stream);
+/* What a call of src/tlwe.c:143-191 over a batch will do (pure; no device; the function the launcher decides with).  `cus` is reserved for sizing grids: it is
+ * checked (>= 1) and sizes nothing today, every unit of work being one wavefront of a flat grid.
+ * plan = { form (0 dense, 1 sparse), TJ = output rows per wavefront, words per lane, workgroups, grid folds (gridDim.y; gridDim.x = ceil(workgroups / folds)),
+ *          passes over the input = ceil(rows_out / TJ), input bytes read by the model = passes * count * rows_in * (n+1) * 8, multiply sequence (0 narrow, 1 wide) } */
+int mosfhet_hip_tlwe_linear_plan(int rows_out, int rows_in, long long nnz /* -1 dense */, int narrow, int n, int count, int cus, long long plan[8]);
+/* src/tlwe.c:143-191, then the body of mosfhet_hip_keyswitch_functional_bootstrap_batch on the count * rows_out results: d_in [count][rows_in][kN+1], d_out
+ * [count * rows_out][kN+1] (extract = 1) or [count * rows_out][k+1][N] (0); tv_count is 1 or count * rows_out.  The linear map's output lives in the calling
+ * thread's pool, the switched samples in the bootstrap key's scratch as in that call: one stream per host thread. */
+int mosfhet_hip_linear_keyswitch_functional_bootstrap_batch(mosfhet_hip_ctx_t ctx, mosfhet_hip_linear_t lin, mosfhet_hip_ksk_t ksk, mosfhet_hip_bsk_t bsk,
+                                                            uint64_t *d_out, const uint64_t *d_tv, int tv_count, const uint64_t *d_in /*[count][rows_in][kN+1]*/,
+                                                            int count, int torus_base, int extract, void *stream);
+
 /* CMUX over a batch with one shared selector = entry `key_index` of a key handle (e.g. circuit-bootstrap outputs turned into a handle by
  * mosfhet_hip_bsk_create_from_device): d_out[b] = d_in0[b] + key (.) (d_in1[b] - d_in0[b]); d_out may alias d_in0.  The leveled caller of
  * the path (applications/leveled_lut/vertical_packing.c:24-52: CMUX tree, then blind_rotate with the selectors as key). */

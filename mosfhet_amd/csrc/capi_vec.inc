@@ -29,10 +29,10 @@ __global__ void tlwe_trivial_kernel(uint64_t *__restrict__ out, size_t words, in
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < words) out[i] = (i % (size_t)row == (size_t)row - 1) ? value : 0;
 }
-// out = out + a + b  /  out + a - b over flat words
-__global__ void words_add2_kernel(uint64_t *__restrict__ out, const uint64_t *__restrict__ a, const uint64_t *__restrict__ b, size_t words, int subtract_b) {
+// out = out + a + b  /  out + a - b over flat words; accumulate = 0: out = a + b  /  a - b (out is not read)
+__global__ void words_add2_kernel(uint64_t *__restrict__ out, const uint64_t *__restrict__ a, const uint64_t *__restrict__ b, size_t words, int subtract_b, int accumulate) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < words) out[i] = out[i] + a[i] + (subtract_b ? (uint64_t)0 - b[i] : b[i]);
+  if (i < words) out[i] = (accumulate ? out[i] : (uint64_t)0) + a[i] + (subtract_b ? (uint64_t)0 - b[i] : b[i]);
 }
 // trlwe_torus_packing of `slots` values into a trivial TRLWE (src/trlwe.c:662-667): b[i] = lut[i / (N / slots)]
 __global__ void torus_packing_kernel(uint64_t *__restrict__ tv, int N, const uint64_t *__restrict__ lut, int slots) {
@@ -56,11 +56,6 @@ __global__ void lut_level_slots_kernel(uint64_t *__restrict__ dst, const uint64_
   dst[i] = table[((j * B + q) * M + m) * row + w];
 }
 
-// out = a - b over flat words
-__global__ void words_sub_kernel(uint64_t *__restrict__ out, const uint64_t *__restrict__ a, const uint64_t *__restrict__ b, size_t words) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < words) out[i] = a[i] - b[i];
-}
 // packing-switch inputs of the comparison (src/integer.c:216-245): per integer m the B slots of its LUT.  mode 0: slot 0 = the running result c0[m], the others the
 // trivial sample `one`; mode 1 (sign steps): slots below B / 2 = c0[m], the others -c0[m].  dst [M][B][row]
 __global__ void cmp_slots_kernel(uint64_t *__restrict__ dst, const uint64_t *__restrict__ c0, size_t M, int B, int row, int mode, uint64_t one) {
@@ -134,7 +129,7 @@ extern "C" int mosfhet_hip_vec_addsub(mosfhet_hip_vec_t vec, uint64_t *d_c, cons
   hipLaunchKernelGGL(tlwe_trivial_kernel, dim3(g_plane), dim3(256), 0, s, d_c, plane, row, (uint64_t)0);
   for (int i = 0; i < d; i++) {
     uint64_t *c_i = d_c + (size_t)i * plane;
-    hipLaunchKernelGGL(words_add2_kernel, dim3(g_plane), dim3(256), 0, s, c_i, d_a + (size_t)i * plane, d_b + (size_t)i * plane, plane, subtract);
+    hipLaunchKernelGGL(words_add2_kernel, dim3(g_plane), dim3(256), 0, s, c_i, d_a + (size_t)i * plane, d_b + (size_t)i * plane, plane, subtract, 1);
     if ((rc = mosfhet_hip_keyswitch_functional_bootstrap_batch(ctx, vec->ksk, vec->bsk, rot, vec->d_luts, 1, c_i, M, B, 0, stream))) return rc;
     if ((rc = mosfhet_hip_trlwe_mv_extract_batch(ctx, c_i, rot, N, subtract ? 2 : 3, B, M, stream))) return rc;
     hipLaunchKernelGGL(tlwe_add_to_b_kernel, dim3(g_m), dim3(256), 0, s, c_i, M, (size_t)row, quarter);
@@ -278,7 +273,7 @@ extern "C" int mosfhet_hip_vec_cmp(mosfhet_hip_vec_t vec, uint64_t *d_c, const u
     return mosfhet_hip_functional_bootstrap_batch(ctx, vec->bsk, d_c, tvs, M, sel, M, B, stream);
   };
   for (int i = 0; i < d; i++) {
-    hipLaunchKernelGGL(words_sub_kernel, dim3(g_plane), dim3(256), 0, s, diff, d_a + (size_t)i * plane, d_b + (size_t)i * plane, plane);
+    hipLaunchKernelGGL(words_add2_kernel, dim3(g_plane), dim3(256), 0, s, diff, d_a + (size_t)i * plane, d_b + (size_t)i * plane, plane, 1, 0);   // diff = a - b
     if ((rc = step(diff, 0))) return rc;
   }
   if (a_signed && (rc = step(d_a + (size_t)(d - 1) * plane, 1))) return rc;

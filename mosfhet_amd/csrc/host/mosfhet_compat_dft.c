@@ -432,6 +432,44 @@ void mosfhet_eval_LUTs_packed_bits(TLWE **out, TLWE **in, int size, TRLWE **LUTs
   eval_LUTs_bits("mosfhet_eval_LUTs_packed_bits", out, in, size, LUTs, tables, pack_log, count, key, kska, kskb, ksk_out);
 }
 
+/* y = W x + bias with cleartext weights on `count` independent inputs (mosfhet_hip_tlwe_linear_batch; tlwe_scale_addto of src/tlwe.c:143-191 row by row):
+ * in[b][i] input i of instance b, W [rows_out][rows_in], bias [rows_out] or NULL, out[b][j] of the inputs' dimension.  With a bootstrap key: the linear map, then
+ * tlwe_keyswitch, then functional_bootstrap (mosfhet_hip_linear_keyswitch_functional_bootstrap_batch), out[b][j] of dimension N. */
+static void tlwe_linear(const char *name, TLWE **out, TLWE **in, const int64_t *W, const Torus *bias, int rows_out, int rows_in, int count, TRLWE tv, Bootstrap_Key key,
+                        TLWE_KS_Key ksk, int torus_base) {
+  const int n = in[0][0]->n, n_res = key ? key->N : n, N = key ? key->N : 0;
+  if (key) need_of(n == key->k * key->N, name, "the inputs must have the dimension k N of the bootstrap key's ring (the key switch's input dimension)");
+  const size_t tv_w = key ? (size_t)2 * N : 0, in_w = (size_t)count * (size_t)rows_in * ((size_t)n + 1), out_w = (size_t)count * (size_t)rows_out * ((size_t)n_res + 1);
+  const size_t up_w = tv_w + in_w;
+  Torus *h = (Torus *)mc_hstage_alloc(sizeof(Torus) * (up_w > out_w ? up_w : out_w)), *d = (Torus *)mc_stage_alloc(sizeof(Torus) * (up_w + out_w));
+  if (key) mc_trlwe_to_flat(h, tv);
+  lut_stage_bits(h + tv_w, in, rows_in, count, n, name);
+  mc_dev_copy(d, h, sizeof(Torus) * up_w, HIP_H2D);
+  mosfhet_hip_linear_t lin = NULL;
+  check_rc(mosfhet_hip_linear_create_dense(ectx(), &lin, W, bias, rows_out, rows_in), name);
+  if (key)
+    check_rc(mosfhet_hip_linear_keyswitch_functional_bootstrap_batch(ectx(), lin, (mosfhet_hip_ksk_t)mc_key_here(ksk->device, MC_KEY_KSK),
+                                                                     (mosfhet_hip_bsk_t)mc_key_here(key->device, MC_KEY_BSK), d + up_w, d, 1, d + tv_w, count, torus_base, 1, NULL),
+             name);
+  else
+    check_rc(mosfhet_hip_tlwe_linear_batch(ectx(), lin, d + up_w, d + tv_w, n, count, NULL), name);
+  mc_dev_copy(h, d + up_w, sizeof(Torus) * out_w, HIP_D2H);   /* (synchronous: the handle is idle when it is destroyed) */
+  mosfhet_hip_linear_destroy(lin);
+  lut_unstage_outputs(out, h, count, rows_out, n_res, name, "an output sample has the wrong dimension (the inputs' without a bootstrap key, N with one)");
+  mc_hstage_free(h);
+}
+
+void mosfhet_tlwe_linear_inputs(TLWE **out, TLWE **in, const int64_t *W, const Torus *bias, int rows_out, int rows_in, int count) {
+  need(out && in && W && rows_out >= 1 && rows_in >= 1 && count >= 1, "mosfhet_tlwe_linear_inputs: bad argument");
+  tlwe_linear("mosfhet_tlwe_linear_inputs", out, in, W, bias, rows_out, rows_in, count, NULL, NULL, NULL, 0);
+}
+
+void mosfhet_tlwe_linear_bootstrap_inputs(TLWE **out, TLWE **in, const int64_t *W, const Torus *bias, int rows_out, int rows_in, int count, TRLWE tv, Bootstrap_Key key,
+                                          TLWE_KS_Key ksk, int torus_base) {
+  need(out && in && W && tv && key && ksk && rows_out >= 1 && rows_in >= 1 && count >= 1, "mosfhet_tlwe_linear_bootstrap_inputs: bad argument");
+  tlwe_linear("mosfhet_tlwe_linear_bootstrap_inputs", out, in, W, bias, rows_out, rows_in, count, tv, key, ksk, torus_base);
+}
+
 /* src/trlwe.c:775-781: out = KeySwitch_{ks_key}(in(X^gen)); ks_key switches from key(X^gen) back to key (any entry of a key set) */
 void trlwe_eval_automorphism(TRLWE out, TRLWE in, uint64_t gen, TRLWE_KS_Key ks_key) {
   const int N = in->b->N;

@@ -154,6 +154,37 @@ def set_lut_bits_workspace(nbytes):
     _check(lib().mosfhet_hip_set_lut_bits_workspace(C.c_longlong(int(nbytes))))
 
 
+def tlwe_linear_plan(rows_out, rows_in, n, count, nnz=-1, narrow=True, cus=256):
+    """What a tlwe_linear call will do (no device needed; the launcher's own decision): dict(form, tj, words_per_lane, workgroups, grid_folds, passes,
+    input_bytes, multiply) -- "dense" / "sparse", output rows per wavefront, words per lane, workgroups, gridDim.y (gridDim.x = ceil(workgroups / grid_folds)),
+    passes over the input = ceil(rows_out / tj), passes * count * rows_in * (n + 1) * 8 and "narrow" / "wide".  include/mosfhet_hip.h: mosfhet_hip_tlwe_linear_plan."""
+    plan = (C.c_longlong * 8)()
+    _check(lib().mosfhet_hip_tlwe_linear_plan(int(rows_out), int(rows_in), C.c_longlong(int(nnz)), int(narrow), int(n), int(count), int(cus), plan))
+    return dict(form=("dense", "sparse")[plan[0]], tj=int(plan[1]), words_per_lane=int(plan[2]), workgroups=int(plan[3]), grid_folds=int(plan[4]), passes=int(plan[5]),
+                input_bytes=int(plan[6]), multiply=("narrow", "wide")[plan[7]])
+
+
+class LinearMap:
+    """The cleartext weights of y = W x + bias on the device (mosfhet_hip_linear_t): made by Engine.linear_dense / Engine.linear_sparse."""
+
+    def __init__(self, engine, handle):
+        self.engine, self.h = engine, handle
+        i = self.info()
+        self.rows_out, self.rows_in = i["rows_out"], i["rows_in"]
+
+    def info(self):
+        v = (C.c_longlong * 6)()
+        _check(lib().mosfhet_hip_linear_info(self.h, v))
+        return dict(rows_out=int(v[0]), rows_in=int(v[1]), nnz=int(v[2]), narrow=bool(v[3]), nbytes=int(v[4]), form=("dense", "sparse")[v[5]])
+
+    def close(self):
+        if self.h:
+            lib().mosfhet_hip_linear_destroy(self.h)
+            self.h = None
+
+    free = close
+
+
 class BootstrapKey:
     def __init__(self, engine, handle, n, k, N, l, Bg_bit):
         self.engine, self.h = engine, handle
@@ -881,6 +912,60 @@ class Engine:
             assert not addto
             out = self.torch.empty_like(a)
         _check(lib().mosfhet_hip_dft_mul_batch(self.h, _ptr(out), _ptr(a), _ptr(b), N, count, int(addto), self._stream()))
+        return out
+
+    # ---- cleartext-weight linear layers (include/mosfhet_hip.h: mosfhet_hip_linear_*, mosfhet_hip_tlwe_linear_batch) ----
+    @staticmethod
+    def _bias(bias, rows_out):
+        if bias is None:
+            return None, None
+        b = np.ascontiguousarray(np.asarray(bias).astype(np.uint64, copy=False))
+        assert b.shape == (rows_out,), "bias: one torus word per output row"
+        return b, b.ctypes.data_as(C.c_void_p)
+
+    def linear_dense(self, W, bias=None):
+        """Handle of a dense layer: W [rows_out][rows_in] int64 (the multipliers tlwe_scale takes), bias [rows_out] torus words or None."""
+        W = np.ascontiguousarray(W, dtype=np.int64)
+        assert W.ndim == 2
+        keep, pb = self._bias(bias, W.shape[0])
+        h = C.c_void_p()
+        _check(lib().mosfhet_hip_linear_create_dense(self.h, C.byref(h), W.ctypes.data_as(C.c_void_p), pb, int(W.shape[0]), int(W.shape[1])))
+        return LinearMap(self, h)
+
+    def linear_sparse(self, row_ptr, col, val, rows_in, bias=None):
+        """Handle of a sparse map in CSR: row_ptr [rows_out + 1], col / val [nnz] (columns may be unsorted or repeat within a row; rows may be empty)."""
+        row_ptr = np.ascontiguousarray(row_ptr, dtype=np.int32)
+        col, val = np.ascontiguousarray(col, dtype=np.int32), np.ascontiguousarray(val, dtype=np.int64)
+        rows_out = len(row_ptr) - 1
+        assert len(col) == len(val) and (rows_out < 0 or len(col) >= row_ptr[-1])
+        keep, pb = self._bias(bias, rows_out)
+        h = C.c_void_p()
+        _check(lib().mosfhet_hip_linear_create_sparse(self.h, C.byref(h), row_ptr.ctypes.data_as(C.c_void_p), col.ctypes.data_as(C.c_void_p),
+                                                      val.ctypes.data_as(C.c_void_p), pb, int(rows_out), int(rows_in)))
+        return LinearMap(self, h)
+
+    def clone_linear(self, lin):
+        """A copy of a LinearMap of another engine for this one (mosfhet_hip_linear_clone)."""
+        h = C.c_void_p()
+        _check(lib().mosfhet_hip_linear_clone(self.h, lin.h, C.byref(h)))
+        return LinearMap(self, h)
+
+    def tlwe_linear(self, lin, ct, out=None):
+        """out[b][j] = (0, bias[j]) + sum_i W[j][i] ct[b][i]: ct [count][rows_in][n + 1] -> [count][rows_out][n + 1], exact mod 2^64."""
+        count, rows_in, row = ct.shape
+        if out is None:
+            out = self.empty(count, lin.rows_out, row)
+        _check(lib().mosfhet_hip_tlwe_linear_batch(self.h, lin.h, _ptr(out), _ptr(ct), row - 1, count, self._stream()))
+        return out
+
+    def linear_keyswitch_functional_bootstrap(self, lin, ksk, bsk, tv, ct, torus_base, extract=True, out=None):
+        """tlwe_linear, then keyswitch_functional_bootstrap on the count * rows_out results, in one call: ct [count][rows_in][kN + 1] -> [count][rows_out][kN + 1]
+        (extract) or [count][rows_out][k + 1][N]; tv one test vector or one per result."""
+        count, samples = ct.shape[0], ct.shape[0] * lin.rows_out
+        if out is None:
+            out = self.empty(count, lin.rows_out, bsk.k * bsk.N + 1) if extract else self.empty(count, lin.rows_out, bsk.k + 1, bsk.N)
+        _check(lib().mosfhet_hip_linear_keyswitch_functional_bootstrap_batch(self.h, lin.h, ksk.h, bsk.h, _ptr(out), _ptr(tv), self._tv(tv, bsk, samples), _ptr(ct), count,
+                                                                             torus_base, int(extract), self._stream()))
         return out
 
     # ---- key switch ----
