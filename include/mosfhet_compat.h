@@ -320,6 +320,12 @@ void mosfhet_tlwe_linear_inputs(TLWE **out /*[count][rows_out]*/, TLWE **in /*[c
 void mosfhet_tlwe_linear_bootstrap_inputs(TLWE **out /*[count][rows_out]*/, TLWE **in /*[count][rows_in]*/, const int64_t *W, const Torus *bias /* or NULL */,
                                           int rows_out, int rows_in, int count, TRLWE tv, Bootstrap_Key key, TLWE_KS_Key ksk, int torus_base);
 
+/* trlwe_full_packing_keyswitch (src/keyswitch.c:195-227) over a batch in one call (new; mosfhet_hip_tlwe_pack_batch): out[o], o < ceil(total / per), packs the samples
+ * in[o per .. min(total, (o + 1) per) - 1], sample j of it at coefficient j (1 <= per <= N); key: what trlwe_new_full_packing_KS_key returns.  split = 1 gives the
+ * reference's summation (one accumulator pair, one rounding); split = P (at most min(n, 64)) cuts the key entries into P parts with a rounding each.
+ * Synchronous; aborts on error; primary device. */
+void mosfhet_tlwe_pack(TRLWE *out /*[ceil(total / per)]*/, TLWE *in /*[total]*/, uint64_t total, uint64_t per, TRLWE_KS_Key key, int split);
+
 /* ---- flat helpers used by the Python binding and bench.py (new) ----
  * Generate a whole bootstrap / key-switch key in the flat torus-domain layouts of mosfhet_hip.h. */
 void mosfhet_gen_bootstrap_key_flat(Torus *out /*[n][(k+1)l][k+1][N]*/, TRGSW_Key out_key, TLWE_Key in_key);

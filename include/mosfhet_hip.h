@@ -486,6 +486,28 @@ int mosfhet_hip_linear_keyswitch_functional_bootstrap_batch(mosfhet_hip_ctx_t ct
                                                             uint64_t *d_out, const uint64_t *d_tv, int tv_count, const uint64_t *d_in /*[count][rows_in][kN+1]*/,
                                                             int count, int torus_base, int extract, void *stream);
 
+/* ---- batches of LWE samples packed into TRLWE samples: trlwe_full_packing_keyswitch over a batch (src/keyswitch.c:195-227) ----
+ * pk: an FFT key-switch key set with entries = n_in (mosfhet_hip_trlwe_ksk_create / _generate; entry i switches from the constant polynomial s_in[i] -- the key
+ * trlwe_new_full_packing_KS_key makes), any t and base_bit, N in {1024, 2048, 4096}.
+ *   d_in [total][n_in + 1] -> d_out [outputs][2][N], outputs = ceil(total / per), 1 <= per <= N: output o packs samples o per .. min(total, (o + 1) per) - 1, sample j
+ *   of it at coefficient j; coefficients from the number of samples upward carry no b word and a zero mask column; the last output may be short.
+ * split = 1: output o is the reference's, word for word -- one accumulator pair over the entries i ascending and the rows j < t ascending, digits by the rounded
+ * rule of polynomial_decompose_i, one inverse transform and rounding per component, out.a = -as.a, out.b[j] = in[j].b - as.b[j].  split = P > 1 (at most
+ * min(n_in, 64)): the entries are cut into P consecutive parts of ceil(n_in / P) (the last one shorter), each with its own accumulator pair and rounding; the
+ * rounded parts are subtracted as 64-bit integers, so that P teams work on one output.  The words depend on the inputs, the key and P only -- never on total, on
+ * the position of an output in the batch, on the workspace, on the device or on the launch geometry; the call never chooses P itself.
+ * Asynchronous on `stream`, never synchronises; temporaries in the calling thread's pool (ONE STREAM PER HOST THREAD at a time); capturable once a call of the same
+ * size has run.  total == 0 is OK.  d_out must not overlap d_in.
+ * The transposed staging ([outputs of a round][n_in][N] words) is bounded by mosfhet_hip_set_tlwe_pack_workspace (default 256 MiB, 0 restores it); a larger batch
+ * runs in rounds of whole outputs.  mosfhet_hip_tlwe_pack_plan says what the launcher will do, as a pure function (no GPU):
+ * plan = { outputs, split used, entries per part, outputs per round, rounds, teams of the main launch (per round), transposed-staging bytes per round, key bytes
+ *          one team reads }.  split = 0 asks it to recommend one for `cus` CUs: enough parts to fill cus x (teams resident per CU at one wavefront per SIMD), never
+ * fewer than 8 entries per part, never above min(n_in, 64), and 1 as soon as the outputs alone fill the chip.  workspace_bytes = 0: the current setting. */
+int mosfhet_hip_tlwe_pack_batch(mosfhet_hip_ctx_t ctx, mosfhet_hip_gak_t pk, uint64_t *d_out /*[outputs][2][N]*/, const uint64_t *d_in /*[total][n_in+1]*/,
+                                int total, int per, int split, void *stream);
+int mosfhet_hip_tlwe_pack_plan(int N, int n_in, int t, int total, int per, int split /*0: recommend*/, int cus, long long workspace_bytes, long long plan[8]);
+int mosfhet_hip_set_tlwe_pack_workspace(long long bytes);
+
 /* CMUX over a batch with one shared selector = entry `key_index` of a key handle (e.g. circuit-bootstrap outputs turned into a handle by
  * mosfhet_hip_bsk_create_from_device): d_out[b] = d_in0[b] + key (.) (d_in1[b] - d_in0[b]); d_out may alias d_in0.  The leveled caller of
  * the path (applications/leveled_lut/vertical_packing.c:24-52: CMUX tree, then blind_rotate with the selectors as key). */

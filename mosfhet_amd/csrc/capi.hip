@@ -27,6 +27,7 @@
 #include "keygen_kernels.h"
 #include "leveled_lut_kernels.h"
 #include "linear_kernels.h"
+#include "pack_kernels.h"
 
 using namespace mosfhet;
 
@@ -78,7 +79,7 @@ struct DevBuf {
 // handle: handles are read-only after creation, so any number of host threads may share them, as the reference's callers share its keys
 // (re-entrant through thread-local scratch, src/polynomial.c:269-352).  A thread's launches are ordered by the stream it passes; buffers are
 // released at thread exit (hipFree waits for work in flight).
-enum { POOL_BSK = 0, POOL_EXT0 = 1, POOL_EXT1 = 2, POOL_CTX0 = 3, POOL_UNFOLD = 6, POOL_PACK = 7, POOL_VEC = 8, POOL_VEC2 = 9, POOL_VEC3 = 10, POOL_VEC4 = 11, POOL_LUT = 12, POOL_BITS = 13, POOL_LINEAR = 14, POOL_LINEAR_OUT = 15, POOL_SLOTS = 16 };
+enum { POOL_BSK = 0, POOL_EXT0 = 1, POOL_EXT1 = 2, POOL_CTX0 = 3, POOL_UNFOLD = 6, POOL_PACK = 7, POOL_VEC = 8, POOL_VEC2 = 9, POOL_VEC3 = 10, POOL_VEC4 = 11, POOL_LUT = 12, POOL_BITS = 13, POOL_LINEAR = 14, POOL_LINEAR_OUT = 15, POOL_PACK_COLS = 16, POOL_PACK_PARTS = 17, POOL_SLOTS = 18 };
 struct ThreadPool {
   struct Dev {
     int device = -1;
@@ -1396,8 +1397,7 @@ extern "C" int mosfhet_hip_trlwe_extract_tlwe_batch(mosfhet_hip_ctx_t ctx, uint6
   if (!ctx || (count > 0 && !d_out) || (count > 0 && !d_in) || N < 1 || idx < 0 || idx >= N || count < 0) return fail(MOSFHET_HIP_EINVAL, "trlwe_extract: bad argument");
   if (count == 0) return MOSFHET_HIP_OK;
   HIP_TRY(hipSetDevice(ctx->device));
-  hipLaunchKernelGGL(trlwe_extract_kernel, dim3((N + 255) / 256, count), dim3(256), 0, pick(ctx, stream), d_out, (size_t)N + 1, d_in,
-                     (size_t)2 * N, N, idx);
+  hipLaunchKernelGGL(trlwe_extract_kernel, dim3((N + 255) / 256, count), dim3(256), 0, pick(ctx, stream), d_out, (size_t)N + 1, d_in, (size_t)2 * N, N, 1, idx);
   HIP_TRY(hipGetLastError());
   return MOSFHET_HIP_OK;
 }
@@ -1406,8 +1406,7 @@ extern "C" int mosfhet_hip_trlwe_extract_tlwe_k_batch(mosfhet_hip_ctx_t ctx, uin
   if (!ctx || (count > 0 && !d_out) || (count > 0 && !d_in) || k < 1 || N < 1 || idx < 0 || idx >= N || count < 0) return fail(MOSFHET_HIP_EINVAL, "trlwe_extract: bad argument");
   if (count == 0) return MOSFHET_HIP_OK;
   HIP_TRY(hipSetDevice(ctx->device));
-  hipLaunchKernelGGL(trlwe_extract_k_kernel, dim3((unsigned)(((size_t)k * N + 255) / 256), count), dim3(256), 0, pick(ctx, stream), d_out, (size_t)k * N + 1, d_in,
-                     (size_t)(k + 1) * N, N, k, idx);
+  hipLaunchKernelGGL(trlwe_extract_kernel, dim3((unsigned)(((size_t)k * N + 255) / 256), count), dim3(256), 0, pick(ctx, stream), d_out, (size_t)k * N + 1, d_in, (size_t)(k + 1) * N, N, k, idx);
   HIP_TRY(hipGetLastError());
   return MOSFHET_HIP_OK;
 }
@@ -1417,7 +1416,7 @@ extern "C" int mosfhet_hip_tlwe_addto_batch(mosfhet_hip_ctx_t ctx, uint64_t *d_o
   const size_t words = (size_t)count * (n + 1);
   if (!words) return MOSFHET_HIP_OK;
   HIP_TRY(hipSetDevice(ctx->device));
-  hipLaunchKernelGGL(words_addto_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, pick(ctx, stream), d_out, d_in, words);
+  hipLaunchKernelGGL(words_add2_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, pick(ctx, stream), d_out, d_in, (const uint64_t *)nullptr, words, 0, 1);
   HIP_TRY(hipGetLastError());
   return MOSFHET_HIP_OK;
 }
@@ -1444,9 +1443,9 @@ extern "C" int mosfhet_hip_full_domain_functional_bootstrap_batch(mosfhet_hip_ct
   // src/bootstrap.c:525-527: sign = 2^62 - 2^(62 - precision), constant test vector (mask components zero, body constant)
   const uint64_t sign = (1ull << 62) - (1ull << (62 - precision));
   if (k > 1) HIP_TRY(hipMemsetAsync(tv_sign, 0, (size_t)(k - 1) * N * sizeof(uint64_t), s));
-  hipLaunchKernelGGL(trlwe_constant_kernel, dim3((N + 255) / 256), dim3(256), 0, s, tv_sign + (size_t)(k - 1) * N, N, sign);
+  hipLaunchKernelGGL(torus_packing_kernel, dim3((N + 255) / 256), dim3(256), 0, s, tv_sign + (size_t)(k - 1) * N, N, (const uint64_t *)nullptr, 1, sign, sign);
   if ((rc = mosfhet_hip_functional_bootstrap_batch(ctx, bsk, ct_sign, tv_sign, 1, d_in, count, 1 << (precision - 1), stream))) return rc;
-  hipLaunchKernelGGL(tlwe_add_to_b_kernel, dim3((count + 255) / 256), dim3(256), 0, s, ct_sign, count, (size_t)k * N + 1, (uint64_t)0 - sign);
+  hipLaunchKernelGGL(tlwe_add_to_word_kernel, dim3((count + 255) / 256), dim3(256), 0, s, ct_sign, count, (size_t)k * N + 1, ((size_t)k * N + 1) - 1, (uint64_t)0 - sign);
   if ((rc = mosfhet_hip_tlwe_keyswitch_batch(ctx, ksk, in2, ct_sign, count, stream))) return rc;
   if ((rc = mosfhet_hip_tlwe_addto_batch(ctx, in2, d_in, n, count, stream))) return rc;
   return mosfhet_hip_functional_bootstrap_batch(ctx, bsk, d_out, d_tv, tv_count, in2, count, 1 << precision, stream);
@@ -1471,11 +1470,9 @@ extern "C" int mosfhet_hip_multivalue_bootstrap_CLOT21_batch(mosfhet_hip_ctx_t c
   const int slot = N / (n_luts * torus_base);
   for (int i = 0; i < n_luts; i++) {
     if (k == 1)
-      hipLaunchKernelGGL(trlwe_extract_kernel, dim3((N + 255) / 256, count), dim3(256), 0, pick(ctx, stream), d_out + (size_t)i * tlwe, (size_t)n_luts * tlwe, rotated, trlwe, N,
-                         i * slot);
+      hipLaunchKernelGGL(trlwe_extract_kernel, dim3((N + 255) / 256, count), dim3(256), 0, pick(ctx, stream), d_out + (size_t)i * tlwe, (size_t)n_luts * tlwe, rotated, trlwe, N, 1, i * slot);
     else   // src/trlwe.c:540-552 over the k mask polynomials
-      hipLaunchKernelGGL(trlwe_extract_k_kernel, dim3((k * N + 255) / 256, count), dim3(256), 0, pick(ctx, stream), d_out + (size_t)i * tlwe, (size_t)n_luts * tlwe, rotated,
-                         trlwe, N, k, i * slot);
+      hipLaunchKernelGGL(trlwe_extract_kernel, dim3((k * N + 255) / 256, count), dim3(256), 0, pick(ctx, stream), d_out + (size_t)i * tlwe, (size_t)n_luts * tlwe, rotated, trlwe, N, k, i * slot);
   }
   HIP_TRY(hipGetLastError());
   return MOSFHET_HIP_OK;
@@ -1733,7 +1730,7 @@ static int circuit_bootstrap_3_run(const char *who, mosfhet_hip_ctx_t ctx, mosfh
   const size_t sel_row = (size_t)2 * (N / 2), sel_stride = (size_t)2 * l * sel_row;   // complex per selector row, per selector
   if (together) {
     for (int i = 0; i < l; i++)
-      hipLaunchKernelGGL(trlwe_extract_kernel, dim3((N + 255) / 256, count), dim3(256), 0, s, ext + (size_t)i * count * (N + 1), (size_t)N + 1, acc, (size_t)2 * N, N, i * slot);
+      hipLaunchKernelGGL(trlwe_extract_kernel, dim3((N + 255) / 256, count), dim3(256), 0, s, ext + (size_t)i * count * (N + 1), (size_t)N + 1, acc, (size_t)2 * N, N, 1, i * slot);
     HIP_TRY(launch_tlwe_keyswitch(kskb->d_ksk, stage, (size_t)2 * N, ext, (size_t)N + 1, l * count, N, 2 * N, N, kskb->t, kskb->base_bit, tl_ws(ctx->device), s, kskb->compressed,
                                   kskb->seed));
     for (int i = 0; i < l; i++) {
@@ -1751,7 +1748,7 @@ static int circuit_bootstrap_3_run(const char *who, mosfhet_hip_ctx_t ctx, mosfh
     return MOSFHET_HIP_OK;
   }
   for (int i = 0; i < l; i++) {
-    hipLaunchKernelGGL(trlwe_extract_kernel, dim3((N + 255) / 256, count), dim3(256), 0, s, ext, (size_t)N + 1, acc, (size_t)2 * N, N, i * slot);
+    hipLaunchKernelGGL(trlwe_extract_kernel, dim3((N + 255) / 256, count), dim3(256), 0, s, ext, (size_t)N + 1, acc, (size_t)2 * N, N, 1, i * slot);
     if (d_sel) {
       HIP_TRY(launch_tlwe_keyswitch(kskb->d_ksk, stage, (size_t)2 * N, ext, (size_t)N + 1, count, N, 2 * N, N, kskb->t, kskb->base_bit, tl_ws(ctx->device), s, kskb->compressed, kskb->seed));
       if ((rc = launch_fft_ks(ctx, kska, kska->d_ak, kska->d_ak + esz, nullptr, 0, stage, (size_t)2 * N, count, 3, s, d_sel + (size_t)i * sel_row, sel_stride))) return rc;
@@ -1807,3 +1804,4 @@ extern "C" int mosfhet_hip_time_programmable_bootstrap(mosfhet_hip_ctx_t ctx, mo
 #include "capi_lut.inc"
 #include "capi_bits.inc"
 #include "capi_linear.inc"
+#include "capi_pack.inc"

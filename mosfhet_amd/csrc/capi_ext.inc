@@ -118,20 +118,20 @@ extern "C" int mosfhet_hip_full_domain_functional_bootstrap_KS21_batch(mosfhet_h
     if ((rc = mosfhet_hip_functional_bootstrap_wo_extract_batch(ctx, bsk, acc, tv_sign, 1, d_in, count, l * half_base, stream))) return rc;
     for (int i = 0; i < l; i++) {
       const uint64_t sign = ~0ull << (64 - (i + 1) * Bg - 1);
-      hipLaunchKernelGGL(trlwe_extract_kernel, dim3((N + 255) / 256, count), dim3(256), 0, s, e_level(i), e_stride, acc, row, N, i * slot_size);
+      hipLaunchKernelGGL(trlwe_extract_kernel, dim3((N + 255) / 256, count), dim3(256), 0, s, e_level(i), e_stride, acc, row, N, 1, i * slot_size);
       hipLaunchKernelGGL(tlwe_add_to_word_kernel, dim3((count + 255) / 256), dim3(256), 0, s, e_level(i), count, e_stride, (size_t)N, (uint64_t)0 - sign);
       if (!together && (rc = switch_level(i))) return rc;
     }
   } else {
     if (rows_together) {
       for (int i = 0; i < l; i++)
-        hipLaunchKernelGGL(trlwe_constant_kernel, dim3((N + 255) / 256), dim3(256), 0, s, tv_sign + (size_t)i * row, N, ~0ull << (64 - (i + 1) * Bg - 1));
+        hipLaunchKernelGGL(torus_packing_kernel, dim3((N + 255) / 256), dim3(256), 0, s, tv_sign + (size_t)i * row, N, (const uint64_t *)nullptr, 1, ~0ull << (64 - (i + 1) * Bg - 1), ~0ull << (64 - (i + 1) * Bg - 1));
       if ((rc = bootstrap_common("full_domain_functional_bootstrap_KS21_2", ctx, bsk, ext, tv_sign, l, d_in, count * l, 0, 0, 0, half_base, 1, 0, stream, l))) return rc;
     }
     for (int i = 0; i < l; i++) {
       const uint64_t sign = ~0ull << (64 - (i + 1) * Bg - 1);
       if (!rows_together) {
-        hipLaunchKernelGGL(trlwe_constant_kernel, dim3((N + 255) / 256), dim3(256), 0, s, tv_sign, N, sign);
+        hipLaunchKernelGGL(torus_packing_kernel, dim3((N + 255) / 256), dim3(256), 0, s, tv_sign, N, (const uint64_t *)nullptr, 1, sign, sign);
         // (wide layout without the row-mode launch: the bootstrap writes level i's samples contiguously; they are spread to their input-major places afterwards)
         if ((rc = mosfhet_hip_functional_bootstrap_batch(ctx, bsk, wide_ext ? acc : ext, tv_sign, 1, d_in, count, half_base, stream))) return rc;
         if (wide_ext)
@@ -165,7 +165,7 @@ extern "C" int mosfhet_hip_multivalue_bootstrap_phase1_batch(mosfhet_hip_ctx_t c
   hipStream_t s = pick(ctx, stream);
   // constant test vector 1 / (4 torus_base)  (double2torus, src/misc.c:13-15)
   const uint64_t c = (uint64_t)(int64_t)(18446744073709551616.0 * (1. / (4 * torus_base)));
-  hipLaunchKernelGGL(trlwe_constant_kernel, dim3((N + 255) / 256), dim3(256), 0, s, tv, N, c);
+  hipLaunchKernelGGL(torus_packing_kernel, dim3((N + 255) / 256), dim3(256), 0, s, tv, N, (const uint64_t *)nullptr, 1, c, c);
   if ((rc = mosfhet_hip_functional_bootstrap_wo_extract_batch(ctx, bsk, acc, tv, 1, d_in, count, torus_base, stream))) return rc;
   hipLaunchKernelGGL(mv_phase1_rotate_kernel, dim3((2 * N + 255) / 256, torus_base + 1, count), dim3(256), 0, s, acc, d_out, N, torus_base);
   HIP_TRY(hipGetLastError());
@@ -248,7 +248,7 @@ extern "C" int mosfhet_hip_circuit_bootstrap_batch_ev(mosfhet_hip_ctx_t ctx, mos
     ext0 = tvs + w_tvs;
     stage0 = ext0 + w_e;
     for (int i = 0; i < l; i++)
-      hipLaunchKernelGGL(circuit_bootstrap_lut2_kernel, dim3((N + 255) / 256), dim3(256), 0, s, tvs + (size_t)i * row, N, 1ull << (64 - (i + 1) * bsk->Bg_bit));
+      hipLaunchKernelGGL(torus_packing_kernel, dim3((N + 255) / 256), dim3(256), 0, s, tvs + (size_t)i * row, N, (const uint64_t *)nullptr, 1, 1ull << (64 - (i + 1) * bsk->Bg_bit), (uint64_t)0);
     if ((rc = bootstrap_common("circuit_bootstrap", ctx, bsk, ext0, tvs, l, d_in, count * l, 0, 0, 0, 2, 1, 0, stream, l))) return rc;
     for (int half = 0; half < 2; half++) {
       const mosfhet_hip_ksk_t key = half ? kskb : kska;
@@ -266,7 +266,7 @@ extern "C" int mosfhet_hip_circuit_bootstrap_batch_ev(mosfhet_hip_ctx_t ctx, mos
   }
   if (together) {
     for (int i = 0; i < l; i++)
-      hipLaunchKernelGGL(trlwe_extract_kernel, dim3((N + 255) / 256, count), dim3(256), 0, s, ext + (size_t)i * count * (N + 1), (size_t)N + 1, acc, row, N, i * (N / (2 * l)));
+      hipLaunchKernelGGL(trlwe_extract_kernel, dim3((N + 255) / 256, count), dim3(256), 0, s, ext + (size_t)i * count * (N + 1), (size_t)N + 1, acc, row, N, 1, i * (N / (2 * l)));
     for (int half = 0; half < 2; half++) {   // rows i < l from the private table, rows l + i from the packing table
       const mosfhet_hip_ksk_t key = half ? kskb : kska;
       HIP_TRY(launch_tlwe_keyswitch(key->d_ksk, stage, row, ext, (size_t)N + 1, l * count, half ? N : N + 1, 2 * N, half ? N : -1, key->t, key->base_bit, tl_ws(ctx->device), s,
@@ -283,10 +283,10 @@ extern "C" int mosfhet_hip_circuit_bootstrap_batch_ev(mosfhet_hip_ctx_t ctx, mos
   }
   for (int i = 0; i < l; i++) {
     if (variant == 0) {
-      hipLaunchKernelGGL(circuit_bootstrap_lut2_kernel, dim3((N + 255) / 256), dim3(256), 0, s, tv, N, 1ull << (64 - (i + 1) * bsk->Bg_bit));
+      hipLaunchKernelGGL(torus_packing_kernel, dim3((N + 255) / 256), dim3(256), 0, s, tv, N, (const uint64_t *)nullptr, 1, 1ull << (64 - (i + 1) * bsk->Bg_bit), (uint64_t)0);
       if ((rc = mosfhet_hip_functional_bootstrap_batch(ctx, bsk, ext, tv, 1, d_in, count, 2, stream))) return rc;
     } else {
-      hipLaunchKernelGGL(trlwe_extract_kernel, dim3((N + 255) / 256, count), dim3(256), 0, s, ext, (size_t)N + 1, acc, row, N, i * (N / (2 * l)));
+      hipLaunchKernelGGL(trlwe_extract_kernel, dim3((N + 255) / 256, count), dim3(256), 0, s, ext, (size_t)N + 1, acc, row, N, 1, i * (N / (2 * l)));
     }
     HIP_TRY(launch_tlwe_keyswitch(kska->d_ksk, d_out + (size_t)i * row, trgsw, ext, (size_t)N + 1, count, N + 1, 2 * N, -1, kska->t, kska->base_bit, tl_ws(ctx->device), s, kska->compressed, kska->seed));
     HIP_TRY(launch_tlwe_keyswitch(kskb->d_ksk, d_out + (size_t)(l + i) * row, trgsw, ext, (size_t)N + 1, count, N, 2 * N, N, kskb->t, kskb->base_bit, tl_ws(ctx->device), s, kskb->compressed, kskb->seed));
@@ -339,7 +339,7 @@ extern "C" int mosfhet_hip_functional_bootstrap_trgsw_phase2_batch(mosfhet_hip_c
   const d2 *g = (const d2 *)d_in_dft;
   RING_DISPATCH(ctx, N, rc = launch_external_product<F>(l, bsk->Bg_bit, s, g, TW, d_tv, tmp, count, key_stride, in_stride, nullptr, nullptr, false));
   if (rc) return rc;
-  hipLaunchKernelGGL(trlwe_extract_kernel, dim3((N + 255) / 256, count), dim3(256), 0, s, d_out, (size_t)N + 1, tmp, (size_t)2 * N, N, 0);
+  hipLaunchKernelGGL(trlwe_extract_kernel, dim3((N + 255) / 256, count), dim3(256), 0, s, d_out, (size_t)N + 1, tmp, (size_t)2 * N, N, 1, 0);
   HIP_TRY(hipGetLastError());
   return MOSFHET_HIP_OK;
 }
@@ -389,7 +389,7 @@ static int tlwe_mul_strided(mosfhet_hip_ctx_t ctx, mosfhet_hip_ksk_t pksk, mosfh
     HIP_TRY(launch_tlwe_keyswitch(pksk->d_ksk, tmp2, row, d_in2, (size_t)N + 1, count, N, 2 * N, N, pksk->t, pksk->base_bit, tl_ws(ctx->device), s, pksk->compressed, pksk->seed));
   }
   if ((rc = mosfhet_hip_trlwe_tensor_prod_FFT_batch(ctx, rlk, prod, tmp1, tmp2, precision, count, stream))) return rc;
-  hipLaunchKernelGGL(trlwe_extract_kernel, dim3((N + 255) / 256, count), dim3(256), 0, s, d_out, (size_t)N + 1, prod, row, N, 0);
+  hipLaunchKernelGGL(trlwe_extract_kernel, dim3((N + 255) / 256, count), dim3(256), 0, s, d_out, (size_t)N + 1, prod, row, N, 1, 0);
   HIP_TRY(hipGetLastError());
   return MOSFHET_HIP_OK;
 }
@@ -427,14 +427,14 @@ extern "C" int mosfhet_hip_full_domain_functional_bootstrap_CLOT21_batch(mosfhet
     const int tb = 1 << (precision - 1);
     if (rows3) {
       HIP_TRY(hipMemcpyAsync(tv3, d_tv, 2 * row * sizeof(uint64_t), hipMemcpyDeviceToDevice, s));
-      hipLaunchKernelGGL(trlwe_constant_kernel, dim3((N + 255) / 256), dim3(256), 0, s, tv3 + 2 * row, N, sign);
+      hipLaunchKernelGGL(torus_packing_kernel, dim3((N + 255) / 256), dim3(256), 0, s, tv3 + 2 * row, N, (const uint64_t *)nullptr, 1, sign, sign);
       if ((rc = bootstrap_common("full_domain_functional_bootstrap_CLOT21", ctx, bsk, ext3, tv3, 3, d_in, count * 3, 0, 0, 0, tb, 1, 0, stream, 3))) return rc;
       uint64_t *dst[3] = {ct_f0, ct_f1, ct_sign};   // sample 3 b + j is input b under test vector j
       for (int j = 0; j < 3; j++)
         HIP_TRY(hipMemcpy2DAsync(dst[j], (size_t)(N + 1) * sizeof(uint64_t), ext3 + (size_t)j * (N + 1), (size_t)3 * (N + 1) * sizeof(uint64_t), (size_t)(N + 1) * sizeof(uint64_t),
                                  (size_t)count, hipMemcpyDeviceToDevice, s));
     } else {
-      hipLaunchKernelGGL(trlwe_constant_kernel, dim3((N + 255) / 256), dim3(256), 0, s, tv, N, sign);
+      hipLaunchKernelGGL(torus_packing_kernel, dim3((N + 255) / 256), dim3(256), 0, s, tv, N, (const uint64_t *)nullptr, 1, sign, sign);
       if ((rc = mosfhet_hip_functional_bootstrap_batch(ctx, bsk, ct_f0, d_tv, 1, d_in, count, tb, stream))) return rc;
       if ((rc = mosfhet_hip_functional_bootstrap_batch(ctx, bsk, ct_f1, d_tv + row, 1, d_in, count, tb, stream))) return rc;
       if ((rc = mosfhet_hip_functional_bootstrap_batch(ctx, bsk, ct_sign, tv, 1, d_in, count, tb, stream))) return rc;
@@ -444,13 +444,13 @@ extern "C" int mosfhet_hip_full_domain_functional_bootstrap_CLOT21_batch(mosfhet
     if (N % (4 * tb)) return fail(MOSFHET_HIP_EINVAL, "fdfb_CLOT21_2: N not divisible by 4 * torus_base");
     hipLaunchKernelGGL(clot21_lut_kernel, dim3((N + 255) / 256), dim3(256), 0, s, tv, d_tv, sign, N, tb);
     if ((rc = mosfhet_hip_functional_bootstrap_wo_extract_batch(ctx, bsk, acc, tv, 1, d_in, count, 4 * tb, stream))) return rc;
-    hipLaunchKernelGGL(trlwe_extract_kernel, dim3((N + 255) / 256, count), dim3(256), 0, s, ct_f0, (size_t)N + 1, acc, row, N, 0);
-    hipLaunchKernelGGL(trlwe_extract_kernel, dim3((N + 255) / 256, count), dim3(256), 0, s, ct_f1, (size_t)N + 1, acc, row, N, slot);
-    hipLaunchKernelGGL(trlwe_extract_kernel, dim3((N + 255) / 256, count), dim3(256), 0, s, ct_sign, (size_t)N + 1, acc, row, N, 2 * slot);
+    hipLaunchKernelGGL(trlwe_extract_kernel, dim3((N + 255) / 256, count), dim3(256), 0, s, ct_f0, (size_t)N + 1, acc, row, N, 1, 0);
+    hipLaunchKernelGGL(trlwe_extract_kernel, dim3((N + 255) / 256, count), dim3(256), 0, s, ct_f1, (size_t)N + 1, acc, row, N, 1, slot);
+    hipLaunchKernelGGL(trlwe_extract_kernel, dim3((N + 255) / 256, count), dim3(256), 0, s, ct_sign, (size_t)N + 1, acc, row, N, 1, 2 * slot);
   }
-  hipLaunchKernelGGL(tlwe_add_to_b_kernel, dim3((count + 255) / 256), dim3(256), 0, s, ct_sign, count, (size_t)N + 1, (uint64_t)0 - sign);
+  hipLaunchKernelGGL(tlwe_add_to_word_kernel, dim3((count + 255) / 256), dim3(256), 0, s, ct_sign, count, (size_t)N + 1, ((size_t)N + 1) - 1, (uint64_t)0 - sign);
   if ((rc = tlwe_mul_strided(ctx, pksk, rlk, ct_f1, ct_f1, ct_sign, precision, count, stream))) return rc;
-  hipLaunchKernelGGL(tlwe_add_to_b_kernel, dim3((count + 255) / 256), dim3(256), 0, s, ct_sign, count, (size_t)N + 1, 2 * sign);
+  hipLaunchKernelGGL(tlwe_add_to_word_kernel, dim3((count + 255) / 256), dim3(256), 0, s, ct_sign, count, (size_t)N + 1, ((size_t)N + 1) - 1, 2 * sign);
   if ((rc = tlwe_mul_strided(ctx, pksk, rlk, ct_f0, ct_f0, ct_sign, precision, count, stream))) return rc;
   HIP_TRY(hipMemcpyAsync(d_out, ct_f0, lwe * sizeof(uint64_t), hipMemcpyDeviceToDevice, s));
   return mosfhet_hip_tlwe_addto_batch(ctx, d_out, ct_f1, N, count, stream);
@@ -665,7 +665,7 @@ static int bootstrap_unfolded(const char *who, mosfhet_hip_ctx_t ctx, mosfhet_hi
         const long long tv_stride_b = tv_count == 1 ? 0 : (long long)2 * N;   // one test vector per ciphertext: the chunk's first
         if ((rc = launch_ubr_phase2(ctx, bsk, s, (const d2 *)sa, in_c, d_tv + (size_t)lo * (size_t)tv_stride_b, acc + (size_t)lo * 2 * N, c, 1, prec, tv_stride_b))) return rc;
       }
-      if (extract) hipLaunchKernelGGL(trlwe_extract_kernel, dim3((N + 255) / 256, count), dim3(256), 0, s, d_out, (size_t)N + 1, acc, (size_t)2 * N, N, 0);
+      if (extract) hipLaunchKernelGGL(trlwe_extract_kernel, dim3((N + 255) / 256, count), dim3(256), 0, s, d_out, (size_t)N + 1, acc, (size_t)2 * N, N, 1, 0);
       HIP_TRY(hipGetLastError());
       return MOSFHET_HIP_OK;
     }
@@ -680,7 +680,7 @@ static int bootstrap_unfolded(const char *who, mosfhet_hip_ctx_t ctx, mosfhet_hi
   p.n = bsk->n; p.l = bsk->l; p.Bg_bit = bsk->Bg_bit; p.unfolding = bsk->unfolding;
   p.prec_offset = (uint64_t)((int64_t)(18446744073709551616.0 * (1. / (4 * (double)torus_base))));
   RING_DISPATCH(ctx, N, hipLaunchKernelGGL(pbs_unfolded_kernel<F>, dim3(count), dim3(F::THREADS), 0, s, p));
-  if (extract) hipLaunchKernelGGL(trlwe_extract_kernel, dim3((N + 255) / 256, count), dim3(256), 0, s, d_out, (size_t)N + 1, acc, (size_t)2 * N, N, 0);
+  if (extract) hipLaunchKernelGGL(trlwe_extract_kernel, dim3((N + 255) / 256, count), dim3(256), 0, s, d_out, (size_t)N + 1, acc, (size_t)2 * N, N, 1, 0);
   HIP_TRY(hipGetLastError());
   return MOSFHET_HIP_OK;
 }
@@ -715,7 +715,7 @@ extern "C" int mosfhet_hip_multivalue_bootstrap_UBR_phase2_batch(mosfhet_hip_ctx
   const uint64_t prec = (uint64_t)((int64_t)(18446744073709551616.0 * (1. / (4 * (double)torus_base))));
   hipStream_t s = pick(ctx, stream);
   if ((rc = launch_ubr_phase2(ctx, bsk, s, (const d2 *)d_sa, d_in, d_tvs, acc, units, tv_count, prec))) return rc;
-  hipLaunchKernelGGL(trlwe_extract_kernel, dim3((N + 255) / 256, units), dim3(256), 0, s, d_out, (size_t)N + 1, acc, (size_t)2 * N, N, 0);
+  hipLaunchKernelGGL(trlwe_extract_kernel, dim3((N + 255) / 256, units), dim3(256), 0, s, d_out, (size_t)N + 1, acc, (size_t)2 * N, N, 1, 0);
   HIP_TRY(hipGetLastError());
   return MOSFHET_HIP_OK;
 }

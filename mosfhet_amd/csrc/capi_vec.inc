@@ -29,16 +29,6 @@ __global__ void tlwe_trivial_kernel(uint64_t *__restrict__ out, size_t words, in
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < words) out[i] = (i % (size_t)row == (size_t)row - 1) ? value : 0;
 }
-// out = out + a + b  /  out + a - b over flat words; accumulate = 0: out = a + b  /  a - b (out is not read)
-__global__ void words_add2_kernel(uint64_t *__restrict__ out, const uint64_t *__restrict__ a, const uint64_t *__restrict__ b, size_t words, int subtract_b, int accumulate) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < words) out[i] = (accumulate ? out[i] : (uint64_t)0) + a[i] + (subtract_b ? (uint64_t)0 - b[i] : b[i]);
-}
-// trlwe_torus_packing of `slots` values into a trivial TRLWE (src/trlwe.c:662-667): b[i] = lut[i / (N / slots)]
-__global__ void torus_packing_kernel(uint64_t *__restrict__ tv, int N, const uint64_t *__restrict__ lut, int slots) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < N) { tv[i] = 0; tv[N + i] = lut[i / (N / slots)]; }
-}
 // packing-switch inputs of ReLU (src/ml.c:6-10): unit (i, m), slot q = digit i of integer m for q < B/2, a trivial zero above; dst [units][B][row]
 __global__ void relu_slots_kernel(uint64_t *__restrict__ dst, const uint64_t *__restrict__ in, size_t units, int B, int row) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -83,19 +73,19 @@ extern "C" int mosfhet_hip_vec_create(mosfhet_hip_ctx_t ctx, mosfhet_hip_vec_t *
   const int N = bsk->N;
   HIP_TRY(hipMalloc((void **)&v->d_luts, (size_t)3 * 2 * N * sizeof(uint64_t)));
   // ADDSUB_LUT: every slot -1/(4B) (src/ufhe.c:61-64)
-  hipLaunchKernelGGL(trlwe_constant_kernel, dim3((N + 255) / 256), dim3(256), 0, nullptr, v->d_luts, N, vec_double2torus(-1. / (4 * torus_base)));
+  hipLaunchKernelGGL(torus_packing_kernel, dim3((N + 255) / 256), dim3(256), 0, nullptr, v->d_luts, N, (const uint64_t *)nullptr, 1, vec_double2torus(-1. / (4 * torus_base)), vec_double2torus(-1. / (4 * torus_base)));
   // ReLU's LUT for the top digit (src/ml.c:14-18): slot j < B/2 keeps j, the negative half gives 0
   std::vector<uint64_t> slots(torus_base, 0);
   for (int j = 0; j < torus_base / 2; j++) slots[j] = vec_double2torus((double)j / (torus_base * 2));
   DevBuf d_slots;
   HIP_TRY(d_slots.alloc(slots.size() * sizeof(uint64_t)));
   HIP_TRY(hipMemcpy(d_slots.p, slots.data(), slots.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(torus_packing_kernel, dim3((N + 255) / 256), dim3(256), 0, nullptr, v->d_luts + (size_t)2 * N, N, d_slots.as<uint64_t>(), torus_base);
+  hipLaunchKernelGGL(torus_packing_kernel, dim3((N + 255) / 256), dim3(256), 0, nullptr, v->d_luts + (size_t)2 * N, N, d_slots.as<uint64_t>(), torus_base, (uint64_t)0, (uint64_t)0);
   HIP_TRY(hipStreamSynchronize(nullptr));
   // SIGNEXTEND_LUT (src/ufhe.c:66-71): 0 for the non-negative half, (B - 1) / (2 B) for the negative one
   for (int j = 0; j < torus_base; j++) slots[j] = j < torus_base / 2 ? 0 : vec_double2torus((double)(torus_base - 1) / (2 * torus_base));
   HIP_TRY(hipMemcpy(d_slots.p, slots.data(), slots.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(torus_packing_kernel, dim3((N + 255) / 256), dim3(256), 0, nullptr, v->d_luts + (size_t)4 * N, N, d_slots.as<uint64_t>(), torus_base);
+  hipLaunchKernelGGL(torus_packing_kernel, dim3((N + 255) / 256), dim3(256), 0, nullptr, v->d_luts + (size_t)4 * N, N, d_slots.as<uint64_t>(), torus_base, (uint64_t)0, (uint64_t)0);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(nullptr));
   *out = v.release();
@@ -132,7 +122,7 @@ extern "C" int mosfhet_hip_vec_addsub(mosfhet_hip_vec_t vec, uint64_t *d_c, cons
     hipLaunchKernelGGL(words_add2_kernel, dim3(g_plane), dim3(256), 0, s, c_i, d_a + (size_t)i * plane, d_b + (size_t)i * plane, plane, subtract, 1);
     if ((rc = mosfhet_hip_keyswitch_functional_bootstrap_batch(ctx, vec->ksk, vec->bsk, rot, vec->d_luts, 1, c_i, M, B, 0, stream))) return rc;
     if ((rc = mosfhet_hip_trlwe_mv_extract_batch(ctx, c_i, rot, N, subtract ? 2 : 3, B, M, stream))) return rc;
-    hipLaunchKernelGGL(tlwe_add_to_b_kernel, dim3(g_m), dim3(256), 0, s, c_i, M, (size_t)row, quarter);
+    hipLaunchKernelGGL(tlwe_add_to_word_kernel, dim3(g_m), dim3(256), 0, s, c_i, M, (size_t)row, ((size_t)row) - 1, quarter);
     if (i != d - 1) {
       uint64_t *c_n = c_i + plane;
       hipLaunchKernelGGL(tlwe_trivial_kernel, dim3(g_plane), dim3(256), 0, s, c_n, plane, row, carry0);
@@ -278,7 +268,7 @@ extern "C" int mosfhet_hip_vec_cmp(mosfhet_hip_vec_t vec, uint64_t *d_c, const u
   }
   if (a_signed && (rc = step(d_a + (size_t)(d - 1) * plane, 1))) return rc;
   if (b_signed && (rc = step(d_b + (size_t)(d - 1) * plane, 1))) return rc;
-  hipLaunchKernelGGL(tlwe_add_to_b_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, s, d_c, M, (size_t)row, one);
+  hipLaunchKernelGGL(tlwe_add_to_word_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, s, d_c, M, (size_t)row, ((size_t)row) - 1, one);
   HIP_TRY(hipGetLastError());
   return MOSFHET_HIP_OK;
 }
@@ -342,10 +332,10 @@ static int vec_carry_step(mosfhet_hip_vec_t vec, uint64_t *c_i, uint64_t *c_next
   int rc;
   if ((rc = mosfhet_hip_keyswitch_functional_bootstrap_batch(ctx, vec->ksk, vec->bsk, rot, vec->d_luts, 1, c_i, M, B, 0, stream))) return rc;
   if ((rc = mosfhet_hip_trlwe_mv_extract_batch(ctx, c_i, rot, N, 3, B, M, stream))) return rc;
-  hipLaunchKernelGGL(tlwe_add_to_b_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, s, c_i, M, (size_t)row, vec_double2torus(-0.25));
+  hipLaunchKernelGGL(tlwe_add_to_word_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, s, c_i, M, (size_t)row, ((size_t)row) - 1, vec_double2torus(-0.25));
   if (c_next) {
     if (set) hipLaunchKernelGGL(tlwe_trivial_kernel, dim3((unsigned)((plane + 255) / 256)), dim3(256), 0, s, c_next, plane, row, vec_double2torus(1. / (4 * B)));
-    else hipLaunchKernelGGL(tlwe_add_to_b_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, s, c_next, M, (size_t)row, vec_double2torus(1. / (4 * B)));
+    else hipLaunchKernelGGL(tlwe_add_to_word_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, s, c_next, M, (size_t)row, ((size_t)row) - 1, vec_double2torus(1. / (4 * B)));
     if ((rc = mosfhet_hip_trlwe_mv_extract_batch(ctx, c_next, rot, N, 2, 1, M, stream))) return rc;
   }
   return MOSFHET_HIP_OK;
@@ -385,8 +375,8 @@ static int vec_sl_add(mosfhet_hip_vec_t vec, uint64_t *d_c, int dc, const uint64
   hipLaunchKernelGGL(tlwe_trivial_kernel, dim3(g_plane), dim3(256), 0, s, d_c, plane, row, (uint64_t)0);
   for (int i = 0; i < size; i++) {
     uint64_t *c_i = d_c + (size_t)i * plane, *c_n = i != size - 1 ? c_i + plane : nullptr;
-    if (i - g >= 0 && i - g < da) hipLaunchKernelGGL(words_addto_kernel, dim3(g_plane), dim3(256), 0, s, c_i, d_a + (size_t)(i - g) * plane, plane);
-    if (i - h >= 0 && i - h < db) hipLaunchKernelGGL(words_addto_kernel, dim3(g_plane), dim3(256), 0, s, c_i, d_b + (size_t)(i - h) * plane, plane);
+    if (i - g >= 0 && i - g < da) hipLaunchKernelGGL(words_add2_kernel, dim3(g_plane), dim3(256), 0, s, c_i, d_a + (size_t)(i - g) * plane, (const uint64_t *)nullptr, plane, 0, 1);
+    if (i - h >= 0 && i - h < db) hipLaunchKernelGGL(words_add2_kernel, dim3(g_plane), dim3(256), 0, s, c_i, d_b + (size_t)(i - h) * plane, (const uint64_t *)nullptr, plane, 0, 1);
     if (i - g < 0 || i - h < 0) {
       if (c_n) hipLaunchKernelGGL(tlwe_trivial_kernel, dim3(g_plane), dim3(256), 0, s, c_n, plane, row, (uint64_t)0);
       continue;
@@ -405,7 +395,7 @@ static int vec_sl_addto(mosfhet_hip_vec_t vec, uint64_t *d_b, int db, const uint
   int rc;
   for (int i = 0; i < size; i++) {
     uint64_t *b_i = d_b + (size_t)i * plane;
-    if (i - g >= 0 && i - g < da) hipLaunchKernelGGL(words_addto_kernel, dim3((unsigned)((plane + 255) / 256)), dim3(256), 0, s, b_i, d_a + (size_t)(i - g) * plane, plane);
+    if (i - g >= 0 && i - g < da) hipLaunchKernelGGL(words_add2_kernel, dim3((unsigned)((plane + 255) / 256)), dim3(256), 0, s, b_i, d_a + (size_t)(i - g) * plane, (const uint64_t *)nullptr, plane, 0, 1);
     if (i - g < 0) continue;
     if ((rc = vec_carry_step(vec, b_i, i != size - 1 ? b_i + plane : nullptr, 0, rot, M, stream))) return rc;
   }

@@ -106,12 +106,6 @@ __global__ void trgsw_trivial_one_kernel(uint64_t *__restrict__ g, int N, int l,
   g[(size_t)q * 2 * N + pos] = pos == hot ? 1ull << (64 - (q % l + 1) * Bg_bit) : 0;
 }
 
-// two-slot test vector {0, h} of circuit_bootstrap [src/bootstrap.c:314-315]
-__global__ void circuit_bootstrap_lut2_kernel(uint64_t *__restrict__ tv, int N, uint64_t h) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < N) { tv[i] = 0; tv[N + i] = i >= N / 2 ? h : 0; }
-}
-
 // multivalue_bootstrap_phase1 rotations [src/bootstrap.c:236-241]: out[b][i] = acc[b] X^(i N / torus_base) for i < torus_base
 // (i = 0: copy) and out[b][torus_base] = acc[b] X^torus_base + acc[b].  grid = (2N / 256, torus_base + 1, count)
 __global__ void mv_phase1_rotate_kernel(const uint64_t *__restrict__ acc, uint64_t *__restrict__ out, int N, int torus_base) {

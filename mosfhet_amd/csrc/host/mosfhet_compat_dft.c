@@ -470,6 +470,31 @@ void mosfhet_tlwe_linear_bootstrap_inputs(TLWE **out, TLWE **in, const int64_t *
   tlwe_linear("mosfhet_tlwe_linear_bootstrap_inputs", out, in, W, bias, rows_out, rows_in, count, tv, key, ksk, torus_base);
 }
 
+/* trlwe_full_packing_keyswitch (src/keyswitch.c:195-227) over a batch in one call (mosfhet_hip_tlwe_pack_batch): out[o] packs in[o per .. min(total, (o + 1) per) - 1],
+ * sample j of it at coefficient j; key from trlwe_new_full_packing_KS_key; split = 1 gives the reference's summation, split = P cuts the key entries into P parts. */
+void mosfhet_tlwe_pack(TRLWE *out, TLWE *in, uint64_t total, uint64_t per, TRLWE_KS_Key key, int split) {
+  const char *name = "mosfhet_tlwe_pack";
+  need(out && in && key && key->device && total >= 1 && total <= 0x7fffffffu && per >= 1 && per <= 4096, "mosfhet_tlwe_pack: bad argument");
+  const int n = key->k, N = out[0]->b->N;
+  const size_t outputs = (size_t)((total + per - 1) / per);
+  const size_t in_w = (size_t)total * ((size_t)n + 1), out_w = outputs * 2 * (size_t)N;
+  Torus *h = (Torus *)mc_hstage_alloc(sizeof(Torus) * (in_w > out_w ? in_w : out_w)), *d = (Torus *)mc_stage_alloc(sizeof(Torus) * (in_w + out_w));
+  for (uint64_t j = 0; j < total; j++) {
+    Torus *w = h + (size_t)j * ((size_t)n + 1);
+    need_of(in[j]->n == n, name, "an input is not an LWE sample of the key's input dimension");
+    memcpy(w, in[j]->a, sizeof(Torus) * (size_t)n);
+    w[n] = in[j]->b;
+  }
+  mc_dev_copy(d, h, sizeof(Torus) * in_w, HIP_H2D);
+  check_rc(mosfhet_hip_tlwe_pack_batch(ectx(), (mosfhet_hip_gak_t)mc_key_here(key->device, MC_KEY_GAK), d + in_w, d, (int)total, (int)per, split, NULL), name);
+  mc_dev_copy(h, d + in_w, sizeof(Torus) * out_w, HIP_D2H);
+  for (size_t o = 0; o < outputs; o++) {
+    need_of(out[o]->k == 1 && out[o]->b->N == N, name, "an output is not a k = 1 TRLWE sample of the key's ring");
+    mc_trlwe_from_flat(out[o], h + o * 2 * (size_t)N);
+  }
+  mc_hstage_free(h);
+}
+
 /* src/trlwe.c:775-781: out = KeySwitch_{ks_key}(in(X^gen)); ks_key switches from key(X^gen) back to key (any entry of a key set) */
 void trlwe_eval_automorphism(TRLWE out, TRLWE in, uint64_t gen, TRLWE_KS_Key ks_key) {
   const int N = in->b->N;

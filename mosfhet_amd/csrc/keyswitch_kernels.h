@@ -178,42 +178,31 @@ __global__ __launch_bounds__(64 * NW) void tlwe_keyswitch_kernel(const uint64_t 
 }
 
 // ---- small batched TLWE / TRLWE glue kernels (all exact mod 2^64) ----
-// tlwe_addto over flat batches [src/tlwe.c:170-173]: out[i] += in[i]
-__global__ void words_addto_kernel(uint64_t *__restrict__ out, const uint64_t *__restrict__ in, size_t words) {
+// out = out + a + b  /  out + a - b over flat words; accumulate = 0: out = a + b  /  a - b (out is not read); b == nullptr: no second operand (tlwe_addto over flat
+// batches, src/tlwe.c:170-173: out += a)
+__global__ void words_add2_kernel(uint64_t *__restrict__ out, const uint64_t *__restrict__ a, const uint64_t *__restrict__ b, size_t words, int subtract_b, int accumulate) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < words) out[i] += in[i];
+  if (i < words) out[i] = (accumulate ? out[i] : (uint64_t)0) + a[i] + (b ? (subtract_b ? (uint64_t)0 - b[i] : b[i]) : (uint64_t)0);
 }
 
-// ct[b].b += delta for every sample of a batch (row = n + 1 words)  [src/bootstrap.c:530: ct_sign->b -= sign]
-__global__ void tlwe_add_to_b_kernel(uint64_t *__restrict__ ct, int count, size_t row, uint64_t delta) {
-  const int b = blockIdx.x * blockDim.x + threadIdx.x;
-  if (b < count) ct[(size_t)b * row + row - 1] += delta;
-}
-
-// the same with the samples `stride` words apart and the b word at `word` (samples interleaved with others: capi_ext.inc, the KS21 level layout)
+// ct[b][word] += delta for every sample of a batch, the samples `stride` words apart: word = stride - 1 is the b word of rows of n + 1 words (src/bootstrap.c:530:
+// ct_sign->b -= sign); any other pair serves samples interleaved with others (capi_ext.inc, the KS21 level layout)
 __global__ void tlwe_add_to_word_kernel(uint64_t *__restrict__ ct, int count, size_t stride, size_t word, uint64_t delta) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b < count) ct[(size_t)b * stride + word] += delta;
 }
 
-// fill a trivial TRLWE whose b polynomial is the constant `value` (trlwe_torus_packing with one slot, src/trlwe.c:662-667)
-__global__ void trlwe_constant_kernel(uint64_t *__restrict__ tv, int N, uint64_t value) {
+// trivial TRLWE test vectors.  lut != nullptr: trlwe_torus_packing of `slots` values (src/trlwe.c:662-667), b[i] = lut[i / (N / slots)].  lut == nullptr: b[i] = low
+// below N / 2 and value from there on -- value == low is the constant polynomial (trlwe_torus_packing with one slot), low = 0 the two-slot test vector {0, h} of
+// circuit_bootstrap (src/bootstrap.c:314-315)
+__global__ void torus_packing_kernel(uint64_t *__restrict__ tv, int N, const uint64_t *__restrict__ lut, int slots, uint64_t value, uint64_t low) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < N) { tv[i] = 0; tv[N + i] = value; }
+  if (i < N) { tv[i] = 0; tv[N + i] = lut ? lut[i / (N / slots)] : (i >= N / 2 ? value : low); }
 }
 
-// trlwe_extract_tlwe at coefficient idx for a batch (k = 1) [src/trlwe.c:540-552]; in stride / out stride in words
+// trlwe_extract_tlwe at coefficient idx for a batch, k >= 1 mask polynomials [src/trlwe.c:540-552 loops over i < k]: in = [k+1][N] words, out = [kN+1]; in stride /
+// out stride in words
 __global__ void trlwe_extract_kernel(uint64_t *__restrict__ out, size_t out_stride, const uint64_t *__restrict__ in, size_t in_stride,
-                                     int N, int idx) {
-  const uint64_t *c = in + (size_t)blockIdx.y * in_stride;
-  uint64_t *o = out + (size_t)blockIdx.y * out_stride;
-  const int j = blockIdx.x * blockDim.x + threadIdx.x;
-  if (j < N) o[j] = (j <= idx) ? c[idx - j] : (0 - c[N + idx - j]);
-  if (j == 0) o[N] = c[N + idx];
-}
-
-// the same for k >= 1 mask polynomials [src/trlwe.c:540-552 loops over i < k]: in = [k+1][N] words, out = [kN+1]
-__global__ void trlwe_extract_k_kernel(uint64_t *__restrict__ out, size_t out_stride, const uint64_t *__restrict__ in, size_t in_stride,
                                        int N, int k, int idx) {
   const uint64_t *c = in + (size_t)blockIdx.y * in_stride;
   uint64_t *o = out + (size_t)blockIdx.y * out_stride;

@@ -164,6 +164,23 @@ def tlwe_linear_plan(rows_out, rows_in, n, count, nnz=-1, narrow=True, cus=256):
                 input_bytes=int(plan[6]), multiply=("narrow", "wide")[plan[7]])
 
 
+def tlwe_pack_plan(N, n_in, t, total, per, split=0, cus=256, workspace_bytes=0):
+    """What a tlwe_pack call will do (no device needed; the launcher's own decision): dict(outputs, split, part_entries, outputs_per_round, rounds, teams,
+    staging_bytes, key_bytes) -- TRLWE samples written, parts the entries are cut into (split = 0 asks for a recommendation on `cus` CUs), entries per part,
+    outputs per round of the transposed staging, rounds, teams of a round's main launch, bytes of a round's staging and key bytes one team reads.
+    workspace_bytes = 0: the current setting.  include/mosfhet_hip.h: mosfhet_hip_tlwe_pack_plan."""
+    plan = (C.c_longlong * 8)()
+    _check(lib().mosfhet_hip_tlwe_pack_plan(int(N), int(n_in), int(t), int(total), int(per), int(split), int(cus), C.c_longlong(int(workspace_bytes)), plan))
+    return dict(outputs=int(plan[0]), split=int(plan[1]), part_entries=int(plan[2]), outputs_per_round=int(plan[3]), rounds=int(plan[4]), teams=int(plan[5]),
+                staging_bytes=int(plan[6]), key_bytes=int(plan[7]))
+
+
+def set_tlwe_pack_workspace(nbytes):
+    """Bound of tlwe_pack's transposed staging (0 restores the default of 256 MiB): batches that need more run in rounds of whole outputs; results do not depend
+    on it."""
+    _check(lib().mosfhet_hip_set_tlwe_pack_workspace(C.c_longlong(int(nbytes))))
+
+
 class LinearMap:
     """The cleartext weights of y = W x + bias on the device (mosfhet_hip_linear_t): made by Engine.linear_dense / Engine.linear_sparse."""
 
@@ -966,6 +983,18 @@ class Engine:
             out = self.empty(count, lin.rows_out, bsk.k * bsk.N + 1) if extract else self.empty(count, lin.rows_out, bsk.k + 1, bsk.N)
         _check(lib().mosfhet_hip_linear_keyswitch_functional_bootstrap_batch(self.h, lin.h, ksk.h, bsk.h, _ptr(out), _ptr(tv), self._tv(tv, bsk, samples), _ptr(ct), count,
                                                                              torus_base, int(extract), self._stream()))
+        return out
+
+    # ---- LWE batches packed into TRLWE samples (include/mosfhet_hip.h: mosfhet_hip_tlwe_pack_batch) ----
+    def tlwe_pack(self, pk, ct, per=None, split=1, out=None):
+        """trlwe_full_packing_keyswitch over a batch: ct [total][n_in + 1] -> [ceil(total / per)][2][N]; pk an FFT key-switch key set of n_in entries
+        (load_trlwe_ks_keys / generate_trlwe_ks_keys), per samples per output (default N), sample j of an output at coefficient j.  split = 1: the reference's
+        words; split = P: P teams per output (tlwe_pack_plan recommends one)."""
+        total = ct.shape[0]
+        per = pk.N if per is None else int(per)
+        if out is None:
+            out = self.empty(-(-total // per) if per >= 1 else 0, 2, pk.N)
+        _check(lib().mosfhet_hip_tlwe_pack_batch(self.h, pk.h, _ptr(out) if total else None, _ptr(ct) if total else None, int(total), per, int(split), self._stream()))
         return out
 
     # ---- key switch ----

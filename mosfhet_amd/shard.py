@@ -16,6 +16,15 @@ def shard_bounds(count, rank, world):
     return lo, lo + base + (1 if rank < extra else 0)
 
 
+def shard_bounds_whole(count, unit, rank, world):
+    """shard_bounds for work that is cut at multiples of `unit` only: the ceil(count / unit) groups are dealt like shard_bounds deals units and the slice is
+    returned in units, the last group possibly short.  Packing LWE samples into TRLWE samples (Engine.tlwe_pack) shards this way with unit = per: every rank
+    packs whole outputs, so the outputs of the ranks, concatenated, are the outputs of the unsharded call."""
+    assert unit >= 1
+    lo, hi = shard_bounds(-(-count // unit), rank, world)
+    return min(count, lo * unit), min(count, hi * unit)
+
+
 def shard(array, rank, world):
     lo, hi = shard_bounds(len(array), rank, world)
     return array[lo:hi]
