@@ -326,6 +326,13 @@ void mosfhet_tlwe_linear_bootstrap_inputs(TLWE **out /*[count][rows_out]*/, TLWE
  * Synchronous; aborts on error; primary device. */
 void mosfhet_tlwe_pack(TRLWE *out /*[ceil(total / per)]*/, TLWE *in /*[total]*/, uint64_t total, uint64_t per, TRLWE_KS_Key key, int split);
 
+/* trlwe_extract_tlwe (src/trlwe.c:540-552) over a batch in one call (new; mosfhet_hip_trlwe_unpack_batch), the inverse layout of mosfhet_tlwe_pack: out[o per + j] =
+ * extract(in[o], j) for o < ceil(total / per), 1 <= per <= N, of dimension N; the last input may be opened in part.  Synchronous; aborts on error; primary device. */
+void mosfhet_trlwe_unpack(TLWE *out /*[total]*/, TRLWE *in /*[ceil(total / per)]*/, uint64_t total, uint64_t per);
+/* ... and tlwe_keyswitch (src/tlwe.c:289-303; ksk: N -> n, what tlwe_new_KS_key returns) of every extracted sample in the same call (new;
+ * mosfhet_hip_trlwe_unpack_keyswitch_batch): out[j] of dimension n, the same words as the two steps one after the other. */
+void mosfhet_trlwe_unpack_keyswitch(TLWE *out /*[total]*/, TRLWE *in /*[ceil(total / per)]*/, uint64_t total, uint64_t per, TLWE_KS_Key ksk);
+
 /* ---- flat helpers used by the Python binding and bench.py (new) ----
  * Generate a whole bootstrap / key-switch key in the flat torus-domain layouts of mosfhet_hip.h. */
 void mosfhet_gen_bootstrap_key_flat(Torus *out /*[n][(k+1)l][k+1][N]*/, TRGSW_Key out_key, TLWE_Key in_key);

@@ -508,6 +508,32 @@ int mosfhet_hip_tlwe_pack_batch(mosfhet_hip_ctx_t ctx, mosfhet_hip_gak_t pk, uin
 int mosfhet_hip_tlwe_pack_plan(int N, int n_in, int t, int total, int per, int split /*0: recommend*/, int cus, long long workspace_bytes, long long plan[8]);
 int mosfhet_hip_set_tlwe_pack_workspace(long long bytes);
 
+/* ---- packed TRLWE samples opened into batches of LWE samples: trlwe_extract_tlwe (src/trlwe.c:540-552, k = 1) over a batch, the inverse layout of tlwe_pack ----
+ *   d_in [outputs][2][N] -> [total] samples, outputs = ceil(total / per), 1 <= per <= N, N a power of two in 256 .. 4096: sample o per + j is
+ *   trlwe_extract_tlwe(in[o], j), word for word: a[i] = in[o].a[j - i] for i <= j, -in[o].a[N + j - i] above, b = in[o].b[j].  The last input may be opened in part.
+ * Pure integer work: the words depend on d_in, per and the index only.
+ * mosfhet_hip_trlwe_unpack_batch writes the batch d_out [total][N + 1]; rows from `total` on are not touched.  Asynchronous on `stream`, never synchronises, allocates
+ * nothing, capturable from the first call.
+ * mosfhet_hip_trlwe_unpack_keyswitch_batch: every word equals mosfhet_hip_tlwe_keyswitch_batch applied to that batch, which is never written -- the pre-pass of the
+ * table key switch (the transposition of the tiles, the digit entries of the word-lane form) reads the packed words directly.  ksk: an LWE -> LWE key with n_in == N
+ * (stored or seed-compressed); a packing key, a key of another ring or of another context is refused.  No word depends on the form that ran, on total, on the piece
+ * boundaries or on mosfhet_hip_set_ks_words.  Up to 16 samples are unpacked into the calling thread's pool and take the direct kernels.
+ * mosfhet_hip_unpack_keyswitch_functional_bootstrap_batch: that call followed by the body of mosfhet_hip_keyswitch_functional_bootstrap_batch on the `total` switched
+ * samples (k = 1) -- the same scratch, the same words as the two calls one after the other.
+ * Both: asynchronous, temporaries in the key-switch workspace of the calling thread (ONE STREAM PER HOST THREAD at a time), capturable once a call of the same size
+ * has run.  total == 0 is OK.  d_out must not overlap d_in.
+ * mosfhet_hip_trlwe_unpack_plan says what the launchers will do, as a pure function (no GPU; n_out = 0 asks about mosfhet_hip_trlwe_unpack_batch alone):
+ * plan = { outputs, form of the switch (0: up to 16 samples, unpacked first; 1: word-lane; 2: tiles of 256; 3: tiles of 512 -- launch_tlwe_keyswitch's own decision at
+ *          the current mosfhet_hip_set_ks_words), pieces (word-lane: ceil(total / 8192)), workgroups of the source pre-pass, bytes the pre-pass writes, bytes of the
+ *          [total][N + 1] batch that is not written, pool bytes used, samples per workgroup of mosfhet_hip_trlwe_unpack_batch's kernel }. */
+int mosfhet_hip_trlwe_unpack_batch(mosfhet_hip_ctx_t ctx, uint64_t *d_out /*[total][N+1]*/, const uint64_t *d_in /*[outputs][2][N]*/, int N, int total, int per, void *stream);
+int mosfhet_hip_trlwe_unpack_keyswitch_batch(mosfhet_hip_ctx_t ctx, mosfhet_hip_ksk_t ksk, uint64_t *d_out /*[total][n_out+1]*/, const uint64_t *d_in /*[outputs][2][N]*/,
+                                             int total, int per, void *stream);
+int mosfhet_hip_unpack_keyswitch_functional_bootstrap_batch(mosfhet_hip_ctx_t ctx, mosfhet_hip_ksk_t ksk, mosfhet_hip_bsk_t bsk, uint64_t *d_out, const uint64_t *d_tv,
+                                                            int tv_count, const uint64_t *d_in /*[outputs][2][N]*/, int total, int per, int torus_base, int extract,
+                                                            void *stream);
+int mosfhet_hip_trlwe_unpack_plan(int N, int n_out, int t, int base_bit, int compressed, int total, int per, int cus, long long plan[8]);
+
 /* CMUX over a batch with one shared selector = entry `key_index` of a key handle (e.g. circuit-bootstrap outputs turned into a handle by
  * mosfhet_hip_bsk_create_from_device): d_out[b] = d_in0[b] + key (.) (d_in1[b] - d_in0[b]); d_out may alias d_in0.  The leveled caller of
  * the path (applications/leveled_lut/vertical_packing.c:24-52: CMUX tree, then blind_rotate with the selectors as key). */

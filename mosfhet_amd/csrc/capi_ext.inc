@@ -114,7 +114,7 @@ extern "C" int mosfhet_hip_full_domain_functional_bootstrap_KS21_batch(mosfhet_h
   };
   if (variant == 0) {
     const int slot_size = N / (l * half_base);
-    hipLaunchKernelGGL(ks21_sign_lut_kernel, dim3((N + 255) / 256), dim3(256), 0, s, tv_sign, N, l, Bg, half_base);
+    hipLaunchKernelGGL(ks21_sign_lut_kernel, dim3((N + 255) / 256), dim3(256), 0, s, tv_sign, N, l, Bg, half_base, (uint64_t *)nullptr, (uint64_t *)nullptr);
     if ((rc = mosfhet_hip_functional_bootstrap_wo_extract_batch(ctx, bsk, acc, tv_sign, 1, d_in, count, l * half_base, stream))) return rc;
     for (int i = 0; i < l; i++) {
       const uint64_t sign = ~0ull << (64 - (i + 1) * Bg - 1);
@@ -144,7 +144,7 @@ extern "C" int mosfhet_hip_full_domain_functional_bootstrap_KS21_batch(mosfhet_h
   }
   if (together)   // all l count samples at once: sample b l + i lands on selector row (b, i)
     HIP_TRY(launch_tlwe_keyswitch(pksk->d_ksk, sel, row, ext, (size_t)N + 1, l * count, N, 2 * N, N, pksk->t, pksk->base_bit, tl_ws(ctx->device), s, pksk->compressed, pksk->seed));
-  hipLaunchKernelGGL(ks21_split_tv_kernel, dim3((N + 255) / 256), dim3(256), 0, s, d_tv, p0, p1, N);
+  hipLaunchKernelGGL(ks21_sign_lut_kernel, dim3((N + 255) / 256), dim3(256), 0, s, const_cast<uint64_t *>(d_tv), N, l, Bg, half_base, p0, p1);   // (p0 given: d_tv is only read)
   if ((rc = launch_public_mux(ctx, tv2, row, p0, p1, sel, (size_t)l * row, dec, (d2 *)pdec, N, l, Bg, count, s))) return rc;
   return mosfhet_hip_functional_bootstrap_batch(ctx, bsk, d_out, tv2, count, d_in, count, half_base, stream);
 }

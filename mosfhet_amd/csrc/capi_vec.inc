@@ -48,11 +48,16 @@ __global__ void lut_level_slots_kernel(uint64_t *__restrict__ dst, const uint64_
 
 // packing-switch inputs of the comparison (src/integer.c:216-245): per integer m the B slots of its LUT.  mode 0: slot 0 = the running result c0[m], the others the
 // trivial sample `one`; mode 1 (sign steps): slots below B / 2 = c0[m], the others -c0[m].  dst [M][B][row]
-__global__ void cmp_slots_kernel(uint64_t *__restrict__ dst, const uint64_t *__restrict__ c0, size_t M, int B, int row, int mode, uint64_t one) {
+// ... and of the product tables (src/integer.c:183-196), modes 2 and 3: the B slots [0, c0[m] (mode 2) or 0 (mode 3), v_2[m], .., v_{B-1}[m]]; vals [B-2][M][row]
+__global__ void cmp_slots_kernel(uint64_t *__restrict__ dst, const uint64_t *__restrict__ c0, const uint64_t *__restrict__ vals, size_t M, int B, int row, int mode, uint64_t one) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const size_t total = M * (size_t)B * row;
   if (i >= total) return;
   const size_t w = i % row, q = (i / row) % B, m = i / ((size_t)row * B);
+  if (mode >= 2) {
+    dst[i] = q == 0 ? 0 : (q == 1 ? (mode == 2 ? c0[m * row + w] : 0) : vals[((q - 2) * M + m) * row + w]);
+    return;
+  }
   const uint64_t c = c0[m * row + w];
   if (mode == 0) dst[i] = q == 0 ? c : (w == (size_t)row - 1 ? one : 0);
   else dst[i] = q < (size_t)B / 2 ? c : (uint64_t)0 - c;
@@ -258,7 +263,7 @@ extern "C" int mosfhet_hip_vec_cmp(mosfhet_hip_vec_t vec, uint64_t *d_c, const u
   auto step = [&](const uint64_t *selector_N, int mode) -> int {   // c <- LUT_c[selector]
     int r2;
     if ((r2 = mosfhet_hip_tlwe_keyswitch_batch(ctx, vec->ksk, sel, selector_N, M, stream))) return r2;
-    hipLaunchKernelGGL(cmp_slots_kernel, dim3(g_slots), dim3(256), 0, s, slots, d_c, (size_t)M, B, row, mode, one);
+    hipLaunchKernelGGL(cmp_slots_kernel, dim3(g_slots), dim3(256), 0, s, slots, d_c, (const uint64_t *)nullptr, (size_t)M, B, row, mode, one);
     if ((r2 = mosfhet_hip_trlwe_lut_packing_keyswitch_batch(ctx, vec->pksk, B, tvs, slots, M, stream))) return r2;
     return mosfhet_hip_functional_bootstrap_batch(ctx, vec->bsk, d_c, tvs, M, sel, M, B, stream);
   };
@@ -313,15 +318,6 @@ extern "C" int mosfhet_hip_vec_lut_cleartext(mosfhet_hip_vec_t vec, uint64_t *d_
 }
 
 // ---- shifted additions and the multiplication (ufhe_sl_add_integer, ufhe_sl_addto_integer, ufhe_extend_integer, ufhe_mul_integer: src/integer.c:64-77,79-134,166-203) ----
-// packing-switch inputs of the product tables (src/integer.c:183-196): per integer m the B slots [0, x_m or 0, v_2[m], .., v_{B-1}[m]]; vals [B-2][M][row]
-__global__ void mul_slots_kernel(uint64_t *__restrict__ dst, const uint64_t *__restrict__ x, const uint64_t *__restrict__ vals, size_t M, int B, int row, int with_x) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const size_t total = M * (size_t)B * row;
-  if (i >= total) return;
-  const size_t w = i % row, q = (i / row) % B, m = i / ((size_t)row * B);
-  dst[i] = q == 0 ? 0 : (q == 1 ? (with_x ? x[m * row + w] : 0) : vals[((q - 2) * M + m) * row + w]);
-}
-
 // one carry step on digit plane c_i (ufhe_sl_add_integer's loop body, src/integer.c:94-104): c_i <- c_i reduced mod B, its carry into c_next (set = 1: c_next starts
 // from the trivial 1/(4B), sl_add; set = 0: 1/(4B) is added to what c_next holds, sl_addto).  rot: [M][2][N] scratch.
 static int vec_carry_step(mosfhet_hip_vec_t vec, uint64_t *c_i, uint64_t *c_next, int set, uint64_t *rot, int M, void *stream) {
@@ -472,7 +468,7 @@ extern "C" int mosfhet_hip_vec_mul(mosfhet_hip_vec_t vec, uint64_t *d_c, int dc,
         for (int q = 0; q < B; q++) mat[q] = which ? (j * q) / B : (j * q) % B;   // row j of the matrices of src/ufhe.c:84-93
         if ((rc = mosfhet_hip_multivalue_bootstrap_phase2_batch(ctx, vals + (size_t)(j - 2) * plane, mat.data(), rot, N, B, logB, M, stream))) return rc;
       }
-      hipLaunchKernelGGL(mul_slots_kernel, dim3((unsigned)((w_slots + 255) / 256)), dim3(256), 0, s, slots, a_i, vals, (size_t)M, B, row, which == 0);
+      hipLaunchKernelGGL(cmp_slots_kernel, dim3((unsigned)((w_slots + 255) / 256)), dim3(256), 0, s, slots, a_i, vals, (size_t)M, B, row, which == 0 ? 2 : 3, (uint64_t)0);
       if ((rc = mosfhet_hip_trlwe_lut_packing_keyswitch_batch(ctx, vec->pksk, B, tv + (size_t)which * M * 2 * N, slots, M, stream))) return rc;
       // every digit of b against its integer's table: the M tables tiled db times, one launch
       for (int j = 0; j < db; j++)

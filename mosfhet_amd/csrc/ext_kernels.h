@@ -84,18 +84,14 @@ __global__ __launch_bounds__(F::THREADS, 2) void public_mux_kernel(const uint64_
 
 // test vector of full_domain_functional_bootstrap_KS21 [src/bootstrap.c:399-404]: l interleaved LUTs of torus_base/2 slots,
 // LUT j constant -2^(63 - (j+1) Bg)  (trlwe_torus_packing_many_LUT, src/trlwe.c:677-687)
-__global__ void ks21_sign_lut_kernel(uint64_t *__restrict__ tv, int N, int l, int Bg_bit, int half_base) {
+// p0 != nullptr: the split of a caller's test vector instead, p0[i] = tv[i], p1[i] = -tv[i + N]  [src/bootstrap.c:417-421] (tv is only read)
+__global__ void ks21_sign_lut_kernel(uint64_t *__restrict__ tv, int N, int l, int Bg_bit, int half_base, uint64_t *__restrict__ p0, uint64_t *__restrict__ p1) {
   const int x = blockIdx.x * blockDim.x + threadIdx.x;
   if (x >= N) return;
+  if (p0) { p0[x] = tv[x]; p1[x] = 0 - tv[N + x]; return; }
   const int span = N / (half_base * l), idx = x / span, j = idx % l;   // integer division as the reference: a tail stays zero
   tv[x] = 0;
   tv[N + x] = idx < half_base * l ? ~0ull << (64 - (j + 1) * Bg_bit - 1) : 0;
-}
-
-// p0[i] = tv[i], p1[i] = -tv[i + N]  [src/bootstrap.c:417-421]
-__global__ void ks21_split_tv_kernel(const uint64_t *__restrict__ tv, uint64_t *__restrict__ p0, uint64_t *__restrict__ p1, int N) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < N) { p0[i] = tv[i]; p1[i] = 0 - tv[N + i]; }
 }
 
 // trivial TRGSW(1) [src/trgsw.c:130-142]: row q < l carries 2^(64-(q+1)Bg) on a[0], row l + q on b[0]; grid = (2N / 256, 2l)

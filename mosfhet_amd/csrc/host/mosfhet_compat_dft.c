@@ -495,6 +495,43 @@ void mosfhet_tlwe_pack(TRLWE *out, TLWE *in, uint64_t total, uint64_t per, TRLWE
   mc_hstage_free(h);
 }
 
+/* trlwe_extract_tlwe (src/trlwe.c:540-552) over a batch in one call (mosfhet_hip_trlwe_unpack_batch), the inverse layout of mosfhet_tlwe_pack: out[o per + j] =
+ * extract(in[o], j); with a key, tlwe_keyswitch of every extracted sample as well (mosfhet_hip_trlwe_unpack_keyswitch_batch: the batch of N + 1 words per sample is
+ * never written). */
+static void trlwe_unpack(const char *name, TLWE *out, TRLWE *in, uint64_t total, uint64_t per, TLWE_KS_Key ksk) {
+  const int N = in[0]->b->N, n_res = ksk ? out[0]->n : N;
+  const size_t inputs = (size_t)((total + per - 1) / per);
+  const size_t in_w = inputs * 2 * (size_t)N, out_w = (size_t)total * ((size_t)n_res + 1);
+  Torus *h = (Torus *)mc_hstage_alloc(sizeof(Torus) * (in_w > out_w ? in_w : out_w)), *d = (Torus *)mc_stage_alloc(sizeof(Torus) * (in_w + out_w));
+  for (size_t o = 0; o < inputs; o++) {
+    need_of(in[o]->k == 1 && in[o]->b->N == N, name, "an input is not a k = 1 TRLWE sample of the first input's ring");
+    mc_trlwe_to_flat(h + o * 2 * (size_t)N, in[o]);
+  }
+  mc_dev_copy(d, h, sizeof(Torus) * in_w, HIP_H2D);
+  if (ksk)
+    check_rc(mosfhet_hip_trlwe_unpack_keyswitch_batch(ectx(), (mosfhet_hip_ksk_t)mc_key_here(ksk->device, MC_KEY_KSK), d + in_w, d, (int)total, (int)per, NULL), name);
+  else
+    check_rc(mosfhet_hip_trlwe_unpack_batch(ectx(), d + in_w, d, N, (int)total, (int)per, NULL), name);
+  mc_dev_copy(h, d + in_w, sizeof(Torus) * out_w, HIP_D2H);
+  for (uint64_t j = 0; j < total; j++) {
+    const Torus *w = h + (size_t)j * ((size_t)n_res + 1);
+    need_of(out[j]->n == n_res, name, "an output sample has the wrong dimension (N without a key, the key's output dimension with one)");
+    memcpy(out[j]->a, w, sizeof(Torus) * (size_t)n_res);
+    out[j]->b = w[n_res];
+  }
+  mc_hstage_free(h);
+}
+
+void mosfhet_trlwe_unpack(TLWE *out, TRLWE *in, uint64_t total, uint64_t per) {
+  need(out && in && total >= 1 && total <= 0x7fffffffu && per >= 1 && per <= 4096, "mosfhet_trlwe_unpack: bad argument");
+  trlwe_unpack("mosfhet_trlwe_unpack", out, in, total, per, NULL);
+}
+
+void mosfhet_trlwe_unpack_keyswitch(TLWE *out, TRLWE *in, uint64_t total, uint64_t per, TLWE_KS_Key ksk) {
+  need(out && in && ksk && ksk->device && total >= 1 && total <= 0x7fffffffu && per >= 1 && per <= 4096, "mosfhet_trlwe_unpack_keyswitch: bad argument");
+  trlwe_unpack("mosfhet_trlwe_unpack_keyswitch", out, in, total, per, ksk);
+}
+
 /* src/trlwe.c:775-781: out = KeySwitch_{ks_key}(in(X^gen)); ks_key switches from key(X^gen) back to key (any entry of a key set) */
 void trlwe_eval_automorphism(TRLWE out, TRLWE in, uint64_t gen, TRLWE_KS_Key ks_key) {
   const int N = in->b->N;

@@ -22,8 +22,25 @@
 #include <stdint.h>
 
 #include "keygen_kernels.h"
+#include "unpack_kernels.h"
 
 namespace mosfhet {
+
+// Where a table key switch reads its ciphertexts.  Plain: rows of words, `in_stride` apart.  Packed (packed != nullptr): TRLWE samples [..][2][N]; ciphertext c
+// is sample (first + c) % per of input (first + c) / per (unpack_kernels.h) -- the kernels that re-orient the input read the packed words directly.
+struct KsSource {
+  const uint64_t *in = nullptr;
+  size_t in_stride = 0;
+  const uint64_t *packed = nullptr;
+  int N = 0, per = 1, first = 0;
+  static KsSource rows(const uint64_t *in, size_t in_stride) { KsSource s; s.in = in; s.in_stride = in_stride; return s; }
+  static KsSource trlwe(const uint64_t *packed, int N, int per, int first) { KsSource s; s.packed = packed; s.N = N; s.per = per; s.first = first; return s; }
+  KsSource from(int c) const {   // the source of ciphertexts c, c + 1, ...
+    KsSource s = *this;
+    if (packed) s.first = first + c; else s.in = in + (size_t)c * in_stride;
+    return s;
+  }
+};
 
 // out[c][r] = sum_{s < parts} in[s * part_stride + r * ldin + c] for an R x C matrix of 64-bit words (leading
 // dimensions ldin / ldout; parts = 1: plain transpose); out rows c >= C and columns r >= R are not touched.
@@ -223,7 +240,7 @@ struct KsWorkspace {
 // Returns hipSuccess or the failing error.  ws is grown on demand (kept by the key handle between calls).
 // in: rows of n_in + 1 words (n_in when b_word < 0) spaced in_stride words apart; out: rows of `row` words spaced out_stride apart.
 template <int NW>
-inline hipError_t launch_tlwe_keyswitch_nw(const uint64_t *ksk, uint64_t *out, size_t out_stride, const uint64_t *in, size_t in_stride, int count,
+inline hipError_t launch_tlwe_keyswitch_nw(const uint64_t *ksk, uint64_t *out, size_t out_stride, const KsSource &src, int count,
                                            int n_in, int row, int b_word, int t, int base_bit, KsWorkspace &ws, hipStream_t s, bool compressed,
                                            uint64_t seed, int mask_words) {
   constexpr int W = KS_W, TILE = 64 * NW;
@@ -257,9 +274,13 @@ inline hipError_t launch_tlwe_keyswitch_nw(const uint64_t *ksk, uint64_t *out, s
     ws.words_out = need_out;
   }
   if (Bp != (size_t)count && (e = hipMemsetAsync(ws.inT, 0, need_in * sizeof(uint64_t), s)) != hipSuccess) return e;
-  // in[count][n_in + 1] -> inT[n_in + 1][Bp]
-  hipLaunchKernelGGL(transpose_u64_kernel, dim3((in_words + 31) / 32, (count + 31) / 32), dim3(32, 8), 0, s, in, ws.inT, count, in_words,
-                     in_stride, Bp, 1, (size_t)0);
+  // in[count][n_in + 1] -> inT[n_in + 1][Bp]; from packed samples inT is written directly, column by column (n_in = N, the b word is row N)
+  if (src.packed)
+    hipLaunchKernelGGL(trlwe_unpack_kernel, dim3((unsigned)((count + UNPACK_THREADS - 1) / UNPACK_THREADS), (unsigned)((in_words + UNPACK_COL_WORDS - 1) / UNPACK_COL_WORDS)),
+                       dim3(UNPACK_THREADS), 0, s, ws.inT, src.packed, src.N, src.per, src.first, count, (size_t)1, Bp, 0);
+  else
+    hipLaunchKernelGGL(transpose_u64_kernel, dim3((in_words + 31) / 32, (count + 31) / 32), dim3(32, 8), 0, s, src.in, ws.inT, count, in_words,
+                       src.in_stride, Bp, 1, (size_t)0);
   const int cands = (1 << base_bit) - 1;
   // LDS per buffer = digit positions per stage (one barrier per stage).  Small digit sets (base_bit 2) take all of an input word's positions in
   // one stage; base_bit 3 and 4 take TWO positions per stage (same-box sweep with the 512-ciphertext tile: packing switch 5.00 -> 4.40 ms per 1024
@@ -426,25 +447,46 @@ inline hipError_t launch_tlwe_keyswitch_scaled(const uint64_t *ksk, uint64_t *ou
 #include "keyswitch_words_kernels.h"   // the other orientation (output words on the lanes): launch_tlwe_keyswitch_words
 namespace mosfhet {
 
-// Tile of 256 ciphertexts per workgroup for small digit sets (the table is cache resident), 512 for base_bit >= 3, where the
-// multi-gigabyte table is re-read once per tile (packing switch 5.3 -> 4.9 ms, lvl2 LWE switch 4.45 -> 4.16 ms; SET_1 prefers 256).
+// Which form a table key switch of `count` ciphertexts takes -- the one decision of launch_tlwe_keyswitch, also what mosfhet_hip_trlwe_unpack_plan reports:
+// 0 the direct kernels of few ciphertexts, 1 output words on the lanes, 2 tiles of 256 ciphertexts, 3 tiles of 512.
+enum { KS_FORM_SMALL = 0, KS_FORM_WORDS = 1, KS_FORM_TILES_256 = 2, KS_FORM_TILES_512 = 3 };
+inline int ks_form(int count, int n_in, int row, int t, int base_bit, bool compressed, int mask_words) {
+  // up to this many ciphertexts take the direct form (MOSFHET_KS_SMALL_MAX overrides, 0 disables): beyond it the tiled kernel's one pass over the table wins
+  static const int small_max = getenv("MOSFHET_KS_SMALL_MAX") ? atoi(getenv("MOSFHET_KS_SMALL_MAX")) : 16;
+  if (count <= small_max) return KS_FORM_SMALL;
+  // digit sets of at most 15 candidates: output words on the lanes, wave-uniform digits (keyswitch_words_kernels.h; MOSFHET_HIP_KS_WORDS / mosfhet_hip_set_ks_words: 0 = the LDS-gather tiles below)
+  if (ks_words_applies(count, n_in, row, t, base_bit, compressed, mask_words)) return KS_FORM_WORDS;
+  // Tile of 256 ciphertexts per workgroup for small digit sets (the table is cache resident), 512 for base_bit >= 3, where the
+  // multi-gigabyte table is re-read once per tile (packing switch 5.3 -> 4.9 ms, lvl2 LWE switch 4.45 -> 4.16 ms; SET_1 prefers 256).
+  // (up to 256 ciphertexts one 256-wide tile holds them all: the 512-wide tile's extra wavefronts would only stage rows -- +15 % on circuit bootstraps of
+  // 64 - 256 ciphertexts, the shape of a batch of 1024 split over 8 GPUs)
+  if (base_bit >= 3 && (count > 256 || base_bit > 4)) return KS_FORM_TILES_512;   // (wider digits need the 512-thread tile's staging width)
+  return KS_FORM_TILES_256;
+}
+// compressed keys: TRLWE rows (b_word = N or none) keep their b polynomial, LWE rows (b_word = row - 1) their one b word
+inline int ks_mask_words(bool compressed, int row, int b_word) { return !compressed ? 0 : (b_word == row - 1 ? row - 1 : row / 2); }
+
+// A packed source takes every form but the direct one, which walks no table and re-orients nothing: its caller unpacks first (capi_unpack.inc).
+inline hipError_t launch_tlwe_keyswitch(const uint64_t *ksk, uint64_t *out, size_t out_stride, const KsSource &src, int count,
+                                        int n_in, int row, int b_word, int t, int base_bit, KsWorkspace &ws, hipStream_t s, bool compressed = false,
+                                        uint64_t seed = 0) {
+  const int mask_words = ks_mask_words(compressed, row, b_word);
+  switch (ks_form(count, n_in, row, t, base_bit, compressed, mask_words)) {
+    case KS_FORM_SMALL:
+      if (src.packed) return hipErrorInvalidValue;
+      return launch_tlwe_keyswitch_small(ksk, out, out_stride, src.in, src.in_stride, count, n_in, row, b_word, t, base_bit, ws, s, compressed, seed, mask_words);
+    case KS_FORM_WORDS:
+      return launch_tlwe_keyswitch_words(ksk, out, out_stride, src, count, n_in, row, b_word, t, base_bit, ws, s, compressed, seed, mask_words);
+    case KS_FORM_TILES_512:
+      return launch_tlwe_keyswitch_nw<8>(ksk, out, out_stride, src, count, n_in, row, b_word, t, base_bit, ws, s, compressed, seed, mask_words);
+    default:
+      return launch_tlwe_keyswitch_nw<KS_NW>(ksk, out, out_stride, src, count, n_in, row, b_word, t, base_bit, ws, s, compressed, seed, mask_words);
+  }
+}
 inline hipError_t launch_tlwe_keyswitch(const uint64_t *ksk, uint64_t *out, size_t out_stride, const uint64_t *in, size_t in_stride, int count,
                                         int n_in, int row, int b_word, int t, int base_bit, KsWorkspace &ws, hipStream_t s, bool compressed = false,
                                         uint64_t seed = 0) {
-  // compressed keys: TRLWE rows (b_word = N or none) keep their b polynomial, LWE rows (b_word = row - 1) their one b word
-  const int mask_words = !compressed ? 0 : (b_word == row - 1 ? row - 1 : row / 2);
-  // up to this many ciphertexts take the direct form (MOSFHET_KS_SMALL_MAX overrides, 0 disables): beyond it the tiled kernel's one pass over the table wins
-  static const int small_max = getenv("MOSFHET_KS_SMALL_MAX") ? atoi(getenv("MOSFHET_KS_SMALL_MAX")) : 16;
-  if (count <= small_max)
-    return launch_tlwe_keyswitch_small(ksk, out, out_stride, in, in_stride, count, n_in, row, b_word, t, base_bit, ws, s, compressed, seed, mask_words);
-  // digit sets of at most 15 candidates: output words on the lanes, wave-uniform digits (keyswitch_words_kernels.h; MOSFHET_HIP_KS_WORDS / mosfhet_hip_set_ks_words: 0 = the LDS-gather tiles below)
-  if (ks_words_applies(count, n_in, row, t, base_bit, compressed, mask_words))
-    return launch_tlwe_keyswitch_words(ksk, out, out_stride, in, in_stride, count, n_in, row, b_word, t, base_bit, ws, s, compressed, seed, mask_words);
-  // (up to 256 ciphertexts one 256-wide tile holds them all: the 512-wide tile's extra wavefronts would only stage rows -- +15 % on circuit bootstraps of
-  // 64 - 256 ciphertexts, the shape of a batch of 1024 split over 8 GPUs)
-  if (base_bit >= 3 && (count > 256 || base_bit > 4))   // (wider digits need the 512-thread tile's staging width)
-    return launch_tlwe_keyswitch_nw<8>(ksk, out, out_stride, in, in_stride, count, n_in, row, b_word, t, base_bit, ws, s, compressed, seed, mask_words);
-  return launch_tlwe_keyswitch_nw<KS_NW>(ksk, out, out_stride, in, in_stride, count, n_in, row, b_word, t, base_bit, ws, s, compressed, seed, mask_words);
+  return launch_tlwe_keyswitch(ksk, out, out_stride, KsSource::rows(in, in_stride), count, n_in, row, b_word, t, base_bit, ws, s, compressed, seed);
 }
 
 }  // namespace mosfhet

@@ -181,6 +181,21 @@ def set_tlwe_pack_workspace(nbytes):
     _check(lib().mosfhet_hip_set_tlwe_pack_workspace(C.c_longlong(int(nbytes))))
 
 
+KS_FORMS = ("small", "words", "tiles_256", "tiles_512")
+
+
+def trlwe_unpack_plan(N, n_out=0, t=0, base_bit=0, total=0, per=None, compressed=False, cus=256):
+    """What a trlwe_unpack (n_out = 0) or trlwe_unpack_keyswitch call will do (no device needed; the launchers' own decision at the current set_ks_words):
+    dict(outputs, form, pieces, prepass_workgroups, prepass_bytes, saved_bytes, pool_bytes, rows_per_workgroup) -- packed inputs read, form of the switch ("small":
+    up to 16 samples, unpacked first; "words"; "tiles_256"; "tiles_512"), pieces (ceil(total / 8192) for "words"), workgroups and written bytes of the pre-pass that
+    reads the packed samples, bytes of the [total][N + 1] batch that is never written, pool bytes and samples per workgroup of trlwe_unpack's kernel.
+    include/mosfhet_hip.h: mosfhet_hip_trlwe_unpack_plan."""
+    plan = (C.c_longlong * 8)()
+    _check(lib().mosfhet_hip_trlwe_unpack_plan(int(N), int(n_out), int(t), int(base_bit), int(bool(compressed)), int(total), int(N if per is None else per), int(cus), plan))
+    return dict(outputs=int(plan[0]), form=KS_FORMS[plan[1]], pieces=int(plan[2]), prepass_workgroups=int(plan[3]), prepass_bytes=int(plan[4]), saved_bytes=int(plan[5]),
+                pool_bytes=int(plan[6]), rows_per_workgroup=int(plan[7]))
+
+
 class LinearMap:
     """The cleartext weights of y = W x + bias on the device (mosfhet_hip_linear_t): made by Engine.linear_dense / Engine.linear_sparse."""
 
@@ -995,6 +1010,44 @@ class Engine:
         if out is None:
             out = self.empty(-(-total // per) if per >= 1 else 0, 2, pk.N)
         _check(lib().mosfhet_hip_tlwe_pack_batch(self.h, pk.h, _ptr(out) if total else None, _ptr(ct) if total else None, int(total), per, int(split), self._stream()))
+        return out
+
+    # ---- packed TRLWE samples opened into LWE batches (include/mosfhet_hip.h: mosfhet_hip_trlwe_unpack_batch) ----
+    def _unpack_shape(self, trlwe, total, per, ksk=None):
+        outputs, two, N = trlwe.shape
+        assert two == 2
+        if ksk is not None and ksk.n_in != N:   # (the C call takes N from the key: it cannot see the tensor's)
+            raise MosfhetHipError("trlwe_unpack_keyswitch: the key switches from n_in = %d words, the packed samples have N = %d" % (ksk.n_in, N))
+        per = N if per is None else int(per)
+        total = outputs * per if total is None else int(total)
+        assert total <= outputs * per, "total = %d: %d packed samples of %d hold %d" % (total, outputs, per, outputs * per)
+        return N, total, per
+
+    def trlwe_unpack(self, trlwe, total=None, per=None, out=None):
+        """trlwe_extract_tlwe over a batch, the inverse layout of tlwe_pack: trlwe [outputs][2][N] -> [total][N + 1], sample o per + j = extract(trlwe[o], j); per
+        defaults to N, total to outputs * per."""
+        N, total, per = self._unpack_shape(trlwe, total, per)
+        if out is None:
+            out = self.empty(max(total, 0), N + 1)
+        _check(lib().mosfhet_hip_trlwe_unpack_batch(self.h, _ptr(out) if total else None, _ptr(trlwe) if total else None, N, total, per, self._stream()))
+        return out
+
+    def trlwe_unpack_keyswitch(self, ksk, trlwe, total, per, out=None):
+        """tlwe_keyswitch of trlwe_unpack's samples without writing them: trlwe [outputs][2][N] -> [total][n_out + 1]; ksk an LWE -> LWE key with n_in == N."""
+        N, total, per = self._unpack_shape(trlwe, total, per, ksk)
+        if out is None:
+            out = self.empty(max(total, 0), ksk.n_out + 1)
+        _check(lib().mosfhet_hip_trlwe_unpack_keyswitch_batch(self.h, ksk.h, _ptr(out) if total else None, _ptr(trlwe) if total else None, total, per, self._stream()))
+        return out
+
+    def unpack_keyswitch_functional_bootstrap(self, ksk, bsk, tv, trlwe, total, per, torus_base, extract=True, out=None):
+        """trlwe_unpack_keyswitch followed by functional_bootstrap[_wo_extract] in one call: trlwe [outputs][2][N] -> [total][N + 1] (extract) or [total][2][N]; tv one
+        test vector or one per sample."""
+        N, total, per = self._unpack_shape(trlwe, total, per, ksk)
+        if out is None:
+            out = self.empty(max(total, 0), bsk.N + 1) if extract else self.empty(max(total, 0), 2, bsk.N)
+        _check(lib().mosfhet_hip_unpack_keyswitch_functional_bootstrap_batch(self.h, ksk.h, bsk.h, _ptr(out) if total else None, _ptr(tv), self._tv(tv, bsk, total),
+                                                                             _ptr(trlwe) if total else None, total, per, torus_base, int(extract), self._stream()))
         return out
 
     # ---- key switch ----

@@ -19,7 +19,9 @@ def shard_bounds(count, rank, world):
 def shard_bounds_whole(count, unit, rank, world):
     """shard_bounds for work that is cut at multiples of `unit` only: the ceil(count / unit) groups are dealt like shard_bounds deals units and the slice is
     returned in units, the last group possibly short.  Packing LWE samples into TRLWE samples (Engine.tlwe_pack) shards this way with unit = per: every rank
-    packs whole outputs, so the outputs of the ranks, concatenated, are the outputs of the unsharded call."""
+    packs whole outputs, so the outputs of the ranks, concatenated, are the outputs of the unsharded call.  Opening packed samples (Engine.trlwe_unpack,
+    trlwe_unpack_keyswitch, unpack_keyswitch_functional_bootstrap) shards the same way: rank r reads the packed inputs lo / per .. ceil(hi / per) - 1 whole and its
+    samples, concatenated with the other ranks', are the unsharded call's."""
     assert unit >= 1
     lo, hi = shard_bounds(-(-count // unit), rank, world)
     return min(count, lo * unit), min(count, hi * unit)
