@@ -326,6 +326,11 @@ void mosfhet_tlwe_linear_bootstrap_inputs(TLWE **out /*[count][rows_out]*/, TLWE
  * Synchronous; aborts on error; primary device. */
 void mosfhet_tlwe_pack(TRLWE *out /*[ceil(total / per)]*/, TLWE *in /*[total]*/, uint64_t total, uint64_t per, TRLWE_KS_Key key, int split);
 
+/* trlwe_packing1_keyswitch_CDKS21 (src/keyswitch.c:526-546) over a batch in one call (new; mosfhet_hip_tlwe_trace_pack_batch): out[c] = the trace switch of in[c],
+ * c < count, word for word what `count` single calls give.  ks_key from trlwe_new_packing1_KS_key_CDKS21.  The inputs must lie under the extracted ring key
+ * (trlwe_extract_tlwe_key of the key the set switches to): the phase of out[c] is N m at coefficient 0. */
+void mosfhet_tlwe_trace_pack(TRLWE *out /*[count]*/, TLWE *in /*[count]*/, int count, TRLWE_KS_Key *ks_key);
+
 /* trlwe_extract_tlwe (src/trlwe.c:540-552) over a batch in one call (new; mosfhet_hip_trlwe_unpack_batch), the inverse layout of mosfhet_tlwe_pack: out[o per + j] =
  * extract(in[o], j) for o < ceil(total / per), 1 <= per <= N, of dimension N; the last input may be opened in part.  Synchronous; aborts on error; primary device. */
 void mosfhet_trlwe_unpack(TLWE *out /*[total]*/, TRLWE *in /*[ceil(total / per)]*/, uint64_t total, uint64_t per);

@@ -534,6 +534,40 @@ int mosfhet_hip_unpack_keyswitch_functional_bootstrap_batch(mosfhet_hip_ctx_t ct
                                                             void *stream);
 int mosfhet_hip_trlwe_unpack_plan(int N, int n_out, int t, int base_bit, int compressed, int total, int per, int cus, long long plan[8]);
 
+/* ---- the LWE -> TRLWE switch by the trace and the gadget -> TRGSW conversion over batches (src/keyswitch.c:526-546, 65-97, 559-572) ----
+ * tks: an FFT key-switch key set (mosfhet_hip_trlwe_ksk_create / _generate), any t and base_bit, k = 1, N in {1024, 2048, 4096}; `entry0` names the first entry a call
+ * uses, so that one set can hold several keys.  All three: one launch, asynchronous on `stream`, no allocation, no synchronisation, capturable from the first call;
+ * count == 0 is OK; bad arguments return MOSFHET_HIP_EINVAL before any HIP call.
+ *
+ * mosfhet_hip_tlwe_trace_pack_batch: trlwe_packing1_keyswitch_CDKS21 over a batch, d_in [count][N + 1] -> d_out [count][2][N].  Entries entry0 + j, j < log2 N, switch
+ * from s(X^(N / 2^j + 1)) to s (the order of trlwe_new_packing1_KS_key_CDKS21); the set must hold entry0 + log2 N entries.  Per sample: out = (a', in.b X^0) with
+ * a'[0] = in.a[0], a'[N - i] = -in.a[i]; then for j = 0 .. log2 N - 1: out += KeySwitch_j(out(X^(N / 2^j + 1))), KeySwitch = trlwe_keyswitch.  Every word equals that
+ * sequence made of polynomial_permute, mosfhet_hip_trlwe_keyswitch_batch and an addition (rows 0 .. t - 1 in one chain, one rounding per component and step).
+ * THE INPUT MUST LIE UNDER THE EXTRACTED RING KEY (trlwe_extract_tlwe_key of the key the set switches to) -- what bootstraps write: the trace adds the un-switched
+ * accumulator to its switched image, so a sample under an independent LWE key decrypts to noise.  The phase of the result is N m at coefficient 0 (the trace
+ * multiplies by N) and 0 elsewhere, up to the key-switch noise.  d_out must not overlap d_in.
+ *
+ * mosfhet_hip_trlwe_rlwe_priv_keyswitch_batch: trlwe_RLWE_priv_keyswitch over a batch, [count][2][N] -> [count][2][N]: TRLWE(m) -> TRLWE(m v).  Entry entry0 switches
+ * from s_in v, entry entry0 + 1 from v (trlwe_new_RLWE_priv_KS_key).  out = sum_j dec_j(in.b) KS1_j - sum_j dec_j(in.a) KS0_j: two passes, each with its own
+ * accumulators, inverse transforms and rounding -- the two trlwe_keyswitch calls, the negation and the addition of the reference, word for word.  d_out may be d_in.
+ *
+ * mosfhet_hip_trgsw_from_gadget_batch: trgsw_from_gadget over a batch: d_gadget [count][l][2][N], row i = TRLWE(m 2^(64 - (i + 1) Bg_bit)), -> d_out_dft
+ * [count][2l][2][N/2] complex in the engine's slot order -- the d_sel_dft of the leveled-LUT calls, an entry of a bootstrap key (what mosfhet_hip_bsk_create_from_device makes of the same rows in the torus domain;
+ * mosfhet_hip_bsk_view_create takes it as it is).  Row i < l is
+ * the forward transform of the private switch of gadget row i (the key of v = -s: trlwe_new_gadget_to_RGSW_KS), row l + i that of gadget row i itself, both exactly
+ * as mosfhet_hip_torus_to_dft_batch transforms the torus words; no torus-domain word is written.  1 <= l <= 6; count * l teams.
+ *
+ * mosfhet_hip_trace_plan checks a shape as the calls do, as a pure function (no GPU): kind 0 trace pack, 1 private switch, 2 TRGSW from gadget (l is read for kind 2
+ * only), `entries` what the set holds.  plan = { key entries a team reads, teams of the launch, threads per team, forward transforms per team, inverse transforms per
+ * team, key bytes a team reads }. */
+int mosfhet_hip_tlwe_trace_pack_batch(mosfhet_hip_ctx_t ctx, mosfhet_hip_gak_t tks, int entry0, uint64_t *d_out /*[count][2][N]*/, const uint64_t *d_in /*[count][N+1]*/,
+                                      int count, void *stream);
+int mosfhet_hip_trlwe_rlwe_priv_keyswitch_batch(mosfhet_hip_ctx_t ctx, mosfhet_hip_gak_t tks, int entry0, uint64_t *d_out /*[count][2][N]*/, const uint64_t *d_in, int count,
+                                                void *stream);
+int mosfhet_hip_trgsw_from_gadget_batch(mosfhet_hip_ctx_t ctx, mosfhet_hip_gak_t tks, int entry0, double *d_out_dft /*[count][2l][2][N/2] complex*/,
+                                        const uint64_t *d_gadget /*[count][l][2][N]*/, int l, int count, void *stream);
+int mosfhet_hip_trace_plan(int kind, int N, int t, int base_bit, int entries, int entry0, int l, int count, long long plan[6]);
+
 /* CMUX over a batch with one shared selector = entry `key_index` of a key handle (e.g. circuit-bootstrap outputs turned into a handle by
  * mosfhet_hip_bsk_create_from_device): d_out[b] = d_in0[b] + key (.) (d_in1[b] - d_in0[b]); d_out may alias d_in0.  The leveled caller of
  * the path (applications/leveled_lut/vertical_packing.c:24-52: CMUX tree, then blind_rotate with the selectors as key). */

@@ -1896,48 +1896,40 @@ __global__ __launch_bounds__(F::THREADS, 1) void trlwe_fft_keyswitch_kernel(cons
 
 // trgsw_to_DFT / polynomial_torus_to_DFT for a flat array of polynomials [src/trgsw.c:345-349,
 // src/polynomial.c:368-375]: one team per polynomial, output in slot order [m][thread].
+// inverse != 0: polynomial_DFT_to_torus for a flat array [src/polynomial.c:359-366], in = complex [..][M], out = torus words [..][N] -- the same kernel with the
+// direction named at run time, so that both directions are one instantiation per ring (the kernel table is held below a fixed size: tests/test_host_and_abi.py).
 template <class F>
-__global__ __launch_bounds__(F::THREADS) void torus_to_dft_kernel(const uint64_t *__restrict__ in, d2 *__restrict__ out,
-                                                                const d2 *__restrict__ tw) {
+__global__ __launch_bounds__(F::THREADS) void torus_to_dft_kernel(const void *__restrict__ in, void *__restrict__ out, const d2 *__restrict__ tw, int inverse = 0) {
   constexpr int N = F::N, M = F::M, T = F::THREADS;
   __shared__ __attribute__((aligned(16))) d2 xch[F::XCH_SLOTS];
   const int t = threadIdx.x;
-  const uint64_t *src = in + (size_t)blockIdx.x * N;
   F fft;
   fft.init(tw, t);
   double re[8], im[8];
+  if (inverse) {
+    const d2 *src = static_cast<const d2 *>(in) + (size_t)blockIdx.x * M;
+#pragma unroll
+    for (int m = 0; m < 8; m++) { const d2 v = src[m * T + t]; re[m] = v.x; im[m] = v.y; }
+    fft.inverse(re, im, xch, t);
+    uint64_t *dst = static_cast<uint64_t *>(out) + (size_t)blockIdx.x * N;
+    const RoundCtx scale(0x1p-64 / (double)M);
+#pragma unroll
+    for (int m = 0; m < 8; m++) {
+      dst[m * T + t] = round_mod_2_64(re[m], scale);
+      dst[m * T + t + M] = round_mod_2_64(im[m], scale);
+    }
+    return;
+  }
+  const uint64_t *src = static_cast<const uint64_t *>(in) + (size_t)blockIdx.x * N;
 #pragma unroll
   for (int m = 0; m < 8; m++) {
     re[m] = torus_to_double(src[m * T + t]);
     im[m] = torus_to_double(src[m * T + t + M]);
   }
   fft.forward(re, im, xch, t);
-  d2 *dst = out + (size_t)blockIdx.x * M;
+  d2 *dst = static_cast<d2 *>(out) + (size_t)blockIdx.x * M;
 #pragma unroll
   for (int m = 0; m < 8; m++) dst[m * T + t] = d2{re[m], im[m]};
-}
-
-// polynomial_DFT_to_torus for a flat array [src/polynomial.c:359-366]
-template <class F>
-__global__ __launch_bounds__(F::THREADS) void dft_to_torus_kernel(const d2 *__restrict__ in, uint64_t *__restrict__ out,
-                                                                const d2 *__restrict__ tw) {
-  constexpr int N = F::N, M = F::M, T = F::THREADS;
-  __shared__ __attribute__((aligned(16))) d2 xch[F::XCH_SLOTS];
-  const int t = threadIdx.x;
-  const d2 *src = in + (size_t)blockIdx.x * M;
-  F fft;
-  fft.init(tw, t);
-  double re[8], im[8];
-#pragma unroll
-  for (int m = 0; m < 8; m++) { const d2 v = src[m * T + t]; re[m] = v.x; im[m] = v.y; }
-  fft.inverse(re, im, xch, t);
-  uint64_t *dst = out + (size_t)blockIdx.x * N;
-  const RoundCtx scale(0x1p-64 / (double)M);
-#pragma unroll
-  for (int m = 0; m < 8; m++) {
-    dst[m * T + t] = round_mod_2_64(re[m], scale);
-    dst[m * T + t + M] = round_mod_2_64(im[m], scale);
-  }
 }
 
 // trgsw_mul_trlwe_DFT + trlwe_from_DFT for a batch [src/trgsw.c:385-423, src/trlwe.c:629-634]: out[b] = TRGSW (.) in[b], back in the torus domain.
@@ -1950,7 +1942,7 @@ __global__ __launch_bounds__(F::THREADS) void dft_to_torus_kernel(const d2 *__re
 // functional_bootstrap_trgsw_phase2); in_stride (words): 0 = one shared TRLWE input.
 // in0 != nullptr: CMUX (applications/leveled_lut/vertical_packing.c:24-33): out[b] = in0[b] + TRGSW (.) (in[b] - in0[b])  (out may alias in0)
 // out_dft != nullptr: trgsw_mul_trlwe_DFT as the reference declares it (include/mosfhet.h:344): the result stays in the DFT domain,
-// out_dft[b][c][slot] in slot order; trlwe_from_DFT (dft_to_torus_kernel) finishes it with the same inverse transform and rounding.
+// out_dft[b][c][slot] in slot order; trlwe_from_DFT (torus_to_dft_kernel, inverse) finishes it with the same inverse transform and rounding.
 #define EP_NT_LOAD(p) __builtin_nontemporal_load(p)
 #define EP_NT_STORE(v, p) __builtin_nontemporal_store((v), (p))
 // The unit loop comes in two forms: PLAIN (each component requested where it is used) and PIPELINED (the next component always in flight under the rows of the

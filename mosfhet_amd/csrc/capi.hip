@@ -28,6 +28,7 @@
 #include "leveled_lut_kernels.h"
 #include "linear_kernels.h"
 #include "pack_kernels.h"
+#include "trace_kernels.h"
 
 using namespace mosfhet;
 
@@ -1339,7 +1340,7 @@ extern "C" int mosfhet_hip_dft_to_torus_batch(mosfhet_hip_ctx_t ctx, uint64_t *d
     HIP_TRY(hipGetLastError());
     return MOSFHET_HIP_OK;
   }
-  RING_DISPATCH(ctx, N, hipLaunchKernelGGL(dft_to_torus_kernel<F>, dim3(count), dim3(F::THREADS), 0, pick(ctx, stream), (const d2 *)d_in, d_out, TW));
+  RING_DISPATCH(ctx, N, hipLaunchKernelGGL(torus_to_dft_kernel<F>, dim3(count), dim3(F::THREADS), 0, pick(ctx, stream), d_in, d_out, TW, 1));   // (the inverse direction of the one kernel)
   HIP_TRY(hipGetLastError());
   return MOSFHET_HIP_OK;
 }
@@ -1806,3 +1807,4 @@ extern "C" int mosfhet_hip_time_programmable_bootstrap(mosfhet_hip_ctx_t ctx, mo
 #include "capi_linear.inc"
 #include "capi_pack.inc"
 #include "capi_unpack.inc"
+#include "capi_trace.inc"

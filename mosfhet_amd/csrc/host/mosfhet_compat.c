@@ -2272,21 +2272,38 @@ TRLWE_KS_Key *trlwe_new_packing1_KS_key_CDKS21(TRLWE_Key out_key, TLWE_Key in_ke
   return res;
 }
 
-void trlwe_packing1_keyswitch_CDKS21(TRLWE out, TLWE in, TRLWE_KS_Key *ks_key) {
-  const int N = out->b->N;
-  TRLWE tmp = trlwe_alloc_new_sample(1, N);
-  trlwe_noiseless_trivial_sample(out, NULL);
-  for (int i = 1; i < N; i++) out->a[0]->coeffs[N - i] = (Torus)0 - in->a[i];   /* the LWE mask as the polynomial whose constant term pairs with the key */
-  out->a[0]->coeffs[0] = in->a[0];
-  out->b->coeffs[0] = in->b;
-  for (int i = 1, j = 0; i < N; i <<= 1, j++) {   /* trace: sum over the automorphisms X -> X^(N / 2^j + 1) */
-    const uint64_t gen = (uint64_t)(N >> j) + 1;
-    polynomial_permute(tmp->a[0], out->a[0], gen);
-    polynomial_permute(tmp->b, out->b, gen);
-    trlwe_keyswitch(tmp, tmp, ks_key[j]);
-    trlwe_addto(out, tmp);
+/* The trace on the device, all log2 N steps in one launch per batch (mosfhet_hip_tlwe_trace_pack_batch): the sample as the polynomial whose constant term pairs with
+ * the key, then out += KeySwitch_j(out(X^(N / 2^j + 1))) for j < log2 N.  Word for word the loop of polynomial_permute, trlwe_keyswitch and trlwe_addto it replaces. */
+static void trace_pack_run(const char *who, TRLWE *out, TLWE *in, int count, TRLWE_KS_Key *ks_key) {
+  mosfhet_hip_ctx_t ctx = (mosfhet_hip_ctx_t)mosfhet_engine_ctx();
+  const int N = out[0]->b->N;
+  const size_t in_w = (size_t)count * ((size_t)N + 1), out_w = (size_t)count * 2 * (size_t)N;
+  Torus *h = (Torus *)mc_hstage_alloc(sizeof(Torus) * (in_w > out_w ? in_w : out_w));
+  for (int c = 0; c < count; c++) {
+    Torus *w = h + (size_t)c * ((size_t)N + 1);
+    const int n = in[c]->n < N ? in[c]->n : N;
+    memcpy(w, in[c]->a, sizeof(Torus) * (size_t)n);
+    memset(w + n, 0, sizeof(Torus) * (size_t)(N - n));
+    w[N] = in[c]->b;
   }
-  free_trlwe(tmp);
+  Torus *d = (Torus *)mc_stage_alloc(sizeof(Torus) * (in_w + out_w));
+  mc_dev_copy(d, h, sizeof(Torus) * in_w, HIP_H2D);
+  if (mosfhet_hip_tlwe_trace_pack_batch(ctx, (mosfhet_hip_gak_t)ks_key[0]->device, ks_key[0]->entry, d + in_w, d, count, NULL) || mosfhet_hip_ctx_sync(ctx, NULL)) mc_die(who);
+  mc_dev_copy(h, d + in_w, sizeof(Torus) * out_w, HIP_D2H);
+  for (int c = 0; c < count; c++) {
+    if (out[c]->k != 1 || out[c]->b->N != N) { fprintf(stderr, "mosfhet_amd: %s: an output is not a k = 1 TRLWE sample of the first output's ring\n", who); abort(); }
+    mc_trlwe_from_flat(out[c], h + (size_t)c * 2 * (size_t)N);
+  }
+  stage_free(d);
+  mc_hstage_free(h);
+}
+
+void trlwe_packing1_keyswitch_CDKS21(TRLWE out, TLWE in, TRLWE_KS_Key *ks_key) { trace_pack_run("trlwe_packing1_keyswitch_CDKS21", &out, &in, 1, ks_key); }
+
+/* trlwe_packing1_keyswitch_CDKS21 over a batch in one call (new): out[c] = the trace switch of in[c], c < count; the inputs lie under the extracted ring key */
+void mosfhet_tlwe_trace_pack(TRLWE *out, TLWE *in, int count, TRLWE_KS_Key *ks_key) {
+  if (!out || !in || !ks_key || !ks_key[0] || !ks_key[0]->device || count < 1) { fprintf(stderr, "mosfhet_amd: mosfhet_tlwe_trace_pack: bad argument\n"); abort(); }
+  trace_pack_run("mosfhet_tlwe_trace_pack", out, in, count, ks_key);
 }
 
 /* TRLWE(m) -> TRLWE(m v) for a fixed polynomial v (src/keyswitch.c:64-96,574-608): entry 0 switches from s_in v, entry 1 from v; then
@@ -2303,21 +2320,20 @@ TRLWE_KS_Key trlwe_new_RLWE_priv_KS_key(TRLWE_Key out_key, TRLWE_Key in_key, Tor
   return trlwe_ks_header(dev, 0, 1, t, base_bit);
 }
 
-void trlwe_RLWE_priv_keyswitch(TRLWE out, TRLWE in, TRLWE_KS_Key ks_key) {
+void trlwe_RLWE_priv_keyswitch(TRLWE out, TRLWE in, TRLWE_KS_Key ks_key) {   /* both passes in one launch (mosfhet_hip_trlwe_rlwe_priv_keyswitch_batch) */
+  mosfhet_hip_ctx_t ctx = (mosfhet_hip_ctx_t)mosfhet_engine_ctx();
   const int N = out->b->N;
-  TRLWE src = trlwe_alloc_new_sample(1, N), as = trlwe_alloc_new_sample(1, N);
-  TRLWE_KS_Key entry = trlwe_ks_header(ks_key->device, 0, 0, ks_key->t, ks_key->base_bit);
-  trlwe_noiseless_trivial_sample(src, NULL);
-  memcpy(src->a[0]->coeffs, in->a[0]->coeffs, sizeof(Torus) * (size_t)N);
-  trlwe_keyswitch(as, src, entry);                 /* - sum_j dec_j(in.a) KS0_j */
-  memcpy(src->a[0]->coeffs, in->b->coeffs, sizeof(Torus) * (size_t)N);
-  entry->entry = 1;
-  trlwe_keyswitch(out, src, entry);                /* - sum_j dec_j(in.b) KS1_j */
-  trlwe_negate(out, out);
-  trlwe_addto(out, as);
-  free(entry);
-  free_trlwe(src);
-  free_trlwe(as);
+  const size_t w = (size_t)2 * N;
+  Torus *h = (Torus *)mc_hstage_alloc(sizeof(Torus) * w);
+  mc_trlwe_to_flat(h, in);
+  Torus *d = (Torus *)mc_stage_alloc(sizeof(Torus) * 2 * w);
+  mc_dev_copy(d, h, sizeof(Torus) * w, HIP_H2D);
+  if (mosfhet_hip_trlwe_rlwe_priv_keyswitch_batch(ctx, (mosfhet_hip_gak_t)ks_key->device, ks_key->entry, d + w, d, 1, NULL) || mosfhet_hip_ctx_sync(ctx, NULL))
+    mc_die("trlwe_RLWE_priv_keyswitch");
+  mc_dev_copy(h, d + w, sizeof(Torus) * w, HIP_D2H);
+  mc_trlwe_from_flat(out, h);
+  stage_free(d);
+  mc_hstage_free(h);
 }
 
 TRLWE_KS_Key *trlwe_new_gadget_to_RGSW_KS(TRLWE_Key key, int t, int base_bit) {   /* one key per mask component: v = -s_i */

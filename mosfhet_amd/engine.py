@@ -196,6 +196,18 @@ def trlwe_unpack_plan(N, n_out=0, t=0, base_bit=0, total=0, per=None, compressed
                 pool_bytes=int(plan[6]), rows_per_workgroup=int(plan[7]))
 
 
+TRACE_KINDS = ("trace_pack", "rlwe_priv_keyswitch", "trgsw_from_gadget")
+
+
+def trace_plan(kind, N, t, base_bit, entries, entry0=0, l=1, count=1):
+    """The shape of a tlwe_trace_pack / trlwe_rlwe_priv_keyswitch / trgsw_from_gadget call, checked as the calls check it (no device needed): kind one of TRACE_KINDS,
+    entries what the key set holds.  dict(entries_read, teams, threads, forwards, inverses, key_bytes) -- key entries a team reads, teams of the launch, threads per
+    team, forward and inverse transforms per team, key bytes a team reads.  include/mosfhet_hip.h: mosfhet_hip_trace_plan."""
+    plan = (C.c_longlong * 6)()
+    _check(lib().mosfhet_hip_trace_plan(TRACE_KINDS.index(kind), int(N), int(t), int(base_bit), int(entries), int(entry0), int(l), int(count), plan))
+    return dict(entries_read=int(plan[0]), teams=int(plan[1]), threads=int(plan[2]), forwards=int(plan[3]), inverses=int(plan[4]), key_bytes=int(plan[5]))
+
+
 class LinearMap:
     """The cleartext weights of y = W x + bias on the device (mosfhet_hip_linear_t): made by Engine.linear_dense / Engine.linear_sparse."""
 
@@ -1010,6 +1022,34 @@ class Engine:
         if out is None:
             out = self.empty(-(-total // per) if per >= 1 else 0, 2, pk.N)
         _check(lib().mosfhet_hip_tlwe_pack_batch(self.h, pk.h, _ptr(out) if total else None, _ptr(ct) if total else None, int(total), per, int(split), self._stream()))
+        return out
+
+    # ---- the trace switch and the gadget -> TRGSW conversion (include/mosfhet_hip.h: mosfhet_hip_tlwe_trace_pack_batch) ----
+    def tlwe_trace_pack(self, tks, ct, entry0=0, out=None):
+        """trlwe_packing1_keyswitch_CDKS21 over a batch: ct [count][N + 1] under the extracted ring key -> [count][2][N], phase N m at coefficient 0; tks holds the
+        log2 N trace keys from entry0 on (entry j switches from s(X^(N / 2^j + 1)))."""
+        count = ct.shape[0]
+        if out is None:
+            out = self.empty(count, 2, tks.N)
+        _check(lib().mosfhet_hip_tlwe_trace_pack_batch(self.h, tks.h, int(entry0), _ptr(out) if count else None, _ptr(ct) if count else None, count, self._stream()))
+        return out
+
+    def trlwe_rlwe_priv_keyswitch(self, tks, ct, entry0=0, out=None):
+        """trlwe_RLWE_priv_keyswitch over a batch: ct [count][2][N] -> TRLWE(m v), entries entry0 (from s_in v) and entry0 + 1 (from v); out may be ct."""
+        count = ct.shape[0]
+        if out is None:
+            out = self.empty(count, 2, tks.N)
+        _check(lib().mosfhet_hip_trlwe_rlwe_priv_keyswitch_batch(self.h, tks.h, int(entry0), _ptr(out) if count else None, _ptr(ct) if count else None, count, self._stream()))
+        return out
+
+    def trgsw_from_gadget(self, tks, gadget, entry0=0, out=None):
+        """trgsw_from_gadget over a batch: gadget [count][l][2][N] -> selectors [count][2l][2][N] float64 (DFT domain, the engine's slot order: the d_sel_dft of the
+        leveled-LUT calls); tks holds the gadget key (v = -s) at entry0, entry0 + 1."""
+        count, l, two, N = gadget.shape
+        assert two == 2
+        if out is None:
+            out = self.torch.empty(count, 2 * l, 2, N, dtype=self.torch.float64, device=self.device)
+        _check(lib().mosfhet_hip_trgsw_from_gadget_batch(self.h, tks.h, int(entry0), _ptr(out) if count else None, _ptr(gadget) if count else None, int(l), count, self._stream()))
         return out
 
     # ---- packed TRLWE samples opened into LWE batches (include/mosfhet_hip.h: mosfhet_hip_trlwe_unpack_batch) ----
