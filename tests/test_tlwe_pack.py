@@ -380,6 +380,140 @@ def test_pack_stale_staging_and_extreme_masks(eng, oracle):
         assert (_run(eng, pk, ones, 64, split) == packing_reference.pack_batch(ones, D["ks_dft"], t, bb, N, 64, split)).all()
 
 
+EXTREME = (1024, 8, 3, 8)           # N, n_in, t, base_bit of the extreme-key case
+
+
+def _extreme_case(oracle):
+    """N = 1024, n_in 8, t 3, base_bit 8, per = N.  Key rows: entry i is all -2^63 (i mod 3 = 0), all 2^63 - 1 (1), or 2^63 - 1 at even and -2^63 at odd
+    coefficients (2).  Masks: words whose t digits are all -2^(base_bit-1) ("bottom") or all 2^(base_bit-1) - 1 ("top"): the decomposition's offset taken off the
+    word that holds the digit fields.  Sample j is coefficient j of every entry's digit polynomials, and the products must ADD UP: coefficient n of digits * key is
+    sum_{i <= n} d_i k_(n-i) - sum_{i > n} d_i k_(N+n-i), so
+      output 0 (samples 0 .. N-1)  gives entry i the digits that make every d_i k_(N-1-i) positive -- bottom against -2^63, top against 2^63 - 1, and bottom at even
+                                   / top at odd samples against the alternating rows --: all n_in t N terms of coefficient N - 1 are positive;
+      output 1                     the opposite digits: coefficient N - 1 is as large and negative;
+      output 2                     output 0's digits up to sample N/2 - 1 and the opposite ones after it: the wrapped terms take their sign back, and coefficient
+                                   N/2 - 1 collects all N terms, so the peak is not at the edge of the polynomial;
+      output 3                     6 samples: masks of all 2^64 - 1, and random ones.
+    dict(rows, ks_dft, cts [3 N + 6][n_in + 1], bottom, top)"""
+    if "extreme" in _CACHE:
+        return _CACHE["extreme"]
+    N, n_in, t, bb = EXTREME
+    lo, hi = np.uint64(1 << 63), np.uint64((1 << 63) - 1)
+    rows = np.empty((n_in, t, 2, N), dtype=np.uint64)
+    for i in range(n_in):
+        rows[i] = (lo, hi, lo)[i % 3]
+        if i % 3 == 2:
+            rows[i, :, :, ::2] = hi
+    off = (1 << (63 - t * bb)) + sum(1 << (63 - i * bb) for i in range(t))
+    word = lambda field: np.uint64((sum(field << (64 - (i + 1) * bb) for i in range(t)) - off) % 2 ** 64)
+    bottom, top = word(0), word((1 << bb) - 1)
+    cts = np.random.default_rng(0xE8).integers(0, 2 ** 64, size=(3 * N + 6, n_in + 1), dtype=np.uint64)
+    first = np.empty((N, n_in), dtype=np.uint64)
+    for i in range(n_in):
+        first[:, i] = (bottom, top, bottom)[i % 3]
+        if i % 3 == 2:
+            first[1::2, i] = top
+    opposite = np.where(first == bottom, top, bottom)
+    cts[0:N, :n_in] = first
+    cts[N:2 * N, :n_in] = opposite
+    cts[2 * N:3 * N, :n_in] = np.concatenate([first[:N // 2], opposite[N // 2:]])
+    cts[3 * N:3 * N + 3, :n_in] = np.uint64(0xFFFFFFFFFFFFFFFF)
+    _CACHE["extreme"] = dict(rows=rows, ks_dft=oracle.ks_to_dft(rows), cts=cts, bottom=bottom, top=top)
+    return _CACHE["extreme"]
+
+
+def _exact_entry_sums(oracle, cts, rows, t, base_bit, N):
+    """What one entry adds to packing_reference.pack's accumulators, in exact integers: for each entry i and component c the negacyclic sum over the rows j of
+    digits(a_i, j) * rows[i, j, c], the key words as signed 64-bit integers.  Python integers [n_in][2][N].  Coefficient n takes d_i k_(n-i), negated where it
+    wrapped: row n of the product matrix is the window n .. n + N - 1 of (-k_1 .. -k_(N-1), k_0 .. k_(N-1)) against the reversed digits.  The key words go in two
+    halves of 32 bits, so that every int64 dot product stays below 2^52."""
+    from numpy.lib.stride_tricks import sliding_window_view
+    samples, n_in = cts.shape[0], cts.shape[1] - 1
+    out = np.zeros((n_in, 2, N), dtype=object)
+    for e in range(n_in):
+        a = np.zeros(N, dtype=np.uint64)
+        a[:samples] = cts[:, e]
+        for j in range(t):
+            d = np.ascontiguousarray(oracle.poly_decompose_i(a, base_bit, t, j).view(np.int64)[::-1])
+            for c in range(2):
+                k = rows[e, j, c].view(np.int64)
+                high, low = [sliding_window_view(np.concatenate([-h[1:], h]), N) @ d for h in (k >> 32, k & 0xFFFFFFFF)]
+                out[e, c] += high.astype(object) * (1 << 32) + low.astype(object)
+    return out
+
+
+def _exact_part_sums(entry_sums, split):
+    """the entries' exact sums added up over each of pack's parts: [split][2][N]"""
+    n_in = len(entry_sums)
+    step = -(-n_in // split)
+    return np.stack([entry_sums[part * step:min(n_in, (part + 1) * step)].sum(axis=0) for part in range(split)])
+
+
+def _extreme_magnitudes(oracle):
+    """log2 of the largest exact sum that pack holds before it rounds, for each of the three full outputs of the extreme-key case, at split 1 and split 2, cached"""
+    if "extreme sums" not in _CACHE:
+        N, n_in, t, bb = EXTREME
+        E = _extreme_case(oracle)
+        per_entry = [_exact_entry_sums(oracle, E["cts"][o * N:(o + 1) * N], E["rows"], t, bb, N) for o in range(3)]
+        _CACHE["extreme sums"] = {split: [float(np.log2(float(max(abs(int(v)) for v in _exact_part_sums(s, split).ravel())))) for s in per_entry] for split in (1, 2)}
+    return _CACHE["extreme sums"]
+
+
+def test_extreme_case_sums_pass_the_reduction_free_bound(oracle):
+    """The extreme-key case reaches what it is there for.  Its masks decompose to extreme digits only (oracle.poly_decompose_i), and the exact integer sums that
+    packing_reference.pack holds in its accumulators before rounding (_exact_part_sums, no floating point) are past 2^83 -- up to which rounding without the
+    reduction is exact -- in every full output, at split 1 and in the parts of split 2.  Measured: 2^84.6 at split 1 (the formula n_in t N 2^(base_bit-1) 2^63 of
+    pack_kernels.h, reached to 0.01 bit) and 2^83.6 at split 2, in each of the three outputs.  The exact sums of 5 fresh samples, reduced to 64 bits, are the
+    helper's words to within its FFT error -- the 2^32 of test_helper_against_the_reference; measured 2^22.7 --, which holds _exact_entry_sums itself to the helper."""
+    import packing_reference
+    N, n_in, t, bb = EXTREME
+    E = _extreme_case(oracle)
+    for word, want in ((E["bottom"], -(1 << (bb - 1))), (E["top"], (1 << (bb - 1)) - 1)):
+        for i in range(t):
+            assert (oracle.poly_decompose_i(np.full(N, word), bb, t, i).view(np.int64) == want).all()
+    assert np.isin(E["cts"][:3 * N, :n_in], [E["bottom"], E["top"]]).all()
+    mags = _extreme_magnitudes(oracle)
+    print("largest |key double| 2^%.1f; largest exact sum per output: split 1 %s, split 2 %s; the formula gives 2^%.1f"
+          % (_log2(np.abs(E["ks_dft"]).max()), ["2^%.2f" % m for m in mags[1]], ["2^%.2f" % m for m in mags[2]], np.log2(n_in * t * N) + bb - 1 + 63))
+    assert min(mags[1]) > 83 and min(mags[2]) > 83, mags
+    D = _case(oracle, N, n_in, t, bb, 1024)
+    sums = _exact_part_sums(_exact_entry_sums(oracle, D["cts"][:5], D["rows"], t, bb, N), 2)
+    exact = np.zeros((2, N), dtype=np.uint64)
+    exact[1, :5] = D["cts"][:5, n_in]
+    with np.errstate(over="ignore"):
+        for part in range(2):
+            exact -= np.array([[int(v) % 2 ** 64 for v in comp] for comp in sums[part]], dtype=np.uint64)
+    d = float(oracle.torus_dist(exact, packing_reference.pack(D["cts"][:5], D["ks_dft"], t, bb, N, 2)).max())
+    print("exact sums against the helper on 5 fresh samples: 2^%.1f" % _log2(d))
+    assert d <= 2.0 ** 32
+
+
+@pytest.mark.gpu
+def test_pack_extreme_masks_against_extreme_key_rows(eng, oracle):
+    """The case test_pack_stale_staging_and_extreme_masks leaves out: extreme masks against extreme key rows, arranged so that the products add up (_extreme_case:
+    N = 1024, n_in 8, t 3, base_bit 8, per = N, three full outputs and one of 6 samples), split 1 and 2.  The exact sums behind every full output are past 2^83,
+    asserted here and on the CPU by test_extreme_case_sums_pass_the_reduction_free_bound -- 2^84.6 at split 1, 2^83.6 in the parts of split 2: what pack_kernels.h
+    means by "far past the bound" of the reduction-free rounding -- and every word equals packing_reference.pack_batch on oracle.ks_to_dft of the rows."""
+    import packing_reference
+    N, n_in, t, bb = EXTREME
+    E = _extreme_case(oracle)
+    mags = _extreme_magnitudes(oracle)
+    print("largest |key double| 2^%.1f; largest exact sum per output: split 1 %s, split 2 %s"
+          % (_log2(np.abs(E["ks_dft"]).max()), ["2^%.2f" % m for m in mags[1]], ["2^%.2f" % m for m in mags[2]]))
+    assert min(mags[1]) > 83 and min(mags[2]) > 83, mags
+    pk = eng.load_trlwe_ks_keys(E["rows"], bb)
+    bad = []
+    try:
+        for split in (1, 2):
+            got, want = _run(eng, pk, E["cts"], N, split), packing_reference.pack_batch(E["cts"], E["ks_dft"], t, bb, N, N, split)
+            assert got.shape == want.shape == (4, 2, N)
+            if (got != want).any():
+                bad.append("split %d: %d words differ, outputs %s" % (split, (got != want).sum(), sorted(set(np.nonzero(got != want)[0].tolist()))))
+    finally:
+        pk.free()
+    assert not bad, bad
+
+
 @pytest.mark.gpu
 def test_pack_refusals_on_the_device(eng, oracle):
     """d_out overlapping d_in (the same buffer, a partial overlap), a key used with another context than its own (its clone for that context works and gives the same

@@ -51,18 +51,20 @@ def _want_trace(oracle, D, t, base_bit, N, entry0=0):
     return _CACHE[key]
 
 
-def _gadget_case(oracle, D, N, l, Bg_bit, count, sigma):
-    """gadget rows [count][l][2][N] of the bits 0, 1, 1, ... under D's key, and the helper's TRGSWs in the torus domain [count][2l][2][N]"""
+def _gadget_case(oracle, D, N, l, Bg_bit, count, sigma, seed=None):
+    """gadget rows [count][l][2][N] of the bits 0, 1, 1, ... under D's key, and the helper's TRGSWs in the torus domain [count][2l][2][N].  With a seed the noise
+    comes from a generator of the case's own, so that the rows do not depend on which tests drew from D's generator before."""
     import trace_reference as R
-    key = ("gadget", id(D), l, Bg_bit, count)
+    key = ("gadget", id(D), l, Bg_bit, count, seed)
     if key not in _CACHE:
+        rng = D["rng"] if seed is None else oracle.Rng(seed)
         bits = [0, 1, 1, 0, 1][:count]
         g = np.empty((count, l, 2, N), dtype=U64)
         for c, m in enumerate(bits):
             for i in range(l):
                 msg = np.zeros(N, dtype=U64)
                 msg[0] = U64(m) << U64(64 - (i + 1) * Bg_bit)
-                g[c, i] = oracle.trlwe_sample(D["rng"], msg, D["s"].reshape(1, N), sigma)
+                g[c, i] = oracle.trlwe_sample(rng, msg, D["s"].reshape(1, N), sigma)
         _CACHE[key] = dict(bits=bits, gadget=g)
     return _CACHE[key]
 
@@ -368,11 +370,12 @@ def test_trace_decrypts(eng, oracle, shape):
         assert d <= 4 * max(helper, 1.0) and d <= 2.0 ** 58, (c, _log2(d), _log2(helper))
 
 
-def _priv_inputs(oracle, D, N, count, sigma):
-    key = ("priv", id(D), count)
+def _priv_inputs(oracle, D, N, count, sigma, seed=None):
+    """count TRLWE samples under D's key; with a seed, from a generator of the case's own (see _gadget_case)"""
+    key = ("priv", id(D), count, seed)
     if key not in _CACHE:
-        s1 = D["s"].reshape(1, N)
-        _CACHE[key] = np.stack([oracle.trlwe_sample(D["rng"], D["rng"].words(N) & U64(0xF000000000000000), s1, sigma) for _ in range(count)])
+        s1, rng = D["s"].reshape(1, N), D["rng"] if seed is None else oracle.Rng(seed)
+        _CACHE[key] = np.stack([oracle.trlwe_sample(rng, rng.words(N) & U64(0xF000000000000000), s1, sigma) for _ in range(count)])
     return _CACHE[key]
 
 
@@ -478,3 +481,251 @@ def test_trace_host_face(native_lib, tmp_path):
     r = subprocess.run([_compile_c(tmp_path)], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=600)
     print(r.stdout)
     assert r.returncode == 0 and "trace_conversions ok" in r.stdout, r.stdout
+
+
+# ---------------------------------------------------------------- value edges, uncovered instantiations, run contexts ----------------------------------------------------------------
+EXTREME_KEY_SHAPES = [(4, 9), (2, 8)]
+
+
+def _ks_offset(t, base_bit):
+    """2^(63 - t base_bit) + sum_i 2^(63 - i base_bit): the rounding offset of the key switch's decomposition (trace_kernels.h: `off`)"""
+    return (1 << (63 - t * base_bit)) + sum(1 << (63 - i * base_bit) for i in range(t))
+
+
+def _ks_target(t, base_bit, field):
+    """the torus word whose t digits all come out of the base_bit-bit slot value `field`: 0 -> every digit -2^(base_bit-1), 2^base_bit - 1 -> every digit 2^(base_bit-1) - 1"""
+    return (sum(field << (64 - (i + 1) * base_bit) for i in range(t)) - _ks_offset(t, base_bit)) % 2 ** 64
+
+
+def _extreme_case(oracle, t, base_bit):
+    """N = 1024.  A key set of log2 N + 2 entries whose rows are all -2^63, all 2^63 - 1 and the two alternating by coefficient, in turn, with entry log2 N - 1 -- the
+    trace's last step -- all zero.  Masks: words whose digits are all at the bottom / all at the top (the offset construction with the key switch's offset), such
+    words with the signs the embedding and the first permutation (gen = N + 1: coefficient i times (-1)^i) take off again, so that the FIRST STEP decomposes exactly
+    them; tests/trace_reference.py::digit_boundary_words; all 2^64 - 1.  The same words as TRLWE samples for the private switch, and paired into gadgets of l = 2."""
+    import trace_reference as R
+    key = ("extreme", t, base_bit)
+    if key in _CACHE:
+        return _CACHE[key]
+    N = 1024
+    steps = R.log2n(N)
+    lo, hi = U64(1 << 63), U64((1 << 63) - 1)
+    rows = np.empty((steps + 2, t, 2, N), dtype=U64)
+    for e in range(steps + 2):
+        rows[e] = (lo, hi, lo)[e % 3]
+        if e % 3 == 2:
+            rows[e, :, :, ::2] = hi
+    rows[steps - 1] = 0
+    bottom, top = _ks_target(t, base_bit, 0), _ks_target(t, base_bit, (1 << base_bit) - 1)
+    edges = R.digit_boundary_words(t, base_bit)
+    masks = np.empty((7, N), dtype=U64)
+    masks[0], masks[1] = U64(bottom), U64(top)
+    masks[2] = U64(bottom)
+    masks[2, ::2] = U64(top)
+    for k, word in ((3, bottom), (4, top)):            # in.a[0] = w, in.a[i] = w for odd i and -w for even i: the first step's digit words are all w
+        masks[k] = U64(word)
+        masks[k, 2::2] = U64((-word) % 2 ** 64)
+    masks[5] = edges[np.arange(N) % len(edges)]
+    masks[6] = U64(0xFFFFFFFFFFFFFFFF)
+    rng = np.random.default_rng(0xE7 + t)
+    cts = np.concatenate([masks, rng.integers(0, 2 ** 64, size=(7, 1), dtype=U64)], axis=1)
+    trlwe = np.stack([np.stack([masks[k], masks[(k + 1) % 7]]) for k in (0, 1, 2, 5, 6, 3)])       # [6][2][N]
+    _CACHE[key] = dict(rows=rows, dft=oracle.ks_to_dft(rows), cts=cts, trlwe=trlwe, gadget=trlwe.reshape(3, 2, 2, N), bottom=bottom, top=top)
+    return _CACHE[key]
+
+
+@pytest.mark.parametrize("tb", EXTREME_KEY_SHAPES)
+def test_extreme_masks_decompose_to_extreme_digits(oracle, tb):
+    """oracle.poly_decompose_i on the masks of the extreme-key case: the target words give every one of the t digits -2^(base_bit-1) resp. 2^(base_bit-1) - 1; the
+    signed masks give exactly those words after the embedding and the first step's permutation, i.e. the trace's first step decomposes extreme digits only.  The
+    helper runs on the key rows of +-2^63, and with the zero entry its last step is (a, b + b(X^gen)) exactly: the switch of the permuted sample subtracts nothing."""
+    import trace_reference as R
+    t, bb = tb
+    N = 1024
+    E = _extreme_case(oracle, t, bb)
+    lo, hi = -(1 << (bb - 1)), (1 << (bb - 1)) - 1
+    for k, want in ((0, lo), (1, hi), (3, lo), (4, hi)):
+        first = np.ascontiguousarray(E["cts"][k, :N]) if k < 2 else oracle.poly_permute(np.ascontiguousarray(R.embed(E["cts"][k], N)[0]), N + 1)
+        for i in range(t):
+            assert (oracle.poly_decompose_i(first, bb, t, i).view(np.int64) == want).all(), (tb, k, i)
+    print("t %d base_bit %d: largest |key double| 2^%.1f, the sums reach t N 2^(base_bit-1) 2^63 = 2^%.1f" % (t, bb, _log2(np.abs(E["dft"]).max()), np.log2(t * N) + bb - 1 + 63))
+    steps = R.log2n(N)
+    acc = R.embed(E["cts"][3], N)
+    for j, gen in enumerate(R.trace_gens(N)[:-1]):
+        acc = R.trace_step(oracle, acc, gen, E["dft"][j], t, bb)
+    last = R.trace_step(oracle, acc, R.trace_gens(N)[-1], E["dft"][steps - 1], t, bb)
+    gen = R.trace_gens(N)[-1]
+    with np.errstate(over="ignore"):      # the switch of (a, b)(X^gen) with a zero entry is (0, b(X^gen)): the mask stays, the body takes its own permutation
+        exact = np.stack([acc[0], acc[1] + oracle.poly_permute(np.ascontiguousarray(acc[1]), gen)])
+    assert (last == exact).all()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("tb", EXTREME_KEY_SHAPES)
+def test_extreme_key_rows(eng, oracle, tb):
+    """N = 1024, key rows of -2^63 / 2^63 - 1 / alternating and one zero entry, masks with every digit at the bottom or the top, at the digit boundaries and all
+    2^64 - 1 (_extreme_case): the trace equals tests/trace_reference.py::trace_pack_batch on oracle.ks_to_dft of the same rows, the private switch equals
+    rlwe_priv_keyswitch on them (entries log2 N, log2 N + 1, and entries log2 N - 1, log2 N whose first is the zero entry), trgsw_from_gadget at l = 2 equals the
+    doubles of torus_to_dft of (private-switch words, gadget rows).  The last step without the oracle's key switch: it uses the zero entry and subtracts nothing
+    (the switch of the permuted sample with it is (0, b(X^gen))), so the device's result is (a, b + b(X^gen)) of the accumulator in front of it, word for word.
+    That accumulator is still the oracle's: R.trace_step, key switch included, builds it over the log2 N - 1 earlier steps; only the last step is oracle-free."""
+    import torch
+    import mosfhet_amd as ma
+    import trace_reference as R
+    t, bb = tb
+    N = 1024
+    E = _extreme_case(oracle, t, bb)
+    steps = R.log2n(N)
+    print("t %d base_bit %d: largest |key double| 2^%.1f" % (t, bb, _log2(np.abs(E["dft"]).max())))
+    tks = eng.load_trlwe_ks_keys(E["rows"], bb)
+    try:
+        got = _run_trace(eng, tks, E["cts"])
+        _same(got, R.trace_pack_batch(oracle, E["cts"], E["dft"][:steps], t, bb, N), "trace, t %d" % t)
+        gen = R.trace_gens(N)[-1]
+        for c in range(len(E["cts"])):
+            acc = R.embed(E["cts"][c], N)
+            for j, g in enumerate(R.trace_gens(N)[:-1]):
+                acc = R.trace_step(oracle, acc, g, E["dft"][j], t, bb)
+            with np.errstate(over="ignore"):
+                exact = np.stack([acc[0], acc[1] + oracle.poly_permute(np.ascontiguousarray(acc[1]), gen)])
+            assert (got[c] == exact).all(), "sample %d: the step on the zero entry is not (a, b + b(X^%d))" % (c, gen)
+        d_in = ma.to_device(E["trlwe"], eng.device)
+        for e0 in (steps, steps - 1):
+            want = np.stack([R.rlwe_priv_keyswitch(oracle, c, E["dft"][e0:e0 + 2], t, bb) for c in E["trlwe"]])
+            _same(ma.to_numpy(eng.trlwe_rlwe_priv_keyswitch(tks, d_in, e0)), want, "private switch, t %d, entry0 %d" % (t, e0))
+        d_g = ma.to_device(E["gadget"], eng.device)
+        sel = eng.trgsw_from_gadget(tks, d_g, steps)
+        switched = eng.trlwe_rlwe_priv_keyswitch(tks, d_g.view(6, 2, N), steps).view(3, 2, 2, N)
+        want = eng.torus_to_dft(torch.cat([switched, d_g], dim=1).contiguous().view(-1, N)).view(3, 4, 2, N)
+        torch.cuda.synchronize(eng.device)
+        assert torch.equal(sel, want), "%d doubles differ" % int((sel != want).sum())
+    finally:
+        tks.free()
+
+
+def _gadget_against_the_two_calls(eng, oracle, D, tks, gadget, N, l, t, bb, what):
+    """trgsw_from_gadget == torus_to_dft of (the private switch's words, the gadget rows) as doubles; the private switch's words == the helper"""
+    import torch
+    import mosfhet_amd as ma
+    import trace_reference as R
+    count, e0 = len(gadget), R.log2n(N)
+    d_g = ma.to_device(gadget, eng.device)
+    sel = eng.trgsw_from_gadget(tks, d_g, e0)
+    assert sel.shape == (count, 2 * l, 2, N) and sel.dtype == torch.float64
+    switched = eng.trlwe_rlwe_priv_keyswitch(tks, d_g.view(count * l, 2, N), e0).view(count, l, 2, N)
+    _same(ma.to_numpy(switched), np.stack([R.trgsw_from_gadget(oracle, g, D["dft"][e0:], t, bb)[:l] for g in gadget]), what + ": the private switch of the gadget rows")
+    want = eng.torus_to_dft(torch.cat([switched, d_g], dim=1).contiguous().view(-1, N)).view(count, 2 * l, 2, N)
+    torch.cuda.synchronize(eng.device)
+    assert torch.equal(sel, want), "%s: %d doubles differ" % (what, int((sel != want).sum()))
+    return sel
+
+
+@pytest.mark.gpu
+def test_private_switch_and_gadget_at_4096(eng, oracle):
+    """N = 4096 (t 2, base_bit 8, count 1; 256 threads a team), where the kernel is instantiated and only the trace ran: the private switch equals the helper on
+    every word, and trgsw_from_gadget at l = 2 equals the doubles of torus_to_dft of (private-switch words, gadget rows).  Words and doubles only."""
+    import mosfhet_amd as ma
+    import trace_reference as R
+    N, t, bb = 4096, 2, 8
+    D = _case(oracle, N, t, bb, 1, 2.0 ** -50)
+    tks, e0 = _tks(eng, D, bb), R.log2n(N)
+    ins = _priv_inputs(oracle, D, N, 1, 2.0 ** -50, seed=0x4096A)
+    want = np.stack([R.rlwe_priv_keyswitch(oracle, c, D["dft"][e0:], t, bb) for c in ins])
+    _same(ma.to_numpy(eng.trlwe_rlwe_priv_keyswitch(tks, ma.to_device(ins, eng.device), e0)), want, "N 4096")
+    G = _gadget_case(oracle, D, N, 2, 8, 1, 2.0 ** -50, seed=0x4096B)
+    _gadget_against_the_two_calls(eng, oracle, D, tks, G["gadget"], N, 2, t, bb, "N 4096, l 2")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("l", [1, 6])
+def test_trgsw_from_gadget_shortest_and_longest(eng, oracle, l):
+    """l = 1 and l = 6, the ends of the 1 .. 6 the call accepts (it ran at 2 and 4): N = 1024, count 2, key t 4, base_bit 9, gadget Bg_bit 8.  Words and doubles only."""
+    N, t, bb = 1024, 4, 9
+    D = _case(oracle, N, t, bb, 67, 2.0 ** -45)
+    G = _gadget_case(oracle, D, N, l, 8, 2, 2.0 ** -45, seed=0x6AD0 + l)
+    _gadget_against_the_two_calls(eng, oracle, D, _tks(eng, D, bb), G["gadget"], N, l, t, bb, "l %d" % l)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("call", ["trace", "private switch", "gadget"])
+def test_trace_calls_are_captured_in_a_graph(eng, oracle, call):
+    """Each of the three calls (N = 1024, t 4, base_bit 9), captured on one side stream after an eager call of that shape, replayed twice on different inputs copied
+    into the captured buffer: each replay == the eager words resp. doubles, which equal the helper -- no hidden allocation, synchronisation or state left between
+    replays.  For the gadget call the eager doubles are held to torus_to_dft of (private-switch words, gadget rows), the words to the helper
+    (_gadget_against_the_two_calls).  One stream, no parallel branches."""
+    import torch
+    import mosfhet_amd as ma
+    import trace_reference as R
+    N, t, bb = 1024, 4, 9
+    D = _case(oracle, N, t, bb, 67, 2.0 ** -45)
+    tks, e0 = _tks(eng, D, bb), R.log2n(N)
+    if call == "trace":
+        ins = [D["cts"][:3], D["cts"][3:6]]
+        run = lambda x, out=None: eng.tlwe_trace_pack(tks, x, 0, out=out)
+        want = [_want_trace(oracle, D, t, bb, N)[:3], _want_trace(oracle, D, t, bb, N)[3:6]]
+    elif call == "private switch":
+        both = _priv_inputs(oracle, D, N, 4, 2.0 ** -45, seed=0x6AA1)
+        ins = [both[:2], both[2:4]]
+        run = lambda x, out=None: eng.trlwe_rlwe_priv_keyswitch(tks, x, e0, out=out)
+        want = [np.stack([R.rlwe_priv_keyswitch(oracle, c, D["dft"][e0:], t, bb) for c in x]) for x in ins]
+    else:
+        g = _gadget_case(oracle, D, N, 2, 8, 3, 2.0 ** -45, seed=0x6AA2)["gadget"]
+        ins = [g[:1], g[1:2]]
+        run = lambda x, out=None: eng.trgsw_from_gadget(tks, x, e0, out=out)
+        want = None
+    xs = [ma.to_device(np.ascontiguousarray(x), eng.device) for x in ins]
+    eager = [run(x).clone() for x in xs]
+    torch.cuda.synchronize()
+    if want is not None:
+        for r in range(2):
+            _same(ma.to_numpy(eager[r]), want[r], "%s, eager, inputs %d" % (call, r))
+    else:                           # the eager doubles == torus_to_dft of (private-switch words == the helper, gadget rows)
+        for r in range(2):
+            assert torch.equal(eager[r], _gadget_against_the_two_calls(eng, oracle, D, tks, ins[r], N, 2, t, bb, "gadget, eager, inputs %d" % r))
+        assert not torch.equal(eager[0], eager[1])
+    d_in, d_out = xs[0].clone(), torch.empty_like(eager[0])
+    side = torch.cuda.Stream(device=eng.device)
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g, stream=side):
+        run(d_in, out=d_out)
+    for r in (1, 0):
+        d_in.copy_(xs[r])
+        d_out.zero_()
+        g.replay()
+        torch.cuda.synchronize()
+        assert torch.equal(d_out, eager[r]), "%s: replay on inputs %d differs from the plain call" % (call, r)
+    del g
+
+
+@pytest.mark.gpu
+def test_two_host_threads_run_the_trace(eng, oracle):
+    """Two host threads, each on a stream of its own, run the trace five times concurrently -- one at N = 1024 (3 samples), one at N = 2048 (2 samples): every result
+    equals the helper's words."""
+    import threading
+    import torch
+    import mosfhet_amd as ma
+    jobs = []
+    for N, t, bb, count, sigma in ((1024, 4, 9, 67, 2.0 ** -45), (2048, 4, 9, 2, 2.0 ** -50)):
+        D = _case(oracle, N, t, bb, count, sigma)
+        n = min(count, 3)
+        jobs.append((_tks(eng, D, bb), ma.to_device(D["cts"][:n], eng.device), _want_trace(oracle, D, t, bb, N)[:n]))
+    torch.cuda.synchronize()
+    bad, errors = [0, 0], []
+
+    def worker(k):
+        try:
+            tks, d_in, want = jobs[k]
+            stream = torch.cuda.Stream(device=eng.device)
+            with torch.cuda.stream(stream):
+                for _ in range(5):
+                    bad[k] += int(not (ma.to_numpy(eng.tlwe_trace_pack(tks, d_in, 0)) == want).all())
+        except Exception as e:  # noqa: BLE001
+            errors.append(repr(e))
+
+    threads = [threading.Thread(target=worker, args=(k,)) for k in range(2)]
+    for th in threads:
+        th.start()
+    for th in threads:
+        th.join()
+    assert not errors, errors
+    assert bad == [0, 0], bad
