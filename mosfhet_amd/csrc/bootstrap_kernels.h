@@ -212,7 +212,18 @@ __device__ __forceinline__ uint64_t add_offset(uint64_t x, uint64_t off) {
     return x + off;
   }
 }
-template <class F, int L, int BG>
+// The word the digits of coefficient j are cut from: rot(acc)[j] - acc[j] + off.  NEG: the component is held NEGATED (pbs_body.inc: kNegAcc -- `home_word` is
+// -acc[j] mod 2^64, the staged words are negated too and the caller passes `flip` inverted, so that `rotated` is +rot(acc)[j]); the home word is then ADDED by
+// one 64-bit add (the spelling of add_offset) where the subtraction is v_sub_co / v_subb with a wait state between them.
+template <int BG, bool NEG>
+__device__ __forceinline__ uint64_t digit_source(uint64_t rotated, uint64_t home_word, uint64_t off) {
+  if constexpr (NEG) {
+    return add_pairs(rotated, home_word) + off;
+  } else {
+    return add_offset<BG>(rotated - home_word, off);
+  }
+}
+template <class F, int L, int BG, bool NEG = false>
 __device__ __forceinline__ void cmux_digits(typename Digits<L, BG>::word_t (&w_lo)[8], typename Digits<L, BG>::word_t (&w_hi)[8],
                                             uint32_t (&ext)[8], const uint64_t (&al)[8], const uint64_t (&ah)[8],
                                             const uint64_t *home, d2 *xch, int a_lo, bool flip, uint64_t off, int t) {
@@ -224,8 +235,8 @@ __device__ __forceinline__ void cmux_digits(typename Digits<L, BG>::word_t (&w_l
 #pragma unroll
     for (int m = 0; m < 8; m++) {
       const int j = m * T + t;
-      D::pack(w_lo[m], w_hi[m], ext[m], add_offset<BG>(rot_coeff<N>(home, j, a_lo, flip) - home[j], off),
-              add_offset<BG>(rot_coeff<N>(home, j + M, a_lo, flip) - home[j + M], off));
+      D::pack(w_lo[m], w_hi[m], ext[m], digit_source<BG, NEG>(rot_coeff<N>(home, j, a_lo, flip), home[j], off),
+              digit_source<BG, NEG>(rot_coeff<N>(home, j + M, a_lo, flip), home[j + M], off));
     }
   } else {
     // stage the component and read it back rotated by abar
@@ -239,8 +250,8 @@ __device__ __forceinline__ void cmux_digits(typename Digits<L, BG>::word_t (&w_l
 #pragma unroll
     for (int m = 0; m < 8; m++) {
       const int j = m * T + t;
-      D::pack(w_lo[m], w_hi[m], ext[m], add_offset<BG>(rot_coeff<N>(st, j, a_lo, flip) - al[m], off),
-              add_offset<BG>(rot_coeff<N>(st, j + M, a_lo, flip) - ah[m], off));
+      D::pack(w_lo[m], w_hi[m], ext[m], digit_source<BG, NEG>(rot_coeff<N>(st, j, a_lo, flip), al[m], off),
+              digit_source<BG, NEG>(rot_coeff<N>(st, j + M, a_lo, flip), ah[m], off));
     }
     F::sync();
   }

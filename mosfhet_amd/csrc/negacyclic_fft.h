@@ -883,6 +883,30 @@ __device__ __forceinline__ uint64_t add_rounded(uint64_t acc, double v, const Ro
   return ((uint64_t)hi << 32) | (uint64_t)lo;
 }
 
+// a + b mod 2^64 of two vector register pairs as ONE instruction: no v_add_co / v_addc chain and no wait state between its halves
+__device__ __forceinline__ uint64_t add_pairs(uint64_t a, uint64_t b) {
+  uint64_t r;
+  asm("v_lshl_add_u64 %0, %1, 0, %2" : "=v"(r) : "v"(a), "v"(b));
+  return r;
+}
+
+// -round_mod_2_64(v) mod 2^64 without the reduction mod 1 (add_rounded<false>, same bound on v), as ONE 64-bit value: what a kernel that keeps its
+// accumulator NEGATED adds to it (pbs_body.inc: kNegAcc).  rint is odd, ties-to-even included, so with -v in place of v (a source modifier of the two
+// fmas) h, q and x above all change sign and h 2^32 + x is exactly the negated increment.  Assembled in C's own register pair: the low dword is C's,
+// the high dword is (low dword of A) - (bit 32 of C).  |x| <= 2^31 keeps C inside [2^52, 2^53), so its high dword is that of the magic number (x >= 0)
+// or one less (x < 0): the borrow is (high dword of C) - (high dword of 1.5 * 2^52), and the high dword of the increment ONE three-operand add with the
+// constant in a scalar register -- no carry, no bit-field extract; the caller's add_pairs is the second VALU.
+__device__ __forceinline__ uint64_t neg_rounded(double v, const RoundCtx &rc) {
+  const double A = __builtin_fma(-v, rc.scale32, rc.magic);
+  const double B = A - rc.magic;
+  const double q = __builtin_fma(-v, rc.scale32, -B);
+  const double C = __builtin_fma(q, rc.two32, rc.magic);
+  const uint64_t a = (uint64_t)__double_as_longlong(A), c = (uint64_t)__double_as_longlong(C);
+  uint32_t hi;   // (spelled in assembly: from the plain expression the compiler makes (a << 32) + c + (constant << 32), two moves and three adds)
+  asm("v_add3_u32 %0, %1, %2, %3" : "=v"(hi) : "v"((uint32_t)a), "v"((uint32_t)(c >> 32)), "s"(0u - 0x43380000u));
+  return ((uint64_t)hi << 32) | (uint64_t)(uint32_t)c;
+}
+
 // (double)(int64_t)x, correctly rounded (matches the C cast used by the reference and the oracle)
 __device__ __forceinline__ double torus_to_double(uint64_t x) { return (double)(int64_t)x; }
 

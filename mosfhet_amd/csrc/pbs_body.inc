@@ -7,6 +7,14 @@
   // (the key is (double)(int64_t) of torus words): |sum| <= 2^(ceil log2(2L) + log2 N + BG - 1 + 63).  Below 2^83 the rounding needs no
   // reduction mod 1 in front (add_rounded); that holds for SET_1's 2 x 2^8 gadget at N = 1024 (2^82) and is decided at compile time.
   constexpr bool kReduce = !(BG > 0 && kCeilLog2<2 * L>::value + (F::LOGM + 1) + BG - 1 + 63 < 83);
+  // SET_1's instantiation (G = 1 and G > 1) keeps both accumulator components NEGATED, -acc mod 2^64, from the first load to the last store: the digits then take
+  // rot(acc) + (-acc[j]) + off and the step's tail (-acc) + (-increment), each by one carry-free 64-bit add, where +acc needs a 64-bit subtract for the digits and a
+  // carry chain for the tail (cmux_digits: NEG; neg_rounded).  Component b's add is done by the LDS unit (a 64-bit DS add without return, on the team's own slice:
+  // DS operations of a wavefront execute in order, as wave_lds_sync relies on).  Same increments, same bits.  The one switch:
+#ifndef MOSFHET_PBS_NEGACC
+#define MOSFHET_PBS_NEGACC 1
+#endif
+  constexpr bool kNegAcc = MOSFHET_PBS_NEGACC && F::N == 1024 && L == 2 && BG == 8 && !kReduce && !BYC;
   // (G > 1: one slice per team, its xch and acc1 side by side, so that every LDS address of a team is the G = 1 address plus one team offset)
   constexpr int kSlice = (int)sizeof(d2) * F::XCH_SLOTS + (int)sizeof(uint64_t) * N;
   __shared__ __attribute__((aligned(16))) d2 xch_all[G == 1 ? F::XCH_SLOTS : G * kSlice / (int)sizeof(d2)];
@@ -30,16 +38,17 @@
     const uint64_t *src = p.out + b * (size_t)(2 * N);
 #pragma unroll
     for (int m = 0; m < 8; m++) {
-      al[m] = src[m * T + t];
-      ah[m] = src[M + m * T + t];
-      acc1[m * T + t] = src[N + m * T + t];
-      acc1[M + m * T + t] = src[N + M + m * T + t];
+      al[m] = kNegAcc ? 0 - src[m * T + t] : src[m * T + t];
+      ah[m] = kNegAcc ? 0 - src[M + m * T + t] : src[M + m * T + t];
+      acc1[m * T + t] = kNegAcc ? 0 - src[N + m * T + t] : src[N + m * T + t];
+      acc1[M + m * T + t] = kNegAcc ? 0 - src[N + M + m * T + t] : src[N + M + m * T + t];
     }
   } else {
     // src/bootstrap.c:194-195: acc = tv * X^(2N - bbar), gathered straight from global memory
     const uint64_t *__restrict__ tv = p.rows > 1 ? p.tv + (b % (size_t)p.rows) * (size_t)(2 * N) : p.tv + b * (size_t)p.tv_stride;
     const uint32_t bbar = modswitch<LOG2N2>(pbs_pre(ct[p.n], p, LOG2N2) + p.prec_offset);
-    const int rot = (2 * N - (int)bbar) & (2 * N - 1);
+    // (kNegAcc: -(tv X^r) = tv X^(r + N))
+    const int rot = (2 * N - (int)bbar + (kNegAcc ? N : 0)) & (2 * N - 1);
     const int a_lo = rot & (N - 1);
     const bool flip = (rot & N) != 0;
 #pragma unroll
@@ -73,7 +82,7 @@
     if (abar == 0) continue;  // src/bootstrap.c:114
     const d2 *__restrict__ bkrow = p.bk + (size_t)i * row_sz;
     const int a_lo = abar & (N - 1);
-    const bool flip = (abar & N) != 0;
+    const bool flip = ((abar & N) != 0) != kNegAcc;   // (kNegAcc: what is rotated is -acc, the digits want +rot(acc))
     double o_re[2][8], o_im[2][8];
 #pragma unroll
     for (int c = 0; c < 2; c++)
@@ -85,7 +94,7 @@
       for (int q = 0; q < 2; q++) {
         typename Digits<L, BG>::word_t w_lo[8], w_hi[8];
         uint32_t ext[8];
-        cmux_digits<F, L, BG>(w_lo, w_hi, ext, al, ah, q ? acc1 : nullptr, xch, a_lo, flip, off, t);
+        cmux_digits<F, L, BG, kNegAcc>(w_lo, w_hi, ext, al, ah, q ? acc1 : nullptr, xch, a_lo, flip, off, t);
         // rows two at a time where the transform keeps its pass twiddles in LDS (tools/ab/pbs_ab.hip -DAB_LTW instantiates that) -- at two wavefronts per SIMD
         // the pairs gain nothing here (experiments/README.md round 4): production instantiates pbs_kernel on the register-twiddle transforms
         if constexpr (F::kLtw && F::kForward2 && L % 2 == 0) cmux_rows2<F, L, BG>(w_lo, w_hi, ext, q, o_re, o_im, xch, fft, bkrow, Bg_bit, t);
@@ -118,15 +127,29 @@
       }
     }
     fft.inverse2(o_re[0], o_im[0], o_re[1], o_im[1], xch, t);
+    if constexpr (kNegAcc) {
 #pragma unroll
-    for (int m = 0; m < 8; m++) {
-      al[m] = add_rounded<kReduce>(al[m], o_re[0][m], scale);
-      ah[m] = add_rounded<kReduce>(ah[m], o_im[0][m], scale);
-    }
+      for (int m = 0; m < 8; m++) {
+        al[m] = add_pairs(neg_rounded(o_re[0][m], scale), al[m]);
+        ah[m] = add_pairs(neg_rounded(o_im[0][m], scale), ah[m]);
+      }
 #pragma unroll
-    for (int m = 0; m < 8; m++) {
-      acc1[m * T + t] = add_rounded<kReduce>(acc1[m * T + t], o_re[1][m], scale);
-      acc1[M + m * T + t] = add_rounded<kReduce>(acc1[M + m * T + t], o_im[1][m], scale);
+      for (int m = 0; m < 8; m++) {
+        // (ds_add_u64, nothing returned: no read to wait for at the end of the step, and the next step's reads of acc1 stand behind it in the wavefront's DS order)
+        (void)__hip_atomic_fetch_add(&acc1[m * T + t], neg_rounded(o_re[1][m], scale), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+        (void)__hip_atomic_fetch_add(&acc1[M + m * T + t], neg_rounded(o_im[1][m], scale), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+      }
+    } else {
+#pragma unroll
+      for (int m = 0; m < 8; m++) {
+        al[m] = add_rounded<kReduce>(al[m], o_re[0][m], scale);
+        ah[m] = add_rounded<kReduce>(ah[m], o_im[0][m], scale);
+      }
+#pragma unroll
+      for (int m = 0; m < 8; m++) {
+        acc1[m * T + t] = add_rounded<kReduce>(acc1[m * T + t], o_re[1][m], scale);
+        acc1[M + m * T + t] = add_rounded<kReduce>(acc1[M + m * T + t], o_im[1][m], scale);
+      }
     }
     F::sync();
   }
@@ -148,15 +171,21 @@
     }
     F::sync();
     uint64_t *dst = p.out + b * (size_t)(N + 1);
-    for (int j = te; j < N; j += T) dst[j] = (j == 0) ? st[0] : (0 - st[N - j]);
-    if (te == 0) dst[N] = acc1[0];
+    // (kNegAcc: the resident words are already -acc_a; only a[0] and b are negated back)
+    if constexpr (kNegAcc) {
+      for (int j = te; j < N; j += T) dst[j] = (j == 0) ? (0 - st[0]) : st[N - j];
+      if (te == 0) dst[N] = 0 - acc1[0];
+    } else {
+      for (int j = te; j < N; j += T) dst[j] = (j == 0) ? st[0] : (0 - st[N - j]);
+      if (te == 0) dst[N] = acc1[0];
+    }
   } else {
     uint64_t *dst = p.out + b * (size_t)(2 * N);
 #pragma unroll
     for (int m = 0; m < 8; m++) {
-      dst[m * T + te] = al[m];
-      dst[M + m * T + te] = ah[m];
-      dst[N + m * T + te] = acc1[m * T + te];
-      dst[N + M + m * T + te] = acc1[M + m * T + te];
+      dst[m * T + te] = kNegAcc ? 0 - al[m] : al[m];
+      dst[M + m * T + te] = kNegAcc ? 0 - ah[m] : ah[m];
+      dst[N + m * T + te] = kNegAcc ? 0 - acc1[m * T + te] : acc1[m * T + te];
+      dst[N + M + m * T + te] = kNegAcc ? 0 - acc1[M + m * T + te] : acc1[M + m * T + te];
     }
   }

@@ -63,7 +63,10 @@ SWITCHES = {
 }
 # not library switches: the build's extra compiler flags and bench.py's test hooks (documented where they are read)
 OTHER = {"MOSFHET_HIPCC_EXTRA": "mosfhet_amd/build.py: extra hipcc flags (part of the source hash)", "MOSFHET_BENCH_BACKEND": "bench.py test hook: process-group backend",
-         "MOSFHET_BENCH_SHARE_GPU": "bench.py test hook: every rank on device 0", "MOSFHET_BENCH_FORCE_DIST": "bench.py test hook: process group at world size 1"}
+         "MOSFHET_BENCH_SHARE_GPU": "bench.py test hook: every rank on device 0", "MOSFHET_BENCH_FORCE_DIST": "bench.py test hook: process group at world size 1",
+         "MOSFHET_PBS_NEGACC": "compile-time, pbs_body.inc, default 1: SET_1's throughput bootstrap kernels keep their accumulators negated (carry-free digit and tail adds, "
+                               "component b added by the LDS unit); `-DMOSFHET_PBS_NEGACC=0` through `MOSFHET_HIPCC_EXTRA` or `tools/ab/run_ab.py build` compiles the "
+                               "plain form, instruction for instruction the kernels before it; same bits: `tests/test_pbs_acc_forms.py`"}
 
 
 def in_source():
