@@ -331,6 +331,11 @@ void mosfhet_tlwe_pack(TRLWE *out /*[ceil(total / per)]*/, TLWE *in /*[total]*/,
  * (trlwe_extract_tlwe_key of the key the set switches to): the phase of out[c] is N m at coefficient 0. */
 void mosfhet_tlwe_trace_pack(TRLWE *out /*[count]*/, TLWE *in /*[count]*/, int count, TRLWE_KS_Key *ks_key);
 
+/* Many samples per output by the trace (new; mosfhet_hip_tlwe_trace_pack_many_batch): n = 2^log_per, outputs = ceil(total / n), out[o] packs in[o n .. o n + n - 1] through a
+ * binary tree of n - 1 merges and log2 N - log_per trace steps with the same ks_key (trlwe_new_packing1_KS_key_CDKS21); missing samples of the last output count as zero.
+ * The phase of out[o] is N m_j at coefficient j N / n and 0 elsewhere.  log_per = 0 gives mosfhet_tlwe_trace_pack's words.  One upload, one call, one download. */
+void mosfhet_tlwe_trace_pack_many(TRLWE *out /*[outputs]*/, TLWE *in /*[total]*/, int total, int log_per, TRLWE_KS_Key *ks_key);
+
 /* trlwe_extract_tlwe (src/trlwe.c:540-552) over a batch in one call (new; mosfhet_hip_trlwe_unpack_batch), the inverse layout of mosfhet_tlwe_pack: out[o per + j] =
  * extract(in[o], j) for o < ceil(total / per), 1 <= per <= N, of dimension N; the last input may be opened in part.  Synchronous; aborts on error; primary device. */
 void mosfhet_trlwe_unpack(TLWE *out /*[total]*/, TRLWE *in /*[ceil(total / per)]*/, uint64_t total, uint64_t per);

@@ -568,6 +568,40 @@ int mosfhet_hip_trgsw_from_gadget_batch(mosfhet_hip_ctx_t ctx, mosfhet_hip_gak_t
                                         const uint64_t *d_gadget /*[count][l][2][N]*/, int l, int count, void *stream);
 int mosfhet_hip_trace_plan(int kind, int N, int t, int base_bit, int entries, int entry0, int l, int count, long long plan[6]);
 
+/* ---- many LWE samples packed into one TRLWE sample by the trace (PackLWEs of the paper trlwe_packing1_keyswitch_CDKS21 comes from) ----
+ * Same key set as mosfhet_hip_tlwe_trace_pack_batch (log2 N entries from entry0 on, k = 1, N in {1024, 2048, 4096}, any t), no other key material.
+ * d_in [total][N + 1], n = 2^log_per, L = log_per, 0 <= L <= log2 N, outputs = ceil(total / n), d_out [outputs][2][N]; output o takes samples o n .. o n + n - 1, a sample
+ * index >= total stands for the all-zero sample (the last output only).  With embed the embedding of the trace call (a'[0] = a[0], a'[N - i] = -a[i], b X^0),
+ * KeySwitch_e = trlwe_keyswitch with entry entry0 + e (rows 0 .. t - 1 in one chain, one rounding per component), X^s p the exact negacyclic shift of both components
+ * and every addition mod 2^64:
+ *
+ *   P_0[j] = embed(in[o n + j])                                    j < n
+ *   for lvl = 1 .. L:                                              n / 2^lvl results per output
+ *       E = P_{lvl-1}[r],   O = X^(N / 2^lvl) * P_{lvl-1}[r + n / 2^lvl]        r < n / 2^lvl
+ *       U = E + O,  V = E - O
+ *       P_lvl[r] = U + KeySwitch_{log2 N - lvl}( V(X^(2^lvl + 1)) )
+ *   acc = P_L[0]
+ *   for j = 0 .. log2 N - L - 1:   acc += KeySwitch_j( acc(X^(N / 2^j + 1)) )   -- the trace step
+ *   out[o] = acc
+ *
+ * Every call uses each of the log2 N entries once (level lvl entry log2 N - lvl, the tail entries 0 .. log2 N - L - 1).  The phase N m_j of sample j lands at coefficient
+ * j N / n, every other coefficient has phase 0 up to the key-switch noise.  log_per = 0 is mosfhet_hip_tlwe_trace_pack_batch word for word.  THE INPUTS MUST LIE UNDER THE
+ * EXTRACTED RING KEY, as there.  n - 1 merges and log2 N - L trace steps per output, each one automorphism and one FFT key switch: one launch per level, one team per
+ * merge, the last level's launch runs the tail with the accumulator on chip; at level 1 the two leaves are embedded as they are read.
+ *
+ * Asynchronous on `stream`, never synchronises.  Levels 1 .. L - 1 live in the calling thread's pool (one stream per host thread; capturable once a call of the same size
+ * has run), bounded by mosfhet_hip_set_tlwe_pack_workspace: level 1 holds n / 2 TRLWE samples per output, level 2 n / 4 beside it, later levels reuse the two regions;
+ * a larger batch runs in rounds of whole outputs.  No word depends on total, on an output's position, on the rounds or on what the pool held.  MOSFHET_HIP_EINVAL, before
+ * any HIP call: null ctx / tks, total < 0, entry0 < 0, log_per outside 0 .. log2 N, a set shorter than entry0 + log2 N, null buffers with total > 0, d_out overlapping
+ * d_in, tks of another context, a workspace bound below one output's levels, a level whose teams do not fit one launch.  total == 0 is OK.
+ *
+ * mosfhet_hip_tlwe_trace_pack_many_plan: the launcher's own decision as a pure function (no GPU); workspace_bytes = 0: the current setting.  plan = { outputs, launches
+ * per round, teams of the first launch of a round, merge steps per output (n - 1), tail steps (log2 N - L), outputs per round, rounds, pool bytes per round }. */
+int mosfhet_hip_tlwe_trace_pack_many_batch(mosfhet_hip_ctx_t ctx, mosfhet_hip_gak_t tks, int entry0, uint64_t *d_out /*[outputs][2][N]*/, const uint64_t *d_in /*[total][N+1]*/,
+                                           int total, int log_per, void *stream);
+int mosfhet_hip_tlwe_trace_pack_many_plan(int N, int t, int base_bit, int entries, int entry0, int total, int log_per, long long workspace_bytes /*0: current setting*/,
+                                          long long plan[8]);
+
 /* CMUX over a batch with one shared selector = entry `key_index` of a key handle (e.g. circuit-bootstrap outputs turned into a handle by
  * mosfhet_hip_bsk_create_from_device): d_out[b] = d_in0[b] + key (.) (d_in1[b] - d_in0[b]); d_out may alias d_in0.  The leveled caller of
  * the path (applications/leveled_lut/vertical_packing.c:24-52: CMUX tree, then blind_rotate with the selectors as key). */

@@ -2272,14 +2272,15 @@ TRLWE_KS_Key *trlwe_new_packing1_KS_key_CDKS21(TRLWE_Key out_key, TLWE_Key in_ke
   return res;
 }
 
-/* The trace on the device, all log2 N steps in one launch per batch (mosfhet_hip_tlwe_trace_pack_batch): the sample as the polynomial whose constant term pairs with
- * the key, then out += KeySwitch_j(out(X^(N / 2^j + 1))) for j < log2 N.  Word for word the loop of polynomial_permute, trlwe_keyswitch and trlwe_addto it replaces. */
-static void trace_pack_run(const char *who, TRLWE *out, TLWE *in, int count, TRLWE_KS_Key *ks_key) {
+/* The trace on the device (mosfhet_hip_tlwe_trace_pack_many_batch; log_per = 0 is mosfhet_hip_tlwe_trace_pack_batch, all log2 N steps in one launch per batch): the sample
+ * as the polynomial whose constant term pairs with the key, then out += KeySwitch_j(out(X^(N / 2^j + 1))) for j < log2 N.  Word for word the loop of polynomial_permute,
+ * trlwe_keyswitch and trlwe_addto it replaces.  log_per > 0: 2^log_per samples per output through the packing tree first.  One upload, one call, one download. */
+static void trace_pack_run(const char *who, TRLWE *out, TLWE *in, int total, int log_per, TRLWE_KS_Key *ks_key) {
   mosfhet_hip_ctx_t ctx = (mosfhet_hip_ctx_t)mosfhet_engine_ctx();
-  const int N = out[0]->b->N;
-  const size_t in_w = (size_t)count * ((size_t)N + 1), out_w = (size_t)count * 2 * (size_t)N;
+  const int N = out[0]->b->N, outputs = (int)(((long long)total + (1ll << log_per) - 1) >> log_per);
+  const size_t in_w = (size_t)total * ((size_t)N + 1), out_w = (size_t)outputs * 2 * (size_t)N;
   Torus *h = (Torus *)mc_hstage_alloc(sizeof(Torus) * (in_w > out_w ? in_w : out_w));
-  for (int c = 0; c < count; c++) {
+  for (int c = 0; c < total; c++) {
     Torus *w = h + (size_t)c * ((size_t)N + 1);
     const int n = in[c]->n < N ? in[c]->n : N;
     memcpy(w, in[c]->a, sizeof(Torus) * (size_t)n);
@@ -2288,9 +2289,10 @@ static void trace_pack_run(const char *who, TRLWE *out, TLWE *in, int count, TRL
   }
   Torus *d = (Torus *)mc_stage_alloc(sizeof(Torus) * (in_w + out_w));
   mc_dev_copy(d, h, sizeof(Torus) * in_w, HIP_H2D);
-  if (mosfhet_hip_tlwe_trace_pack_batch(ctx, (mosfhet_hip_gak_t)ks_key[0]->device, ks_key[0]->entry, d + in_w, d, count, NULL) || mosfhet_hip_ctx_sync(ctx, NULL)) mc_die(who);
+  if (mosfhet_hip_tlwe_trace_pack_many_batch(ctx, (mosfhet_hip_gak_t)ks_key[0]->device, ks_key[0]->entry, d + in_w, d, total, log_per, NULL) || mosfhet_hip_ctx_sync(ctx, NULL))
+    mc_die(who);
   mc_dev_copy(h, d + in_w, sizeof(Torus) * out_w, HIP_D2H);
-  for (int c = 0; c < count; c++) {
+  for (int c = 0; c < outputs; c++) {
     if (out[c]->k != 1 || out[c]->b->N != N) { fprintf(stderr, "mosfhet_amd: %s: an output is not a k = 1 TRLWE sample of the first output's ring\n", who); abort(); }
     mc_trlwe_from_flat(out[c], h + (size_t)c * 2 * (size_t)N);
   }
@@ -2298,12 +2300,21 @@ static void trace_pack_run(const char *who, TRLWE *out, TLWE *in, int count, TRL
   mc_hstage_free(h);
 }
 
-void trlwe_packing1_keyswitch_CDKS21(TRLWE out, TLWE in, TRLWE_KS_Key *ks_key) { trace_pack_run("trlwe_packing1_keyswitch_CDKS21", &out, &in, 1, ks_key); }
+void trlwe_packing1_keyswitch_CDKS21(TRLWE out, TLWE in, TRLWE_KS_Key *ks_key) { trace_pack_run("trlwe_packing1_keyswitch_CDKS21", &out, &in, 1, 0, ks_key); }
 
 /* trlwe_packing1_keyswitch_CDKS21 over a batch in one call (new): out[c] = the trace switch of in[c], c < count; the inputs lie under the extracted ring key */
 void mosfhet_tlwe_trace_pack(TRLWE *out, TLWE *in, int count, TRLWE_KS_Key *ks_key) {
   if (!out || !in || !ks_key || !ks_key[0] || !ks_key[0]->device || count < 1) { fprintf(stderr, "mosfhet_amd: mosfhet_tlwe_trace_pack: bad argument\n"); abort(); }
-  trace_pack_run("mosfhet_tlwe_trace_pack", out, in, count, ks_key);
+  trace_pack_run("mosfhet_tlwe_trace_pack", out, in, count, 0, ks_key);
+}
+
+/* 2^log_per samples per output by the trace (new): out[o] packs in[o n .. o n + n - 1], n = 2^log_per; missing samples of the last output count as zero */
+void mosfhet_tlwe_trace_pack_many(TRLWE *out, TLWE *in, int total, int log_per, TRLWE_KS_Key *ks_key) {
+  if (!out || !in || !ks_key || !ks_key[0] || !ks_key[0]->device || total < 1 || log_per < 0 || log_per > 12) {
+    fprintf(stderr, "mosfhet_amd: mosfhet_tlwe_trace_pack_many: bad argument\n");
+    abort();
+  }
+  trace_pack_run("mosfhet_tlwe_trace_pack_many", out, in, total, log_per, ks_key);
 }
 
 /* TRLWE(m) -> TRLWE(m v) for a fixed polynomial v (src/keyswitch.c:64-96,574-608): entry 0 switches from s_in v, entry 1 from v; then

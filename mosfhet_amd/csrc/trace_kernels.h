@@ -1,8 +1,8 @@
-// trace_kernels.h -- device code of mosfhet_hip_tlwe_trace_pack_batch, mosfhet_hip_trlwe_rlwe_priv_keyswitch_batch and mosfhet_hip_trgsw_from_gadget_batch
-// (gfx950).  Own code; the functions they stand for: trlwe_packing1_keyswitch_CDKS21 (src/keyswitch.c:526-546), trlwe_RLWE_priv_keyswitch (:65-97) and
+// trace_kernels.h -- device code of mosfhet_hip_tlwe_trace_pack_batch, mosfhet_hip_tlwe_trace_pack_many_batch, mosfhet_hip_trlwe_rlwe_priv_keyswitch_batch and
+// mosfhet_hip_trgsw_from_gadget_batch (gfx950).  Own code; the functions they stand for: trlwe_packing1_keyswitch_CDKS21 (src/keyswitch.c:526-546), trlwe_RLWE_priv_keyswitch (:65-97) and
 // trgsw_from_gadget (:559-572) of the reference.
 //
-// One kernel, trace_conversions_kernel<F>, with the work named at run time (TraceParams::kind) -- three instantiations, one per ring, for the three calls: the
+// One kernel, trace_conversions_kernel<F>, with the work named at run time (TraceParams::kind) -- three instantiations, one per ring, for the four calls: the
 // library's kernel table is held below a fixed number of instantiations (tests/test_host_and_abi.py).  The bodies share nothing but the transform set-up.
 //
 //   trace_pack_body<F>             one team (F::THREADS) per LWE sample, all log2 N trace steps inside:
@@ -14,6 +14,11 @@
 //                                  rows, two inverse transforms, and the rounded pair subtracted from the accumulator.  Every word mod 2^64 equals the sequence
 //                                  permute, trlwe_fft_keyswitch_kernel mode 0, add: one chain over rows 0 .. t - 1, the same rounding.
 //                                  Key rows come straight from global memory: a set of log2 N entries is 1.4 MiB at N = 2048, t = 4 and every team reads it.
+//                                  kind 3 (mosfhet_hip_tlwe_trace_pack_many_batch; include/mosfhet_hip.h has the definition): the same body with another prologue and
+//                                  fewer steps -- one team per MERGE of the packing tree.  Merge r of output o at level lvl loads E = P[r] and O = X^(N / 2^lvl)
+//                                  P[r + n / 2^lvl] (at level 1 embedded straight from the two LWE samples), keeps U = E + O as the accumulator and runs one step
+//                                  whose switched operand is V = E - O, with generator 2^lvl + 1 and entry log2 N - lvl (trace_step<F, true>: the step of the trace
+//                                  with "kept" and "switched" apart).  The last level's teams go on with trace steps 0 .. log2 N - L - 1 on chip.
 //   rlwe_priv_keyswitch_body<F>
 //                                  one team per TRLWE sample, two passes:  out = round(as(in.b; KS1)) - round(as(in.a; KS0)), each pass with an accumulator pair,
 //                                  two inverse transforms and a rounding of its own (the two trlwe_keyswitch calls, the negation and the addition of the host
@@ -31,80 +36,153 @@
 
 namespace mosfhet {
 
+enum { TRACE_KIND_PACK = 0, TRACE_KIND_PRIV = 1, TRACE_KIND_GADGET = 2, TRACE_KIND_MANY = 3 };
+
+struct TraceParams {
+  const d2 *__restrict__ key;   // the first entry the call uses: [log2 N or 2][t][2][M] complex
+  const d2 *__restrict__ tw;
+  const uint64_t *in;           // kind 0: [count][N + 1]; 1: [count][2][N]; 2: [count][l][2][N]; 3: level 1: the LWE samples of the round [total][N + 1], level > 1: the
+                                // results of the level before [outputs][2 cnt][2][N]
+  uint64_t *out;                // kind 0, 1: [count][2][N] (kind 1: may be `in`); 3: [outputs][cnt][2][N]
+  d2 *sel;                      // kind 2: [count][2l][2][M] complex
+  int kind, t, base_bit, l;
+  int lvl, cnt_log, tail, total;   // kind 3: merge level (>= 1), log2 of the results per output it writes (cnt = n / 2^lvl), trace steps behind the merge (last level only),
+                                   // samples `in` holds at level 1 (a sample index >= total stands for the all-zero sample)
+};
+
+// One step on the accumulator (a in al / ah, b in acc1):  acc += KeySwitch_entry(v(X^gen)).  The permutation of ga_eval_automorphism (scatter through LDS, signs by bit N
+// of i gen): v.a into the staging buffer for the digit words, v.b ADDED into acc1 in place (a permutation: every word has one writer); then ks_rows_rt on the entry's t
+// rows, two inverse transforms, and the rounded pair subtracted from the accumulator.  MERGE = false: v is the accumulator itself (va_* alias al / ah, v.b is read from
+// acc1) -- the trace step.  MERGE = true: v = (va, vb) in registers and the accumulator holds the kept operand -- a merge of the packing tree.
+template <class F, bool MERGE>
+__device__ __forceinline__ void trace_step(uint64_t (&al)[8], uint64_t (&ah)[8], uint64_t *acc1, const uint64_t (&va_lo)[8], const uint64_t (&va_hi)[8],
+                                           const uint64_t (&vb_lo)[8], const uint64_t (&vb_hi)[8], int gen, d2 *xch, const F &fft, const d2 *__restrict__ entry, int t,
+                                           int base_bit, uint64_t off, const RoundCtx &scale, int tid) {
+  constexpr int N = F::N, M = F::M, T = F::THREADS;
+  uint64_t *st = reinterpret_cast<uint64_t *>(xch);
+  uint64_t dd_lo[8], dd_hi[8];
+  {
+    // component a: scatter through the staging buffer, read back in coefficient order, keep only the digit words
+#pragma unroll
+    for (int m = 0; m < 8; m++) {
+      const int i0 = (m * T + tid) * gen, i1 = (M + m * T + tid) * gen;
+      st[i0 & (N - 1)] = (i0 & N) ? (0 - va_lo[m]) : va_lo[m];
+      st[i1 & (N - 1)] = (i1 & N) ? (0 - va_hi[m]) : va_hi[m];
+    }
+    F::sync();
+#pragma unroll
+    for (int m = 0; m < 8; m++) { dd_lo[m] = st[m * T + tid] + off; dd_hi[m] = st[M + m * T + tid] + off; }
+    F::sync();
+  }
+  {
+    // component b: acc1 += v.b(X^gen) in place (the trace step: read everything, barrier; then scatter-add: word (i gen) mod N has this one writer)
+    uint64_t v_lo[8], v_hi[8];
+    if constexpr (MERGE) {
+#pragma unroll
+      for (int m = 0; m < 8; m++) { v_lo[m] = vb_lo[m]; v_hi[m] = vb_hi[m]; }
+    } else {
+#pragma unroll
+      for (int m = 0; m < 8; m++) { v_lo[m] = acc1[m * T + tid]; v_hi[m] = acc1[M + m * T + tid]; }
+      F::sync();
+    }
+#pragma unroll
+    for (int m = 0; m < 8; m++) {
+      const int i0 = (m * T + tid) * gen, i1 = (M + m * T + tid) * gen;
+      acc1[i0 & (N - 1)] += (i0 & N) ? (0 - v_lo[m]) : v_lo[m];
+      acc1[i1 & (N - 1)] += (i1 & N) ? (0 - v_hi[m]) : v_hi[m];
+    }
+    F::sync();
+  }
+  double o_re[2][8], o_im[2][8];
+#pragma unroll
+  for (int cc = 0; cc < 2; cc++)
+#pragma unroll
+    for (int m = 0; m < 8; m++) { o_re[cc][m] = 0.0; o_im[cc][m] = 0.0; }
+  ks_rows_rt<F>(dd_lo, dd_hi, o_re, o_im, xch, fft, entry, t, base_bit, tid);
+  fft.inverse(o_re[0], o_im[0], xch, tid);
+#pragma unroll
+  for (int m = 0; m < 8; m++) {
+    al[m] -= round_mod_2_64(o_re[0][m], scale);
+    ah[m] -= round_mod_2_64(o_im[0][m], scale);
+  }
+  fft.inverse(o_re[1], o_im[1], xch, tid);
+#pragma unroll
+  for (int m = 0; m < 8; m++) {
+    acc1[m * T + tid] -= round_mod_2_64(o_re[1][m], scale);
+    acc1[M + m * T + tid] -= round_mod_2_64(o_im[1][m], scale);
+  }
+  F::sync();
+}
+
+// prologue (kind 0: embed | kind 3: merge) + trace steps 0 .. steps - 1
 template <class F>
-__device__ __forceinline__ void trace_pack_body(d2 *xch, uint64_t *acc1, const F &fft, const d2 *__restrict__ key /* entry0 */, const uint64_t *__restrict__ in /*[count][N + 1]*/,
-                                                uint64_t *__restrict__ out /*[count][2][N]*/, int t, int base_bit, int tid) {
+__device__ __forceinline__ void trace_pack_body(d2 *xch, uint64_t *acc1, const F &fft, const TraceParams &p, int tid) {
   constexpr int N = F::N, M = F::M, T = F::THREADS, LOGN = F::LOGM + 1;
   static_assert(F::XCH_SLOTS * sizeof(d2) >= N * sizeof(uint64_t), "the exchange buffer stages one polynomial of torus words");
-  const uint64_t *c = in + (size_t)blockIdx.x * (N + 1);
+  const int t = p.t, base_bit = p.base_bit;
   uint64_t off = 1ull << (63 - t * base_bit);
   for (int i = 0; i < t; i++) off += 1ull << (63 - i * base_bit);
   const RoundCtx scale(0x1p-64 / (double)M);
   const size_t entry_sz = (size_t)t * 2 * M;
-  // the LWE mask as the polynomial whose constant term pairs with the key (src/keyswitch.c:530-533); coefficient x = m T + tid resp. M + m T + tid
-  uint64_t al[8], ah[8];
-#pragma unroll
-  for (int m = 0; m < 8; m++) {
-    const int x = m * T + tid;
-    al[m] = x == 0 ? c[0] : 0 - c[N - x];
-    ah[m] = 0 - c[M - x];           // coefficient M + x: N - (M + x)
-    acc1[x] = x == 0 ? c[N] : 0;
-    acc1[M + x] = 0;
-  }
-  F::sync();
-  uint64_t *st = reinterpret_cast<uint64_t *>(xch);
-#pragma unroll 1
-  for (int j = 0; j < LOGN; j++) {
-    const int gen = (N >> j) + 1;
-    uint64_t dd_lo[8], dd_hi[8];
-    {
-      // component a: scatter through the staging buffer, read back in coefficient order, keep only the digit words
-#pragma unroll
-      for (int m = 0; m < 8; m++) {
-        const int i0 = (m * T + tid) * gen, i1 = (M + m * T + tid) * gen;
-        st[i0 & (N - 1)] = (i0 & N) ? (0 - al[m]) : al[m];
-        st[i1 & (N - 1)] = (i1 & N) ? (0 - ah[m]) : ah[m];
-      }
-      F::sync();
-#pragma unroll
-      for (int m = 0; m < 8; m++) { dd_lo[m] = st[m * T + tid] + off; dd_hi[m] = st[M + m * T + tid] + off; }
-      F::sync();
-    }
-    {
-      // component b: acc1 += acc1(X^gen) in place (read everything, barrier, scatter-add: word (i gen) mod N has this one writer)
-      uint64_t v_lo[8], v_hi[8];
-#pragma unroll
-      for (int m = 0; m < 8; m++) { v_lo[m] = acc1[m * T + tid]; v_hi[m] = acc1[M + m * T + tid]; }
-      F::sync();
-#pragma unroll
-      for (int m = 0; m < 8; m++) {
-        const int i0 = (m * T + tid) * gen, i1 = (M + m * T + tid) * gen;
-        acc1[i0 & (N - 1)] += (i0 & N) ? (0 - v_lo[m]) : v_lo[m];
-        acc1[i1 & (N - 1)] += (i1 & N) ? (0 - v_hi[m]) : v_hi[m];
-      }
-      F::sync();
-    }
-    double o_re[2][8], o_im[2][8];
-#pragma unroll
-    for (int cc = 0; cc < 2; cc++)
-#pragma unroll
-      for (int m = 0; m < 8; m++) { o_re[cc][m] = 0.0; o_im[cc][m] = 0.0; }
-    ks_rows_rt<F>(dd_lo, dd_hi, o_re, o_im, xch, fft, key + (size_t)j * entry_sz, t, base_bit, tid);
-    fft.inverse(o_re[0], o_im[0], xch, tid);
+  uint64_t al[8], ah[8];   // component a, coefficient x = m T + tid resp. M + m T + tid
+  int steps = LOGN;
+  if (p.kind == TRACE_KIND_PACK) {
+    // the LWE mask as the polynomial whose constant term pairs with the key (src/keyswitch.c:530-533)
+    const uint64_t *c = p.in + (size_t)blockIdx.x * (N + 1);
 #pragma unroll
     for (int m = 0; m < 8; m++) {
-      al[m] -= round_mod_2_64(o_re[0][m], scale);
-      ah[m] -= round_mod_2_64(o_im[0][m], scale);
-    }
-    fft.inverse(o_re[1], o_im[1], xch, tid);
-#pragma unroll
-    for (int m = 0; m < 8; m++) {
-      acc1[m * T + tid] -= round_mod_2_64(o_re[1][m], scale);
-      acc1[M + m * T + tid] -= round_mod_2_64(o_im[1][m], scale);
+      const int x = m * T + tid;
+      al[m] = x == 0 ? c[0] : 0 - c[N - x];
+      ah[m] = 0 - c[M - x];           // coefficient M + x: N - (M + x)
+      acc1[x] = x == 0 ? c[N] : 0;
+      acc1[M + x] = 0;
     }
     F::sync();
+  } else {
+    // merge r of output o at level lvl:  E = P[r], O = X^s P[r + cnt], s = N / 2^lvl;  acc = U = E + O, v = V = E - O;  acc += KeySwitch_(log2 N - lvl)(V(X^(2^lvl + 1)))
+    const int lvl = p.lvl;
+    const unsigned cnt = 1u << p.cnt_log, o = blockIdx.x >> p.cnt_log, r = blockIdx.x & (cnt - 1);
+    const size_t first = (size_t)o * 2 * cnt + r;
+    uint64_t va_lo[8], va_hi[8], vb_lo[8], vb_hi[8];
+    if (lvl == 1) {
+      // the leaves are LWE samples first and first + cnt, embedded on the fly (s = M): O.a[x] = -a'[x + M] = in.a[M - x], O.a[M + x] = a'[x], O.b = in.b X^M.  A sample
+      // past the end is read as sample 0 and masked to zero: no load depends on a branch
+      const uint64_t k0 = first < (size_t)p.total ? ~0ull : 0ull, k1 = first + cnt < (size_t)p.total ? ~0ull : 0ull;
+      const uint64_t *c0 = p.in + (k0 ? first : 0) * (N + 1), *c1 = p.in + (k1 ? first + cnt : 0) * (N + 1);
+#pragma unroll
+      for (int m = 0; m < 8; m++) {
+        const int x = m * T + tid;
+        const uint64_t e_lo = (x == 0 ? c0[0] : 0 - c0[N - x]) & k0, e_hi = (0 - c0[M - x]) & k0;
+        const uint64_t o_lo = c1[M - x] & k1, o_hi = (x == 0 ? c1[0] : 0 - c1[N - x]) & k1;
+        const uint64_t eb = x == 0 ? c0[N] & k0 : 0, ob = x == 0 ? c1[N] & k1 : 0;
+        al[m] = e_lo + o_lo; va_lo[m] = e_lo - o_lo;
+        ah[m] = e_hi + o_hi; va_hi[m] = e_hi - o_hi;
+        acc1[x] = eb; vb_lo[m] = eb;
+        acc1[M + x] = ob; vb_hi[m] = 0 - ob;
+      }
+    } else {
+      // s <= N / 4: only the low half wraps, X^s p [x] = -p[x - s + N] for x < s
+      const int s = N >> lvl;
+      const uint64_t *s0 = p.in + first * (2 * N), *s1 = s0 + (size_t)cnt * (2 * N);
+#pragma unroll
+      for (int m = 0; m < 8; m++) {
+        const int x = m * T + tid;
+        const uint64_t a0 = s1[(x - s) & (N - 1)], b0 = s1[N + ((x - s) & (N - 1))];
+        const uint64_t oa_lo = x < s ? 0 - a0 : a0, ob_lo = x < s ? 0 - b0 : b0, oa_hi = s1[M + x - s], ob_hi = s1[N + M + x - s];
+        const uint64_t ea_lo = s0[x], ea_hi = s0[M + x], eb_lo = s0[N + x], eb_hi = s0[N + M + x];
+        al[m] = ea_lo + oa_lo; va_lo[m] = ea_lo - oa_lo;
+        ah[m] = ea_hi + oa_hi; va_hi[m] = ea_hi - oa_hi;
+        acc1[x] = eb_lo + ob_lo; vb_lo[m] = eb_lo - ob_lo;
+        acc1[M + x] = eb_hi + ob_hi; vb_hi[m] = eb_hi - ob_hi;
+      }
+    }
+    F::sync();
+    trace_step<F, true>(al, ah, acc1, va_lo, va_hi, vb_lo, vb_hi, (1 << lvl) + 1, xch, fft, p.key + (size_t)(LOGN - lvl) * entry_sz, t, base_bit, off, scale, tid);
+    steps = p.tail;
   }
-  uint64_t *o = out + (size_t)blockIdx.x * (2 * N);
+#pragma unroll 1
+  for (int j = 0; j < steps; j++) trace_step<F, false>(al, ah, acc1, al, ah, al, ah, (N >> j) + 1, xch, fft, p.key + (size_t)j * entry_sz, t, base_bit, off, scale, tid);
+  uint64_t *o = p.out + (size_t)blockIdx.x * (2 * N);
 #pragma unroll
   for (int m = 0; m < 8; m++) {
     o[m * T + tid] = al[m];
@@ -189,17 +267,6 @@ __device__ __forceinline__ void rlwe_priv_keyswitch_body(d2 *xch, const F &fft, 
   }
 }
 
-enum { TRACE_KIND_PACK = 0, TRACE_KIND_PRIV = 1, TRACE_KIND_GADGET = 2 };
-
-struct TraceParams {
-  const d2 *__restrict__ key;   // the first entry the call uses: [log2 N or 2][t][2][M] complex
-  const d2 *__restrict__ tw;
-  const uint64_t *in;           // kind 0: [count][N + 1]; 1: [count][2][N]; 2: [count][l][2][N]
-  uint64_t *out;                // kind 0, 1: [count][2][N] (kind 1: may be `in`)
-  d2 *sel;                      // kind 2: [count][2l][2][M] complex
-  int kind, t, base_bit, l;
-};
-
 template <class F>
 __global__ __launch_bounds__(F::THREADS, 1) void trace_conversions_kernel(TraceParams p) {
   __shared__ __attribute__((aligned(16))) d2 xch[F::XCH_SLOTS];
@@ -207,7 +274,7 @@ __global__ __launch_bounds__(F::THREADS, 1) void trace_conversions_kernel(TraceP
   const int tid = threadIdx.x;
   F fft;
   fft.init(p.tw, tid);
-  if (p.kind == TRACE_KIND_PACK) trace_pack_body<F>(xch, acc1, fft, p.key, p.in, p.out, p.t, p.base_bit, tid);
+  if (p.kind == TRACE_KIND_PACK || p.kind == TRACE_KIND_MANY) trace_pack_body<F>(xch, acc1, fft, p, tid);
   else rlwe_priv_keyswitch_body<F>(xch, fft, p.key, p.key + (size_t)p.t * 2 * F::M, p.in, p.out, p.t, p.base_bit, p.kind == TRACE_KIND_GADGET ? p.sel : nullptr, p.l, tid);
 }
 

@@ -208,6 +208,17 @@ def trace_plan(kind, N, t, base_bit, entries, entry0=0, l=1, count=1):
     return dict(entries_read=int(plan[0]), teams=int(plan[1]), threads=int(plan[2]), forwards=int(plan[3]), inverses=int(plan[4]), key_bytes=int(plan[5]))
 
 
+def tlwe_trace_pack_many_plan(N, t, base_bit, entries, total, log_per, entry0=0, workspace_bytes=0):
+    """What a tlwe_trace_pack_many call will do (no device needed; the launcher's own decision): dict(outputs, launches_per_round, teams, merge_steps, tail_steps,
+    outputs_per_round, rounds, pool_bytes) -- TRLWE samples written, launches of a round (one per level; one for log_per = 0), teams of a round's first launch, merges
+    (2^log_per - 1) and trace steps (log2 N - log_per) per output, outputs per round of the pool, rounds, pool bytes of a round.  workspace_bytes = 0: the current
+    set_tlwe_pack_workspace.  include/mosfhet_hip.h: mosfhet_hip_tlwe_trace_pack_many_plan."""
+    plan = (C.c_longlong * 8)()
+    _check(lib().mosfhet_hip_tlwe_trace_pack_many_plan(int(N), int(t), int(base_bit), int(entries), int(entry0), int(total), int(log_per), C.c_longlong(int(workspace_bytes)), plan))
+    return dict(outputs=int(plan[0]), launches_per_round=int(plan[1]), teams=int(plan[2]), merge_steps=int(plan[3]), tail_steps=int(plan[4]), outputs_per_round=int(plan[5]),
+                rounds=int(plan[6]), pool_bytes=int(plan[7]))
+
+
 class LinearMap:
     """The cleartext weights of y = W x + bias on the device (mosfhet_hip_linear_t): made by Engine.linear_dense / Engine.linear_sparse."""
 
@@ -1032,6 +1043,16 @@ class Engine:
         if out is None:
             out = self.empty(count, 2, tks.N)
         _check(lib().mosfhet_hip_tlwe_trace_pack_batch(self.h, tks.h, int(entry0), _ptr(out) if count else None, _ptr(ct) if count else None, count, self._stream()))
+        return out
+
+    def tlwe_trace_pack_many(self, tks, ct, log_per, entry0=0, out=None):
+        """2^log_per samples per output by the trace: ct [total][N + 1] under the extracted ring key -> [ceil(total / 2^log_per)][2][N], sample j of an output with
+        phase N m_j at coefficient j N / 2^log_per; the same log2 N trace keys as tlwe_trace_pack, whose words log_per = 0 gives."""
+        total, log_per = ct.shape[0], int(log_per)
+        if out is None:
+            out = self.empty(-(-total // (1 << log_per)) if 0 <= log_per < 31 else 0, 2, tks.N)
+        _check(lib().mosfhet_hip_tlwe_trace_pack_many_batch(self.h, tks.h, int(entry0), _ptr(out) if total else None, _ptr(ct) if total else None, int(total), log_per,
+                                                            self._stream()))
         return out
 
     def trlwe_rlwe_priv_keyswitch(self, tks, ct, entry0=0, out=None):
