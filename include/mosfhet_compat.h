@@ -343,6 +343,21 @@ void mosfhet_trlwe_unpack(TLWE *out /*[total]*/, TRLWE *in /*[ceil(total / per)]
  * mosfhet_hip_trlwe_unpack_keyswitch_batch): out[j] of dimension n, the same words as the two steps one after the other. */
 void mosfhet_trlwe_unpack_keyswitch(TLWE *out /*[total]*/, TRLWE *in /*[ceil(total / per)]*/, uint64_t total, uint64_t per, TLWE_KS_Key ksk);
 
+/* A cleartext polynomial-weight layer on `count` independent packed inputs in one call (new; mosfhet_hip_trlwe_linear_batch): out[b rows_out + j] = (0, bias[j]) +
+ * sum_i in[b rows_in + i] * W[j][i], the loop of trlwe_to_DFT, trlwe_DFT_mul_by_polynomial / trlwe_DFT_mul_addto_by_polynomial (src/trlwe.c:491-505) and trlwe_from_DFT
+ * over the rows of W [rows_out][rows_in][N] signed 64-bit coefficients; bias [rows_out][N] torus words or NULL.  k = 1, N = 1024, 2048 or 4096 (the inputs').  One upload,
+ * one call, one download; synchronous; aborts on error; primary device. */
+void mosfhet_trlwe_linear(TRLWE *out /*[count * rows_out]*/, TRLWE *in /*[count * rows_in]*/, const int64_t *W, const Torus *bias /* or NULL */, int rows_out, int rows_in,
+                          int count);
+/* ... followed by trlwe_extract_tlwe(., idx) (src/trlwe.c:540-552; new; mosfhet_hip_trlwe_linear_extract_batch): out[b rows_out + j] of dimension N. */
+void mosfhet_trlwe_linear_extract(TLWE *out /*[count * rows_out]*/, TRLWE *in /*[count * rows_in]*/, const int64_t *W, const Torus *bias /* or NULL */, int rows_out,
+                                  int rows_in, int count, int idx);
+/* The weight polynomial of an inner product over `per` packed values (new; pure host integer code): poly[0] = w[0], poly[N - c stride] = -w[c] for 1 <= c < per, zero
+ * elsewhere, so that coefficient 0 of the negacyclic product with a sample that holds value x[c] at coefficient c stride is sum_c w[c] x[c].  stride = 1 suits the
+ * outputs of mosfhet_tlwe_pack; stride = N / 2^L suits those of mosfhet_tlwe_trace_pack_many with log_per = L, whose phases carry the trace's factor N (the sum is then
+ * N sum_c w[c] m[c]).  Returns 0, or -1 (nothing written) for a null pointer, per < 1, stride < 1, an N that is no power of two or per * stride > N. */
+int mosfhet_polylinear_dot_layout(int64_t *poly /*[N]*/, const int64_t *w /*[per]*/, int per, int N, int stride);
+
 /* ---- flat helpers used by the Python binding and bench.py (new) ----
  * Generate a whole bootstrap / key-switch key in the flat torus-domain layouts of mosfhet_hip.h. */
 void mosfhet_gen_bootstrap_key_flat(Torus *out /*[n][(k+1)l][k+1][N]*/, TRGSW_Key out_key, TLWE_Key in_key);

@@ -486,6 +486,56 @@ int mosfhet_hip_linear_keyswitch_functional_bootstrap_batch(mosfhet_hip_ctx_t ct
                                                             uint64_t *d_out, const uint64_t *d_tv, int tv_count, const uint64_t *d_in /*[count][rows_in][kN+1]*/,
                                                             int count, int torus_base, int extract, void *stream);
 
+/* ---- cleartext polynomial-weight linear layers on batches of PACKED TRLWE samples (capi_polylinear.inc; kernel: polylinear_body, trace_kernels.h) ----
+ * The reference's trlwe_to_DFT, trlwe_DFT_mul_by_polynomial / trlwe_DFT_mul_addto_by_polynomial (src/trlwe.c:491-505), trlwe_from_DFT and trlwe_extract_tlwe
+ * (:540-552) for `count` independent inferences at once.  One negacyclic product with the right weight polynomial is an inner product over up to N packed values,
+ * a 1-D convolution, a rotation or a slot sum (mosfhet_polylinear_dot_layout, mosfhet_compat.h, lays out the first).  Ring N in {1024, 2048, 4096}, k = 1.
+ * A handle holds, per output row j, an ordered list of entries (col_e, val_e) -- val_e a cleartext polynomial of N signed 64-bit coefficients -- and an optional
+ * bias polynomial of N torus words.  With F = polynomial_torus_to_DFT (a weight is converted as (double)(int64_t), exactly as a torus word is),
+ * G = polynomial_DFT_to_torus with the general rounding (exact for every double) and mul_addto = polynomial_mul_addto_DFT (two FMAs per part, input first):
+ *     acc_a = acc_b = +0.0
+ *     for e in the entries of row j, in the stored order:   acc_a = mul_addto(acc_a, F(in[b][col_e].a), F(val_e));   acc_b likewise with .b
+ *     out[b][j] = (G(acc_a), G(acc_b) + bias[j])           (mod 2^64)
+ * Any int64 weight is accepted.  No word depends on count, a sample's position in the batch, the workspace, the rounds, the device, the launch geometry or on whether
+ * the handle was made dense or sparse with the same ordered entries.  The weights are transformed on the device at creation and kept in the engine's slot order,
+ * read-only afterwards; no DFT-domain data crosses this interface. */
+typedef struct mosfhet_hip_polylinear *mosfhet_hip_polylinear_t;
+/* src/trlwe.c:491-505 as a dense layer: h_W [rows_out][rows_in][N], h_bias [rows_out][N] or NULL; row j's entries are col = 0 .. rows_in - 1 ascending, zero
+ * polynomials are not skipped */
+int mosfhet_hip_polylinear_create_dense(mosfhet_hip_ctx_t ctx, mosfhet_hip_polylinear_t *out, const int64_t *h_W, const uint64_t *h_bias, int rows_out, int rows_in, int N);
+/* src/trlwe.c:491-505 as a sparse map: CSR over polynomial blocks, h_row_ptr [rows_out+1] (row_ptr[0] = 0, monotone), h_col [nnz], h_val [nnz][N]; the rules of
+ * mosfhet_hip_linear_create_sparse: columns may be unsorted and may repeat within a row (they add, in the stored order), rows may be empty ((0, bias)), columns outside
+ * [0, rows_in) are refused */
+int mosfhet_hip_polylinear_create_sparse(mosfhet_hip_ctx_t ctx, mosfhet_hip_polylinear_t *out, const int *h_row_ptr, const int *h_col, const int64_t *h_val,
+                                         const uint64_t *h_bias, int rows_out, int rows_in, int N);
+int mosfhet_hip_polylinear_destroy(mosfhet_hip_polylinear_t lin);
+/* info: rows_out, rows_in, nnz (-1 dense), N, device bytes, form (0 dense, 1 sparse) */
+int mosfhet_hip_polylinear_info(mosfhet_hip_polylinear_t lin, long long info[6]);
+/* a copy for another context (device), after the pattern of mosfhet_hip_linear_clone */
+int mosfhet_hip_polylinear_clone(mosfhet_hip_ctx_t ctx_other, mosfhet_hip_polylinear_t lin, mosfhet_hip_polylinear_t *out);
+/* src/trlwe.c:491-505 between trlwe_to_DFT and trlwe_from_DFT over a batch: d_in [count][rows_in][2][N] -> d_out [count][rows_out][2][N].  Asynchronous on `stream`,
+ * never synchronises; the transformed inputs of a round live in the calling thread's pool (one stream per host thread; capturable once a call of the same size has run),
+ * bounded by mosfhet_hip_set_tlwe_pack_workspace: a larger batch runs in rounds of whole batch elements.  count == 0 is OK.  MOSFHET_HIP_EINVAL, before any HIP call: null
+ * ctx / lin, count < 0, null buffers with count > 0, lin of another context, d_out overlapping d_in, a round whose teams do not fit one launch, a workspace bound below
+ * one batch element. */
+int mosfhet_hip_trlwe_linear_batch(mosfhet_hip_ctx_t ctx, mosfhet_hip_polylinear_t lin, uint64_t *d_out /*[count][rows_out][2][N]*/,
+                                   const uint64_t *d_in /*[count][rows_in][2][N]*/, int count, void *stream);
+/* The same words followed by trlwe_extract_tlwe(., idx) (src/trlwe.c:540-552), 0 <= idx < N (else MOSFHET_HIP_EINVAL): a[i] = out.a[idx - i] for i <= idx,
+ * -out.a[N + idx - i] above, b = out.b[idx].  The TRLWE result is never written; d_out is the [..][N+1] layout the key switch takes next. */
+int mosfhet_hip_trlwe_linear_extract_batch(mosfhet_hip_ctx_t ctx, mosfhet_hip_polylinear_t lin, uint64_t *d_out /*[count][rows_out][N+1]*/, const uint64_t *d_in, int idx,
+                                           int count, void *stream);
+/* src/trlwe.c:491-505 and :540-552 into the calling thread's pool, then the body of mosfhet_hip_keyswitch_functional_bootstrap_batch on the count * rows_out samples:
+ * the same words as the two calls one after the other.  d_out [count * rows_out][N+1] (extract = 1) or [count * rows_out][2][N] (0); tv_count is 1 or
+ * count * rows_out.  The handle's ring must be the key-switch key's input (else MOSFHET_HIP_EINVAL).  One stream per host thread. */
+int mosfhet_hip_trlwe_linear_keyswitch_functional_bootstrap_batch(mosfhet_hip_ctx_t ctx, mosfhet_hip_polylinear_t lin, mosfhet_hip_ksk_t ksk, mosfhet_hip_bsk_t bsk,
+                                                                  uint64_t *d_out, const uint64_t *d_tv, int tv_count, const uint64_t *d_in /*[count][rows_in][2][N]*/,
+                                                                  int idx, int count, int torus_base, int extract, void *stream);
+/* What a call of src/trlwe.c:491-505 over a batch will do (pure; no device; the function the launcher decides with).  nnz = -1: dense.  `cus` is reserved (checked >= 1).
+ * workspace_bytes = 0: the current setting.  plan = { teams of the main launch of a round, batch elements per round, rounds, pool bytes per round, forward transforms
+ * per call = count * rows_in * 2, inverse transforms per call = count * rows_out * 2, weight bytes one team reads, input bytes one team reads (sparse: of the mean row,
+ * rounded up) } */
+int mosfhet_hip_trlwe_linear_plan(int N, int rows_out, int rows_in, long long nnz, int count, int extract, int cus, long long workspace_bytes, long long plan[8]);
+
 /* ---- batches of LWE samples packed into TRLWE samples: trlwe_full_packing_keyswitch over a batch (src/keyswitch.c:195-227) ----
  * pk: an FFT key-switch key set with entries = n_in (mosfhet_hip_trlwe_ksk_create / _generate; entry i switches from the constant polynomial s_in[i] -- the key
  * trlwe_new_full_packing_KS_key makes), any t and base_bit, N in {1024, 2048, 4096}.

@@ -631,3 +631,56 @@ void free_trgsw_array(void *p, int count) {
   for (int i = 0; i < count; i++) free_trgsw(((void **)p)[i]);
   free(p);
 }
+
+/* y = W x + bias with cleartext POLYNOMIAL weights on `count` independent packed inputs (mosfhet_hip_trlwe_linear_batch / _extract_batch; trlwe_DFT_mul_by_polynomial and
+ * trlwe_DFT_mul_addto_by_polynomial of src/trlwe.c:491-505 row by row): idx < 0: out_trlwe[b rows_out + j]; else out_tlwe[b rows_out + j] = trlwe_extract_tlwe(., idx). */
+static void trlwe_linear(const char *name, TRLWE *out_trlwe, TLWE *out_tlwe, TRLWE *in, const int64_t *W, const Torus *bias, int rows_out, int rows_in, int count, int idx) {
+  const int N = in[0]->b->N;
+  const size_t ins = (size_t)count * (size_t)rows_in, outs = (size_t)count * (size_t)rows_out, one = idx < 0 ? (size_t)2 * N : (size_t)N + 1;
+  const size_t in_w = ins * 2 * (size_t)N, out_w = outs * one;
+  Torus *h = (Torus *)mc_hstage_alloc(sizeof(Torus) * (in_w > out_w ? in_w : out_w)), *d = (Torus *)mc_stage_alloc(sizeof(Torus) * (in_w + out_w));
+  for (size_t o = 0; o < ins; o++) {
+    need_of(in[o]->k == 1 && in[o]->b->N == N, name, "an input is not a k = 1 TRLWE sample of the first input's ring");
+    mc_trlwe_to_flat(h + o * 2 * (size_t)N, in[o]);
+  }
+  mc_dev_copy(d, h, sizeof(Torus) * in_w, HIP_H2D);
+  mosfhet_hip_polylinear_t lin = NULL;
+  check_rc(mosfhet_hip_polylinear_create_dense(ectx(), &lin, W, bias, rows_out, rows_in, N), name);
+  if (idx < 0)
+    check_rc(mosfhet_hip_trlwe_linear_batch(ectx(), lin, d + in_w, d, count, NULL), name);
+  else
+    check_rc(mosfhet_hip_trlwe_linear_extract_batch(ectx(), lin, d + in_w, d, idx, count, NULL), name);
+  mc_dev_copy(h, d + in_w, sizeof(Torus) * out_w, HIP_D2H);   /* (synchronous: the handle is idle when it is destroyed) */
+  mosfhet_hip_polylinear_destroy(lin);
+  for (size_t o = 0; o < outs; o++) {
+    const Torus *w = h + o * one;
+    if (idx < 0) {
+      need_of(out_trlwe[o]->k == 1 && out_trlwe[o]->b->N == N, name, "an output is not a k = 1 TRLWE sample of the inputs' ring");
+      mc_trlwe_from_flat(out_trlwe[o], w);
+    } else {
+      need_of(out_tlwe[o]->n == N, name, "an output sample has the wrong dimension (N)");
+      memcpy(out_tlwe[o]->a, w, sizeof(Torus) * (size_t)N);
+      out_tlwe[o]->b = w[N];
+    }
+  }
+  mc_hstage_free(h);
+}
+
+void mosfhet_trlwe_linear(TRLWE *out, TRLWE *in, const int64_t *W, const Torus *bias, int rows_out, int rows_in, int count) {
+  need(out && in && W && rows_out >= 1 && rows_in >= 1 && count >= 1, "mosfhet_trlwe_linear: bad argument");
+  trlwe_linear("mosfhet_trlwe_linear", out, NULL, in, W, bias, rows_out, rows_in, count, -1);
+}
+
+void mosfhet_trlwe_linear_extract(TLWE *out, TRLWE *in, const int64_t *W, const Torus *bias, int rows_out, int rows_in, int count, int idx) {
+  need(out && in && W && rows_out >= 1 && rows_in >= 1 && count >= 1 && idx >= 0, "mosfhet_trlwe_linear_extract: bad argument");
+  trlwe_linear("mosfhet_trlwe_linear_extract", NULL, out, in, W, bias, rows_out, rows_in, count, idx);
+}
+
+/* pure host integer code: X^(N - c stride) * X^(c stride) = X^N = -1, so the entry at N - c stride is negated */
+int mosfhet_polylinear_dot_layout(int64_t *poly, const int64_t *w, int per, int N, int stride) {
+  if (!poly || !w || per < 1 || stride < 1 || N < 1 || (N & (N - 1)) || (long long)per * stride > N) return -1;
+  memset(poly, 0, sizeof(int64_t) * (size_t)N);
+  poly[0] = w[0];
+  for (int c = 1; c < per; c++) poly[N - c * stride] = (int64_t)(0 - (uint64_t)w[c]);
+  return 0;
+}

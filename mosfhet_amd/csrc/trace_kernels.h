@@ -27,6 +27,15 @@
 //                                  sel != nullptr: team c l + i takes gadget row i of input c and writes rows i (the switched sample) and l + i (the row itself) of
 //                                  selector c in the DFT domain, each polynomial exactly as torus_to_dft_kernel transforms the torus words (torus_to_double,
 //                                  fft.forward); no torus-domain word is written.  The tail is mode 3's, rolled for the same reason.
+//   polylinear_body<F>           kind 4 (mosfhet_hip_trlwe_linear_batch / _extract_batch; trlwe_DFT_mul_by_polynomial / trlwe_DFT_mul_addto_by_polynomial, src/trlwe.c:491-505,
+//                                  trlwe_from_DFT and trlwe_extract_tlwe :540-552): one team per (batch element b, output row j).  The inputs were transformed by
+//                                  torus_to_dft_kernel into the pool, the weight polynomials at creation, both in slot order: the team walks row j's entries in the
+//                                  stored order, loads the two input components and the weight row 16 bytes per lane, and accumulates the pair in registers with the
+//                                  two-FMA complex multiply-add of ks_rows_rt (input first, weight second); then two inverse transforms, the general rounding, the
+//                                  bias, and either the TRLWE sample or the extracted LWE row written straight from the registers.  It has no LDS exchange of its
+//                                  own: the only barriers are the inverse transforms'.  It lives here because this kernel already holds what it needs -- row
+//                                  multiply-accumulate from global memory, the two inverse transforms, the general rounding -- and its register need (two
+//                                  accumulator pairs and three operands) is below the other kinds': the kernel's allocation does not move.
 // Launch bound 1 like trlwe_fft_keyswitch_kernel: digit words, accumulator and the two product pairs are live together.
 #pragma once
 #include <stdint.h>
@@ -36,7 +45,7 @@
 
 namespace mosfhet {
 
-enum { TRACE_KIND_PACK = 0, TRACE_KIND_PRIV = 1, TRACE_KIND_GADGET = 2, TRACE_KIND_MANY = 3 };
+enum { TRACE_KIND_PACK = 0, TRACE_KIND_PRIV = 1, TRACE_KIND_GADGET = 2, TRACE_KIND_MANY = 3, TRACE_KIND_POLYLINEAR = 4 };
 
 struct TraceParams {
   const d2 *__restrict__ key;   // the first entry the call uses: [log2 N or 2][t][2][M] complex
@@ -48,6 +57,12 @@ struct TraceParams {
   int kind, t, base_bit, l;
   int lvl, cnt_log, tail, total;   // kind 3: merge level (>= 1), log2 of the results per output it writes (cnt = n / 2^lvl), trace steps behind the merge (last level only),
                                    // samples `in` holds at level 1 (a sample index >= total stands for the all-zero sample)
+  // kind 4: key = the weight polynomials [entries][M] complex, out = [teams][2][N] or, idx >= 0, [teams][N + 1]
+  const d2 *__restrict__ xin;        // the transformed inputs of the round [count][rows_in][2][M] complex
+  const int *__restrict__ row_ptr;   // [rows_out + 1]
+  const int *__restrict__ col;       // [entries]
+  const uint64_t *__restrict__ bias; // [rows_out][N] or null
+  int rows_out, rows_in, idx;        // idx < 0: the TRLWE sample; else trlwe_extract_tlwe(., idx)
 };
 
 // One step on the accumulator (a in al / ah, b in acc1):  acc += KeySwitch_entry(v(X^gen)).  The permutation of ga_eval_automorphism (scatter through LDS, signs by bit N
@@ -267,6 +282,66 @@ __device__ __forceinline__ void rlwe_priv_keyswitch_body(d2 *xch, const F &fft, 
   }
 }
 
+// out[b][j] = G(sum_e F(in[b][col_e]) (.) F(val_e)) + (0, bias[j]), the sum in the stored order of row j's entries from +0.0; blockIdx.x = b rows_out + j
+template <class F>
+__device__ __forceinline__ void polylinear_body(d2 *xch, const F &fft, const TraceParams &p, int tid) {
+  constexpr int N = F::N, M = F::M, T = F::THREADS;
+  const unsigned b = blockIdx.x / (unsigned)p.rows_out, j = blockIdx.x % (unsigned)p.rows_out;
+  const d2 *__restrict__ x = p.xin + (size_t)b * p.rows_in * (2 * M);
+  double o_re[2][8], o_im[2][8];
+#pragma unroll
+  for (int cc = 0; cc < 2; cc++)
+#pragma unroll
+    for (int m = 0; m < 8; m++) { o_re[cc][m] = 0.0; o_im[cc][m] = 0.0; }
+  const int end = p.row_ptr[j + 1];
+#pragma unroll 1
+  for (int e = p.row_ptr[j]; e < end; e++) {
+    const d2 *__restrict__ w = p.key + (size_t)e * M;
+    const d2 *__restrict__ xa = x + (size_t)p.col[e] * (2 * M);
+    d2 wv[8], a[8], bb[8];
+#pragma unroll
+    for (int m = 0; m < 8; m++) { wv[m] = w[m * T + tid]; a[m] = xa[m * T + tid]; bb[m] = xa[M + m * T + tid]; }
+#pragma unroll
+    for (int m = 0; m < 8; m++) {
+      o_re[0][m] = __builtin_fma(-a[m].y, wv[m].y, __builtin_fma(a[m].x, wv[m].x, o_re[0][m]));
+      o_im[0][m] = __builtin_fma(a[m].y, wv[m].x, __builtin_fma(a[m].x, wv[m].y, o_im[0][m]));
+      o_re[1][m] = __builtin_fma(-bb[m].y, wv[m].y, __builtin_fma(bb[m].x, wv[m].x, o_re[1][m]));
+      o_im[1][m] = __builtin_fma(bb[m].y, wv[m].x, __builtin_fma(bb[m].x, wv[m].y, o_im[1][m]));
+    }
+  }
+  const RoundCtx scale(0x1p-64 / (double)M);
+  const uint64_t *bias = p.bias ? p.bias + (size_t)j * N : nullptr;
+  const int idx = p.idx;
+  uint64_t *o = p.out + (size_t)blockIdx.x * (idx < 0 ? (size_t)2 * N : (size_t)N + 1);
+  fft.inverse(o_re[0], o_im[0], xch, tid);
+#pragma unroll
+  for (int m = 0; m < 8; m++) {
+    const int c0 = m * T + tid, c1 = M + c0;
+    const uint64_t lo = round_mod_2_64(o_re[0][m], scale), hi = round_mod_2_64(o_im[0][m], scale);
+    if (idx < 0) {
+      o[c0] = lo;
+      o[c1] = hi;
+    } else {
+      // trlwe_extract_tlwe: a[i] = out.a[idx - i] for i <= idx, -out.a[N + idx - i] above: coefficient c goes to word (idx - c) mod N, negated when c > idx
+      o[(idx - c0) & (N - 1)] = c0 <= idx ? lo : 0 - lo;
+      o[(idx - c1) & (N - 1)] = c1 <= idx ? hi : 0 - hi;
+    }
+  }
+  fft.inverse(o_re[1], o_im[1], xch, tid);
+#pragma unroll
+  for (int m = 0; m < 8; m++) {
+    const int c0 = m * T + tid, c1 = M + c0;
+    const uint64_t lo = round_mod_2_64(o_re[1][m], scale) + (bias ? bias[c0] : 0), hi = round_mod_2_64(o_im[1][m], scale) + (bias ? bias[c1] : 0);
+    if (idx < 0) {
+      o[N + c0] = lo;
+      o[N + c1] = hi;
+    } else {
+      if (c0 == idx) o[N] = lo;
+      if (c1 == idx) o[N] = hi;
+    }
+  }
+}
+
 template <class F>
 __global__ __launch_bounds__(F::THREADS, 1) void trace_conversions_kernel(TraceParams p) {
   __shared__ __attribute__((aligned(16))) d2 xch[F::XCH_SLOTS];
@@ -275,6 +350,7 @@ __global__ __launch_bounds__(F::THREADS, 1) void trace_conversions_kernel(TraceP
   F fft;
   fft.init(p.tw, tid);
   if (p.kind == TRACE_KIND_PACK || p.kind == TRACE_KIND_MANY) trace_pack_body<F>(xch, acc1, fft, p, tid);
+  else if (p.kind == TRACE_KIND_POLYLINEAR) polylinear_body<F>(xch, fft, p, tid);
   else rlwe_priv_keyswitch_body<F>(xch, fft, p.key, p.key + (size_t)p.t * 2 * F::M, p.in, p.out, p.t, p.base_bit, p.kind == TRACE_KIND_GADGET ? p.sel : nullptr, p.l, tid);
 }
 

@@ -219,6 +219,40 @@ def tlwe_trace_pack_many_plan(N, t, base_bit, entries, total, log_per, entry0=0,
                 rounds=int(plan[6]), pool_bytes=int(plan[7]))
 
 
+def trlwe_linear_plan(N, rows_out, rows_in, count, nnz=-1, extract=False, cus=256, workspace_bytes=0):
+    """What a trlwe_linear / trlwe_linear_extract call will do (no device needed; the launcher's own decision): dict(teams, per_round, rounds, pool_bytes, forwards,
+    inverses, weight_bytes, input_bytes) -- teams of a round's main launch (one per batch element and output row), batch elements per round of the pool, rounds, pool
+    bytes of a round, forward (count * rows_in * 2) and inverse (count * rows_out * 2) transforms per call, weight and input bytes one team reads (sparse: of the mean
+    row).  workspace_bytes = 0: the current set_tlwe_pack_workspace.  include/mosfhet_hip.h: mosfhet_hip_trlwe_linear_plan."""
+    plan = (C.c_longlong * 8)()
+    _check(lib().mosfhet_hip_trlwe_linear_plan(int(N), int(rows_out), int(rows_in), C.c_longlong(int(nnz)), int(count), int(bool(extract)), int(cus),
+                                               C.c_longlong(int(workspace_bytes)), plan))
+    return dict(teams=int(plan[0]), per_round=int(plan[1]), rounds=int(plan[2]), pool_bytes=int(plan[3]), forwards=int(plan[4]), inverses=int(plan[5]),
+                weight_bytes=int(plan[6]), input_bytes=int(plan[7]))
+
+
+class PolyLinearMap:
+    """The cleartext polynomial weights of y = W x + bias on packed TRLWE samples, transformed, on the device (mosfhet_hip_polylinear_t): made by
+    Engine.polylinear_create_dense / Engine.polylinear_create_sparse."""
+
+    def __init__(self, engine, handle):
+        self.engine, self.h = engine, handle
+        i = self.info()
+        self.rows_out, self.rows_in, self.N = i["rows_out"], i["rows_in"], i["N"]
+
+    def info(self):
+        v = (C.c_longlong * 6)()
+        _check(lib().mosfhet_hip_polylinear_info(self.h, v))
+        return dict(rows_out=int(v[0]), rows_in=int(v[1]), nnz=int(v[2]), N=int(v[3]), nbytes=int(v[4]), form=("dense", "sparse")[v[5]])
+
+    def close(self):
+        if self.h:
+            lib().mosfhet_hip_polylinear_destroy(self.h)
+            self.h = None
+
+    free = close
+
+
 class LinearMap:
     """The cleartext weights of y = W x + bias on the device (mosfhet_hip_linear_t): made by Engine.linear_dense / Engine.linear_sparse."""
 
@@ -1021,6 +1055,70 @@ class Engine:
             out = self.empty(count, lin.rows_out, bsk.k * bsk.N + 1) if extract else self.empty(count, lin.rows_out, bsk.k + 1, bsk.N)
         _check(lib().mosfhet_hip_linear_keyswitch_functional_bootstrap_batch(self.h, lin.h, ksk.h, bsk.h, _ptr(out), _ptr(tv), self._tv(tv, bsk, samples), _ptr(ct), count,
                                                                              torus_base, int(extract), self._stream()))
+        return out
+
+    # ---- cleartext polynomial-weight linear layers on packed TRLWE samples (include/mosfhet_hip.h: mosfhet_hip_polylinear_*, mosfhet_hip_trlwe_linear_batch) ----
+    @staticmethod
+    def _poly_bias(bias, rows_out, N):
+        if bias is None:
+            return None, None
+        b = np.ascontiguousarray(np.asarray(bias).astype(np.uint64, copy=False))
+        assert b.shape == (rows_out, N), "bias: one polynomial of N torus words per output row"
+        return b, b.ctypes.data_as(C.c_void_p)
+
+    def polylinear_create_dense(self, W, bias=None):
+        """Handle of a dense layer: W [rows_out][rows_in][N] int64 coefficients of the cleartext weight polynomials, bias [rows_out][N] torus words or None."""
+        W = np.ascontiguousarray(W, dtype=np.int64)
+        assert W.ndim == 3
+        keep, pb = self._poly_bias(bias, W.shape[0], W.shape[2])
+        h = C.c_void_p()
+        _check(lib().mosfhet_hip_polylinear_create_dense(self.h, C.byref(h), W.ctypes.data_as(C.c_void_p), pb, int(W.shape[0]), int(W.shape[1]), int(W.shape[2])))
+        return PolyLinearMap(self, h)
+
+    def polylinear_create_sparse(self, row_ptr, col, val, rows_in, N, bias=None):
+        """Handle of a sparse map in CSR over polynomial blocks: row_ptr [rows_out + 1], col [nnz], val [nnz][N] (columns may be unsorted or repeat within a row --
+        they add in the stored order; rows may be empty)."""
+        row_ptr = np.ascontiguousarray(row_ptr, dtype=np.int32)
+        col, val = np.ascontiguousarray(col, dtype=np.int32), np.ascontiguousarray(val, dtype=np.int64).reshape(-1, int(N))
+        rows_out = len(row_ptr) - 1
+        assert len(col) == len(val) and (rows_out < 0 or len(col) >= row_ptr[-1])
+        keep, pb = self._poly_bias(bias, rows_out, int(N))
+        h = C.c_void_p()
+        _check(lib().mosfhet_hip_polylinear_create_sparse(self.h, C.byref(h), row_ptr.ctypes.data_as(C.c_void_p), col.ctypes.data_as(C.c_void_p),
+                                                          val.ctypes.data_as(C.c_void_p), pb, int(rows_out), int(rows_in), int(N)))
+        return PolyLinearMap(self, h)
+
+    def clone_polylinear(self, lin):
+        """A copy of a PolyLinearMap of another engine for this one (mosfhet_hip_polylinear_clone)."""
+        h = C.c_void_p()
+        _check(lib().mosfhet_hip_polylinear_clone(self.h, lin.h, C.byref(h)))
+        return PolyLinearMap(self, h)
+
+    def trlwe_linear(self, lin, ct, out=None):
+        """out[b][j] = (0, bias[j]) + sum_e ct[b][col_e] * val_e, negacyclic products through the transform in the stored order: ct [count][rows_in][2][N] ->
+        [count][rows_out][2][N]."""
+        count = ct.shape[0]
+        if out is None:
+            out = self.empty(count, lin.rows_out, 2, lin.N)
+        _check(lib().mosfhet_hip_trlwe_linear_batch(self.h, lin.h, _ptr(out) if count else None, _ptr(ct) if count else None, count, self._stream()))
+        return out
+
+    def trlwe_linear_extract(self, lin, ct, idx=0, out=None):
+        """trlwe_linear followed by trlwe_extract_tlwe(., idx), the TRLWE result never written: ct [count][rows_in][2][N] -> [count][rows_out][N + 1]."""
+        count = ct.shape[0]
+        if out is None:
+            out = self.empty(count, lin.rows_out, lin.N + 1)
+        _check(lib().mosfhet_hip_trlwe_linear_extract_batch(self.h, lin.h, _ptr(out) if count else None, _ptr(ct) if count else None, int(idx), count, self._stream()))
+        return out
+
+    def trlwe_linear_keyswitch_functional_bootstrap(self, lin, ksk, bsk, tv, ct, torus_base, idx=0, extract=True, out=None):
+        """trlwe_linear_extract, then keyswitch_functional_bootstrap on the count * rows_out results, in one call: ct [count][rows_in][2][N] -> [count][rows_out][N + 1]
+        (extract) or [count][rows_out][2][N]; tv one test vector or one per result."""
+        count, samples = ct.shape[0], ct.shape[0] * lin.rows_out
+        if out is None:
+            out = self.empty(count, lin.rows_out, bsk.k * bsk.N + 1) if extract else self.empty(count, lin.rows_out, bsk.k + 1, bsk.N)
+        _check(lib().mosfhet_hip_trlwe_linear_keyswitch_functional_bootstrap_batch(self.h, lin.h, ksk.h, bsk.h, _ptr(out), _ptr(tv), self._tv(tv, bsk, samples), _ptr(ct),
+                                                                                   int(idx), count, torus_base, int(extract), self._stream()))
         return out
 
     # ---- LWE batches packed into TRLWE samples (include/mosfhet_hip.h: mosfhet_hip_tlwe_pack_batch) ----
