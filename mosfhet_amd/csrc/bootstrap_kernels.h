@@ -128,23 +128,26 @@ __device__ __forceinline__ uint64_t rot_coeff(const uint64_t *poly, int i, int a
 //   mode PACKED (Bg compile-time, L*Bg <= 32): one 32-bit word per coefficient holding exactly those bits;
 //   mode SPLIT  (Bg compile-time, L*Bg  > 32, at most 16 bits of digits reach below bit 32): the high dword per
 //               coefficient plus one shared 32-bit word with the low-level digits of both coefficients;
-//   mode WIDE   (run-time Bg or anything else): the full 64-bit words.
+//   mode WIDE   (run-time Bg or anything else): the full 64-bit words;
+//   mode RAW    (Bg = 2^8, asked for by the caller: SET_1's throughput bootstrap, cmux_digits<.., SF>): the high dword of (d + offset) as it is -- no shift, no
+//               flip; digit lv is the reference's formula on byte 3 - lv, one byte-selecting add and the conversion.
 template <int X>
 struct kCeilLog2 { static constexpr int value = X <= 1 ? 0 : 1 + kCeilLog2<(X + 1) / 2>::value; };
 template <>
 struct kCeilLog2<1> { static constexpr int value = 0; };
 
-template <int L, int BG>
+template <int L, int BG, bool RAW = false>
 struct Digits {
+  static_assert(!RAW || (BG == 8 && L * BG <= 32), "the raw layout: byte fields of the high dword");
   static constexpr int lo_levels() {
     int n = 0;
     for (int lv = 0; lv < L; lv++) n += (BG > 0 && 64 - (lv + 1) * BG < 32) ? 1 : 0;
     return n;
   }
-  static constexpr bool kPacked = (BG > 0) && (L * BG <= 32);
-  static constexpr bool kSplit = (BG > 0) && !kPacked && (lo_levels() * BG <= 16);
+  static constexpr bool kPacked = (BG > 0) && (L * BG <= 32) && !RAW;
+  static constexpr bool kSplit = (BG > 0) && !kPacked && !RAW && (lo_levels() * BG <= 16);
   static constexpr int kLo = lo_levels(), kHi = L - lo_levels();
-  using word_t = typename std::conditional<kPacked || kSplit, uint32_t, uint64_t>::type;
+  using word_t = typename std::conditional<kPacked || kSplit || RAW, uint32_t, uint64_t>::type;
 
   // u - 2^(BG-1) for a BG-bit field u is the field with its top bit flipped, read as a signed number: the packed words keep
   // the fields top-bit-flipped (one XOR per word) and digit() is a single signed bit-field extract.
@@ -164,7 +167,11 @@ struct Digits {
     return m;
   }
   static __device__ __forceinline__ void pack(word_t &w_lo, word_t &w_hi, uint32_t &ext, uint64_t dd_lo, uint64_t dd_hi) {
-    if constexpr (kPacked) {
+    if constexpr (RAW) {
+      w_lo = (uint32_t)(dd_lo >> 32);
+      w_hi = (uint32_t)(dd_hi >> 32);
+      ext = 0;
+    } else if constexpr (kPacked) {
       w_lo = (uint32_t)(dd_lo >> (64 - L * BG)) ^ packed_flip();
       w_hi = (uint32_t)(dd_hi >> (64 - L * BG)) ^ packed_flip();
       ext = 0;
@@ -182,7 +189,9 @@ struct Digits {
   }
   // signed digit `lv` of the coefficient (half = 0: j, 1: j + M) as a double (exact)
   static __device__ __forceinline__ double digit(word_t w, uint32_t ext, int half, int lv, int Bg_bit) {
-    if constexpr (kPacked) {
+    if constexpr (RAW) {
+      return (double)((int)((w >> (32 - (lv + 1) * BG)) & ((1u << BG) - 1)) - (1 << (BG - 1)));
+    } else if constexpr (kPacked) {
       return (double)(int)__builtin_amdgcn_sbfe(w, (unsigned)((L - 1 - lv) * BG), (unsigned)BG);   // the builtin is typed unsigned
     } else if constexpr (kSplit) {
       if (lv < kHi) return (double)(int)__builtin_amdgcn_sbfe(w, (unsigned)(32 - (lv + 1) * BG), (unsigned)BG);
@@ -223,11 +232,53 @@ __device__ __forceinline__ uint64_t digit_source(uint64_t rotated, uint64_t home
     return add_offset<BG>(rotated - home_word, off);
   }
 }
-template <class F, int L, int BG, bool NEG = false>
+// SF (with NEG; Digits' RAW layout): the high dword of that word without a compare and without a carry chain.  With abar2 = a_lo + (flip ? N : 0) and
+// s = j - abar2, the source index is s & (N - 1) and "negate the staged word" is bit log2 N of s (flip = 0: s < 0; flip = 1: s mod 2N = src + N, the bit is set
+// exactly when src >= 0), as a lane mask m = 0 / ~0 by one signed bit-field extract.  (+-v) + h = (v + (h ^ M)) ^ M mod 2^64 with M = m widened (M = ~0: v + ~h =
+// v - h - 1, whose complement is h - v), and since the offset's low dword is zero the high dword of the sum is ((v + (h ^ M)).hi ^ m) + off.hi: one v_xad_u32.
+__device__ __forceinline__ uint32_t digit_source_hi(uint64_t staged, uint64_t home_word, int s, int log2n, uint64_t off) {
+  const uint32_t m = (uint32_t)__builtin_amdgcn_sbfe((uint32_t)s, (unsigned)log2n, 1u);
+  const uint64_t y = add_pairs(staged, home_word ^ (((uint64_t)m << 32) | m));
+  uint32_t hi;   // (spelled in assembly: the compiler has no pattern for the xor-add; the wave-uniform offset is read from a scalar register, as neg_rounded's constant)
+  asm("v_xad_u32 %0, %1, %2, %3" : "=v"(hi) : "v"((uint32_t)(y >> 32)), "v"(m), "s"((uint32_t)(off >> 32)));
+  return hi;
+}
+template <class F, int L, int BG, bool NEG = false, bool SF = false>
 __device__ __forceinline__ void cmux_digits(typename Digits<L, BG>::word_t (&w_lo)[8], typename Digits<L, BG>::word_t (&w_hi)[8],
                                             uint32_t (&ext)[8], const uint64_t (&al)[8], const uint64_t (&ah)[8],
                                             const uint64_t *home, d2 *xch, int a_lo, bool flip, uint64_t off, int t) {
   constexpr int N = F::N, M = F::M, T = F::THREADS;
+  static_assert(!SF || (NEG && BG == 8 && L * BG <= 32 && F::THREADS == 64), "the sign-free form relies on the negated home word and on an offset with a zero low dword");
+  if constexpr (SF) {
+    int abar2 = a_lo + (flip ? N : 0);
+    asm volatile("" : "+s"(abar2));   // (as a_lo below)
+    if (home) {
+#pragma unroll
+      for (int m = 0; m < 8; m++) {
+        const int j = m * T + t, s_lo = j - abar2, s_hi = j + M - abar2;
+        w_lo[m] = digit_source_hi(home[s_lo & (N - 1)], home[j], s_lo, F::LOGM + 1, off);
+        w_hi[m] = digit_source_hi(home[s_hi & (N - 1)], home[j + M], s_hi, F::LOGM + 1, off);
+        ext[m] = 0;
+      }
+    } else {
+      uint64_t *st = reinterpret_cast<uint64_t *>(xch);
+#pragma unroll
+      for (int m = 0; m < 8; m++) {
+        st[m * T + t] = al[m];
+        st[M + m * T + t] = ah[m];
+      }
+      F::sync();
+#pragma unroll
+      for (int m = 0; m < 8; m++) {
+        const int j = m * T + t, s_lo = j - abar2, s_hi = j + M - abar2;
+        w_lo[m] = digit_source_hi(st[s_lo & (N - 1)], al[m], s_lo, F::LOGM + 1, off);
+        w_hi[m] = digit_source_hi(st[s_hi & (N - 1)], ah[m], s_hi, F::LOGM + 1, off);
+        ext[m] = 0;
+      }
+      F::sync();
+    }
+    return;
+  }
   using D = Digits<L, BG>;
   // keep the rotated LDS addresses from being hoisted out of the component loop (they would be spilled there)
   asm volatile("" : "+s"(a_lo));
@@ -261,12 +312,13 @@ __device__ __forceinline__ void cmux_digits(typename Digits<L, BG>::word_t (&w_l
 // The L rows of component p: digits -> forward transform -> MAC against key rows p*L .. p*L+L-1.
 // The key row's component 0 is loaded under the last transform pass, component 1 under the MAC of component 0.
 // KEY_LDS: the key rows are in LDS (external_product_ldskey_kernel): no early fetch into registers, each component's slots are read where they are used
-template <class F, int L, int BG, bool KEY_LDS = false>
+// RAW: the digit words are in Digits' raw layout (cmux_digits<.., SF>)
+template <class F, int L, int BG, bool KEY_LDS = false, bool RAW = false>
 __device__ __forceinline__ void cmux_rows(const typename Digits<L, BG>::word_t (&w_lo)[8], const typename Digits<L, BG>::word_t (&w_hi)[8],
                                           const uint32_t (&ext)[8], int p, double (&o_re)[2][8], double (&o_im)[2][8], d2 *xch,
                                           const F &fft, const d2 *__restrict__ bkrow, int Bg_bit, int t) {
   constexpr int M = F::M, T = F::THREADS;
-  using D = Digits<L, BG>;
+  using D = Digits<L, BG, RAW>;
   // two levels are unrolled (the next row's digit conversion and first pass overlap the MAC tail; no scratch at l = 2), more stay rolled
   constexpr int kUnroll = (L <= 2 && !KEY_LDS) ? L : 1;   // KEY_LDS: rolled -- unrolled, the LDS reads of both rows are hoisted and spill
 #pragma unroll kUnroll

@@ -15,6 +15,12 @@
 #define MOSFHET_PBS_NEGACC 1
 #endif
   constexpr bool kNegAcc = MOSFHET_PBS_NEGACC && F::N == 1024 && L == 2 && BG == 8 && !kReduce && !BYC;
+  // On top of it the digit words take the rotation's sign and index from one 11-bit subtraction, apply the sign by two XORs around the carry-free add, and keep
+  // the high dword as it is: raw byte fields, the reference's digit formula (cmux_digits: SF; Digits: RAW).  Same digits.  The one switch (0: the kernels as before):
+#ifndef MOSFHET_PBS_SIGNFREE
+#define MOSFHET_PBS_SIGNFREE 1
+#endif
+  constexpr bool kSignFree = kNegAcc && MOSFHET_PBS_SIGNFREE;
   // (G > 1: one slice per team, its xch and acc1 side by side, so that every LDS address of a team is the G = 1 address plus one team offset)
   constexpr int kSlice = (int)sizeof(d2) * F::XCH_SLOTS + (int)sizeof(uint64_t) * N;
   __shared__ __attribute__((aligned(16))) d2 xch_all[G == 1 ? F::XCH_SLOTS : G * kSlice / (int)sizeof(d2)];
@@ -94,11 +100,11 @@
       for (int q = 0; q < 2; q++) {
         typename Digits<L, BG>::word_t w_lo[8], w_hi[8];
         uint32_t ext[8];
-        cmux_digits<F, L, BG, kNegAcc>(w_lo, w_hi, ext, al, ah, q ? acc1 : nullptr, xch, a_lo, flip, off, t);
+        cmux_digits<F, L, BG, kNegAcc, kSignFree>(w_lo, w_hi, ext, al, ah, q ? acc1 : nullptr, xch, a_lo, flip, off, t);
         // rows two at a time where the transform keeps its pass twiddles in LDS (tools/ab/pbs_ab.hip -DAB_LTW instantiates that) -- at two wavefronts per SIMD
         // the pairs gain nothing here (experiments/README.md round 4): production instantiates pbs_kernel on the register-twiddle transforms
         if constexpr (F::kLtw && F::kForward2 && L % 2 == 0) cmux_rows2<F, L, BG>(w_lo, w_hi, ext, q, o_re, o_im, xch, fft, bkrow, Bg_bit, t);
-        else cmux_rows<F, L, BG>(w_lo, w_hi, ext, q, o_re, o_im, xch, fft, bkrow, Bg_bit, t);
+        else cmux_rows<F, L, BG, false, kSignFree>(w_lo, w_hi, ext, q, o_re, o_im, xch, fft, bkrow, Bg_bit, t);
         if constexpr (BYC) {
           // (the slot addresses are made inside the step: hoisted out of the loop over the key they would hold 32 registers and spill, like cmux_digits' rotated addresses)
           int here = 0;

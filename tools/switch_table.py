@@ -66,7 +66,11 @@ OTHER = {"MOSFHET_HIPCC_EXTRA": "mosfhet_amd/build.py: extra hipcc flags (part o
          "MOSFHET_BENCH_SHARE_GPU": "bench.py test hook: every rank on device 0", "MOSFHET_BENCH_FORCE_DIST": "bench.py test hook: process group at world size 1",
          "MOSFHET_PBS_NEGACC": "compile-time, pbs_body.inc, default 1: SET_1's throughput bootstrap kernels keep their accumulators negated (carry-free digit and tail adds, "
                                "component b added by the LDS unit); `-DMOSFHET_PBS_NEGACC=0` through `MOSFHET_HIPCC_EXTRA` or `tools/ab/run_ab.py build` compiles the "
-                               "plain form, instruction for instruction the kernels before it; same bits: `tests/test_pbs_acc_forms.py`"}
+                               "plain form, instruction for instruction the kernels before it; same bits: `tests/test_pbs_acc_forms.py`",
+         "MOSFHET_PBS_SIGNFREE": "compile-time, pbs_body.inc, default 1, on top of `MOSFHET_PBS_NEGACC`: the same kernels take the rotation's sign and source index from one "
+                                 "11-bit subtraction, apply the sign by two XORs around the carry-free add and cut the digits from the raw high dword; "
+                                 "`-DMOSFHET_PBS_SIGNFREE=0` compiles the compare / conditional-negate / flipped-field form, instruction for instruction the kernels before it; "
+                                 "same bits: `tests/test_pbs_sign_forms.py`"}
 
 
 def in_source():
