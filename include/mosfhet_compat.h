@@ -342,6 +342,12 @@ void mosfhet_trlwe_unpack(TLWE *out /*[total]*/, TRLWE *in /*[ceil(total / per)]
 /* ... and tlwe_keyswitch (src/tlwe.c:289-303; ksk: N -> n, what tlwe_new_KS_key returns) of every extracted sample in the same call (new;
  * mosfhet_hip_trlwe_unpack_keyswitch_batch): out[j] of dimension n, the same words as the two steps one after the other. */
 void mosfhet_trlwe_unpack_keyswitch(TLWE *out /*[total]*/, TRLWE *in /*[ceil(total / per)]*/, uint64_t total, uint64_t per, TLWE_KS_Key ksk);
+/* The same two with a geometry (new; mosfhet_hip_trlwe_unpack_strided_batch, mosfhet_hip_trlwe_unpack_strided_keyswitch_batch): out[o per + j] =
+ * extract(in[o], first + j stride), first < N, stride >= 1, first + (per - 1) stride <= N - 1 (no wrapped index) -- what opens the outputs of
+ * mosfhet_tlwe_trace_pack_many (first 0, stride N / n).  One upload, one call, one download. */
+void mosfhet_trlwe_unpack_strided(TLWE *out /*[total]*/, TRLWE *in /*[ceil(total / per)]*/, uint64_t total, uint64_t per, uint64_t first, uint64_t stride);
+void mosfhet_trlwe_unpack_strided_keyswitch(TLWE *out /*[total]*/, TRLWE *in /*[ceil(total / per)]*/, uint64_t total, uint64_t per, uint64_t first, uint64_t stride,
+                                            TLWE_KS_Key ksk);
 
 /* A cleartext polynomial-weight layer on `count` independent packed inputs in one call (new; mosfhet_hip_trlwe_linear_batch): out[b rows_out + j] = (0, bias[j]) +
  * sum_i in[b rows_in + i] * W[j][i], the loop of trlwe_to_DFT, trlwe_DFT_mul_by_polynomial / trlwe_DFT_mul_addto_by_polynomial (src/trlwe.c:491-505) and trlwe_from_DFT

@@ -583,6 +583,28 @@ int mosfhet_hip_unpack_keyswitch_functional_bootstrap_batch(mosfhet_hip_ctx_t ct
                                                             int tv_count, const uint64_t *d_in /*[outputs][2][N]*/, int total, int per, int torus_base, int extract,
                                                             void *stream);
 int mosfhet_hip_trlwe_unpack_plan(int N, int n_out, int t, int base_bit, int compressed, int total, int per, int cus, long long plan[8]);
+/* The same three calls and the plan with a geometry (per, first, stride): sample o per + j is trlwe_extract_tlwe(in[o], first + j stride), word for word -- what
+ * opens the samples mosfhet_hip_tlwe_trace_pack_many_batch puts at coefficients j N / 2^L (first 0, stride N / 2^L) and the valid outputs of a packed convolution.
+ * 1 <= per, 0 <= first < N, 1 <= stride and first + (per - 1) stride <= N - 1, evaluated in 64 bits: coefficient indices do not wrap; anything else returns
+ * MOSFHET_HIP_EINVAL with a message naming the argument, before any HIP call.  The calls above are (first 0, stride 1) of the same bodies.  Same contracts as their
+ * twins: asynchronous, the same pool slots and ONE STREAM PER HOST THREAD, the same refusals, the same capturability, total == 0 is OK.  The words depend on d_in, the
+ * geometry and the sample index only.  The plan's fields do not depend on first or stride: it equals mosfhet_hip_trlwe_unpack_plan at the same (total, per)
+ * whenever the geometry is accepted. */
+int mosfhet_hip_trlwe_unpack_strided_batch(mosfhet_hip_ctx_t ctx, uint64_t *d_out /*[total][N+1]*/, const uint64_t *d_in /*[outputs][2][N]*/, int N, int total, int per,
+                                           int first, int stride, void *stream);
+int mosfhet_hip_trlwe_unpack_strided_keyswitch_batch(mosfhet_hip_ctx_t ctx, mosfhet_hip_ksk_t ksk, uint64_t *d_out /*[total][n_out+1]*/,
+                                                     const uint64_t *d_in /*[outputs][2][N]*/, int total, int per, int first, int stride, void *stream);
+int mosfhet_hip_unpack_strided_keyswitch_functional_bootstrap_batch(mosfhet_hip_ctx_t ctx, mosfhet_hip_ksk_t ksk, mosfhet_hip_bsk_t bsk, uint64_t *d_out,
+                                                                    const uint64_t *d_tv, int tv_count, const uint64_t *d_in /*[outputs][2][N]*/, int total, int per,
+                                                                    int first, int stride, int torus_base, int extract, void *stream);
+int mosfhet_hip_trlwe_unpack_strided_plan(int N, int n_out, int t, int base_bit, int compressed, int total, int per, int first, int stride, int cus, long long plan[8]);
+/* mosfhet_hip_trlwe_linear_batch into the calling thread's pool, then mosfhet_hip_unpack_strided_keyswitch_functional_bootstrap_batch on its count * rows_out results,
+ * `per` samples of each: the same words as the two calls one after the other.  d_out [count * rows_out * per][N+1] (extract = 1) or [..][2][N] (0); tv_count is 1
+ * or count * rows_out * per.  The handle's ring must be the key-switch key's input ring (else MOSFHET_HIP_EINVAL).  One stream per host thread. */
+int mosfhet_hip_trlwe_linear_unpack_keyswitch_functional_bootstrap_batch(mosfhet_hip_ctx_t ctx, mosfhet_hip_polylinear_t lin, mosfhet_hip_ksk_t ksk, mosfhet_hip_bsk_t bsk,
+                                                                         uint64_t *d_out, const uint64_t *d_tv, int tv_count,
+                                                                         const uint64_t *d_in /*[count][rows_in][2][N]*/, int per, int first, int stride, int count,
+                                                                         int torus_base, int extract, void *stream);
 
 /* ---- the LWE -> TRLWE switch by the trace and the gadget -> TRGSW conversion over batches (src/keyswitch.c:526-546, 65-97, 559-572) ----
  * tks: an FFT key-switch key set (mosfhet_hip_trlwe_ksk_create / _generate), any t and base_bit, k = 1, N in {1024, 2048, 4096}; `entry0` names the first entry a call

@@ -265,3 +265,40 @@ extern "C" int mosfhet_hip_trlwe_linear_keyswitch_functional_bootstrap_batch(mos
   if ((rc = polylinear_run(ctx, lin, plan, y, d_in, idx, count, pick(ctx, stream)))) return rc;
   return mosfhet_hip_keyswitch_functional_bootstrap_batch(ctx, ksk, bsk, d_out, d_tv, tv_count, y, (int)samples, torus_base, extract, stream);
 }
+
+// mosfhet_hip_trlwe_linear_batch into the calling thread's pool (slot POOL_POLYLINEAR_OUT, here [count][rows_out][2][N]), then the body of
+// mosfhet_hip_unpack_strided_keyswitch_functional_bootstrap_batch on the count * rows_out results, `per` samples of each: pure composition, the words of the two calls
+// one after the other.
+extern "C" int mosfhet_hip_trlwe_linear_unpack_keyswitch_functional_bootstrap_batch(mosfhet_hip_ctx_t ctx, mosfhet_hip_polylinear_t lin, mosfhet_hip_ksk_t ksk,
+                                                                                    mosfhet_hip_bsk_t bsk, uint64_t *d_out, const uint64_t *d_tv, int tv_count,
+                                                                                    const uint64_t *d_in, int per, int first, int stride, int count, int torus_base,
+                                                                                    int extract, void *stream) {
+  const char *who = "trlwe_linear_unpack_keyswitch_bootstrap";
+  if (!ctx) return fail(MOSFHET_HIP_EINVAL, "%s: null ctx", who);
+  if (!lin) return fail(MOSFHET_HIP_EINVAL, "%s: null lin", who);
+  if (!ksk) return fail(MOSFHET_HIP_EINVAL, "%s: null ksk", who);
+  if (!bsk) return fail(MOSFHET_HIP_EINVAL, "%s: null bsk", who);
+  int rc = unpack_scalars(who, 0, per, first, stride);
+  if (rc) return rc;
+  PolyLinearPlan plan;
+  bool run;
+  rc = polylinear_check(who, ctx, lin, nullptr, d_in, -1, false, count, false, &plan, &run);
+  if (rc || !run) return rc;
+  if (!d_out || !d_tv) return fail(MOSFHET_HIP_EINVAL, "%s: null buffer", who);
+  // the checks of the body below on the two keys and the geometry, BEFORE anything is queued
+  if (ksk->n_in != bsk->k * bsk->N || ksk->n_out != bsk->n || ksk->b_word != ksk->n_out)
+    return fail(MOSFHET_HIP_EINVAL, "%s: key-switch key is %d -> %d, expected %d -> %d", who, ksk->n_in, ksk->n_out, bsk->k * bsk->N, bsk->n);
+  if (bsk->k != 1) return fail(MOSFHET_HIP_EINVAL, "%s: packed inputs have one mask polynomial (k = 1), the bootstrap key has k = %d", who, bsk->k);
+  if (ksk->n_in != lin->N) return fail(MOSFHET_HIP_EINVAL, "%s: the handle's ring is N = %d, the key-switch key opens samples of a ring of %d", who, lin->N, ksk->n_in);
+  if (ksk->ctx != ctx) return fail(MOSFHET_HIP_EINVAL, "%s: ksk belongs to another context (device %d)", who, ksk->device);
+  if (per > lin->N) return fail(MOSFHET_HIP_EINVAL, "%s: per = %d (1 .. N = %d)", who, per, lin->N);
+  if ((rc = unpack_geometry(who, lin->N, per, first, stride))) return rc;
+  const long long inputs = (long long)count * lin->rows_out, samples = inputs * per;
+  if (samples > 0x7fffffffLL) return fail(MOSFHET_HIP_EINVAL, "%s: count = %d x rows_out = %d x per = %d samples do not fit an int", who, count, lin->rows_out, per);
+  if (tv_count != 1 && tv_count != samples) return fail(MOSFHET_HIP_EINVAL, "%s: tv_count = %d (1 or count * rows_out * per = %lld)", who, tv_count, samples);
+  HIP_TRY(hipSetDevice(ctx->device));
+  uint64_t *y = nullptr;
+  if ((rc = pool_get(ctx->device, POOL_POLYLINEAR_OUT, (size_t)inputs * 2 * (size_t)lin->N, &y))) return rc;
+  if ((rc = polylinear_run(ctx, lin, plan, y, d_in, -1, count, pick(ctx, stream)))) return rc;
+  return unpack_keyswitch_bootstrap_body(who, ctx, ksk, bsk, d_out, d_tv, tv_count, y, (int)samples, per, first, stride, torus_base, extract, stream);
+}

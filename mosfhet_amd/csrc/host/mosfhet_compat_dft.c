@@ -497,8 +497,8 @@ void mosfhet_tlwe_pack(TRLWE *out, TLWE *in, uint64_t total, uint64_t per, TRLWE
 
 /* trlwe_extract_tlwe (src/trlwe.c:540-552) over a batch in one call (mosfhet_hip_trlwe_unpack_batch), the inverse layout of mosfhet_tlwe_pack: out[o per + j] =
  * extract(in[o], j); with a key, tlwe_keyswitch of every extracted sample as well (mosfhet_hip_trlwe_unpack_keyswitch_batch: the batch of N + 1 words per sample is
- * never written). */
-static void trlwe_unpack(const char *name, TLWE *out, TRLWE *in, uint64_t total, uint64_t per, TLWE_KS_Key ksk) {
+ * never written).  (first, stride): sample j of an input is the coefficient first + j stride; (0, 1) for the calls without a geometry. */
+static void trlwe_unpack(const char *name, TLWE *out, TRLWE *in, uint64_t total, uint64_t per, uint64_t first, uint64_t stride, TLWE_KS_Key ksk) {
   const int N = in[0]->b->N, n_res = ksk ? out[0]->n : N;
   const size_t inputs = (size_t)((total + per - 1) / per);
   const size_t in_w = inputs * 2 * (size_t)N, out_w = (size_t)total * ((size_t)n_res + 1);
@@ -509,9 +509,10 @@ static void trlwe_unpack(const char *name, TLWE *out, TRLWE *in, uint64_t total,
   }
   mc_dev_copy(d, h, sizeof(Torus) * in_w, HIP_H2D);
   if (ksk)
-    check_rc(mosfhet_hip_trlwe_unpack_keyswitch_batch(ectx(), (mosfhet_hip_ksk_t)mc_key_here(ksk->device, MC_KEY_KSK), d + in_w, d, (int)total, (int)per, NULL), name);
+    check_rc(mosfhet_hip_trlwe_unpack_strided_keyswitch_batch(ectx(), (mosfhet_hip_ksk_t)mc_key_here(ksk->device, MC_KEY_KSK), d + in_w, d, (int)total, (int)per, (int)first, (int)stride,
+                                                              NULL), name);
   else
-    check_rc(mosfhet_hip_trlwe_unpack_batch(ectx(), d + in_w, d, N, (int)total, (int)per, NULL), name);
+    check_rc(mosfhet_hip_trlwe_unpack_strided_batch(ectx(), d + in_w, d, N, (int)total, (int)per, (int)first, (int)stride, NULL), name);
   mc_dev_copy(h, d + in_w, sizeof(Torus) * out_w, HIP_D2H);
   for (uint64_t j = 0; j < total; j++) {
     const Torus *w = h + (size_t)j * ((size_t)n_res + 1);
@@ -524,12 +525,26 @@ static void trlwe_unpack(const char *name, TLWE *out, TRLWE *in, uint64_t total,
 
 void mosfhet_trlwe_unpack(TLWE *out, TRLWE *in, uint64_t total, uint64_t per) {
   need(out && in && total >= 1 && total <= 0x7fffffffu && per >= 1 && per <= 4096, "mosfhet_trlwe_unpack: bad argument");
-  trlwe_unpack("mosfhet_trlwe_unpack", out, in, total, per, NULL);
+  trlwe_unpack("mosfhet_trlwe_unpack", out, in, total, per, 0, 1, NULL);
 }
 
 void mosfhet_trlwe_unpack_keyswitch(TLWE *out, TRLWE *in, uint64_t total, uint64_t per, TLWE_KS_Key ksk) {
   need(out && in && ksk && ksk->device && total >= 1 && total <= 0x7fffffffu && per >= 1 && per <= 4096, "mosfhet_trlwe_unpack_keyswitch: bad argument");
-  trlwe_unpack("mosfhet_trlwe_unpack_keyswitch", out, in, total, per, ksk);
+  trlwe_unpack("mosfhet_trlwe_unpack_keyswitch", out, in, total, per, 0, 1, ksk);
+}
+
+/* ... with a geometry: out[o per + j] = extract(in[o], first + j stride); the ranges are the device call's (mosfhet_hip_trlwe_unpack_strided_batch), which names what it
+ * refuses */
+void mosfhet_trlwe_unpack_strided(TLWE *out, TRLWE *in, uint64_t total, uint64_t per, uint64_t first, uint64_t stride) {
+  need(out && in && total >= 1 && total <= 0x7fffffffu && per >= 1 && per <= 4096 && first < 4096 && stride >= 1 && stride <= 0x7fffffffu,
+       "mosfhet_trlwe_unpack_strided: bad argument");
+  trlwe_unpack("mosfhet_trlwe_unpack_strided", out, in, total, per, first, stride, NULL);
+}
+
+void mosfhet_trlwe_unpack_strided_keyswitch(TLWE *out, TRLWE *in, uint64_t total, uint64_t per, uint64_t first, uint64_t stride, TLWE_KS_Key ksk) {
+  need(out && in && ksk && ksk->device && total >= 1 && total <= 0x7fffffffu && per >= 1 && per <= 4096 && first < 4096 && stride >= 1 && stride <= 0x7fffffffu,
+       "mosfhet_trlwe_unpack_strided_keyswitch: bad argument");
+  trlwe_unpack("mosfhet_trlwe_unpack_strided_keyswitch", out, in, total, per, first, stride, ksk);
 }
 
 /* src/trlwe.c:775-781: out = KeySwitch_{ks_key}(in(X^gen)); ks_key switches from key(X^gen) back to key (any entry of a key set) */

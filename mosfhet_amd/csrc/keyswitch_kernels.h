@@ -27,14 +27,17 @@
 namespace mosfhet {
 
 // Where a table key switch reads its ciphertexts.  Plain: rows of words, `in_stride` apart.  Packed (packed != nullptr): TRLWE samples [..][2][N]; ciphertext c
-// is sample (first + c) % per of input (first + c) / per (unpack_kernels.h) -- the kernels that re-orient the input read the packed words directly.
+// is sample (first + c) % per of input (first + c) / per (unpack_kernels.h), sample j sitting at coefficient coef0 + j coef_stride -- the kernels that re-orient
+// the input read the packed words directly.
 struct KsSource {
   const uint64_t *in = nullptr;
   size_t in_stride = 0;
   const uint64_t *packed = nullptr;
-  int N = 0, per = 1, first = 0;
+  int N = 0, per = 1, first = 0, coef0 = 0, coef_stride = 1;
   static KsSource rows(const uint64_t *in, size_t in_stride) { KsSource s; s.in = in; s.in_stride = in_stride; return s; }
-  static KsSource trlwe(const uint64_t *packed, int N, int per, int first) { KsSource s; s.packed = packed; s.N = N; s.per = per; s.first = first; return s; }
+  static KsSource trlwe(const uint64_t *packed, int N, int per, int first, int coef0 = 0, int coef_stride = 1) {
+    KsSource s; s.packed = packed; s.N = N; s.per = per; s.first = first; s.coef0 = coef0; s.coef_stride = coef_stride; return s;
+  }
   KsSource from(int c) const {   // the source of ciphertexts c, c + 1, ...
     KsSource s = *this;
     if (packed) s.first = first + c; else s.in = in + (size_t)c * in_stride;
@@ -277,7 +280,7 @@ inline hipError_t launch_tlwe_keyswitch_nw(const uint64_t *ksk, uint64_t *out, s
   // in[count][n_in + 1] -> inT[n_in + 1][Bp]; from packed samples inT is written directly, column by column (n_in = N, the b word is row N)
   if (src.packed)
     hipLaunchKernelGGL(trlwe_unpack_kernel, dim3((unsigned)((count + UNPACK_THREADS - 1) / UNPACK_THREADS), (unsigned)((in_words + UNPACK_COL_WORDS - 1) / UNPACK_COL_WORDS)),
-                       dim3(UNPACK_THREADS), 0, s, ws.inT, src.packed, src.N, src.per, src.first, count, (size_t)1, Bp, 0);
+                       dim3(UNPACK_THREADS), 0, s, ws.inT, src.packed, src.N, src.per, src.first, src.coef0, src.coef_stride, count, (size_t)1, Bp, 0);
   else
     hipLaunchKernelGGL(transpose_u64_kernel, dim3((in_words + 31) / 32, (count + 31) / 32), dim3(32, 8), 0, s, src.in, ws.inT, count, in_words,
                        src.in_stride, Bp, 1, (size_t)0);

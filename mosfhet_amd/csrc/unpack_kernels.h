@@ -3,7 +3,9 @@
 //
 //   in [outputs][2][N]; ciphertext c of a call is sample j = (first + c) % per of input o = (first + c) / per, the reference's trlwe_extract_tlwe (src/trlwe.c:540-552, k = 1):
 //     extract(in[o], j).a[i] = (X^i in[o].a)[j] = i <= j ? a[j - i] : -a[N + j - i],      extract(in[o], j).b = in[o].b[j]
-//   Pure integer work: every word depends on the input words, per and the index only.
+//   With a geometry (off, stride) sample j of an input is extract(in[o], off + j stride) instead: the launchers have checked off + (per - 1) stride <= N - 1, so no
+//   coefficient index wraps; (0, 1) is the plain call and computes the same addresses.
+//   Pure integer work: every word depends on the input words, per, the geometry and the index only.
 //
 // Two kernels:
 //   trlwe_unpack_kernel              word (c, i) goes to out[c ldc + i ldi], the b word to out[c ldc + N ldi]: one kernel for both orientations.
@@ -12,7 +14,8 @@
 //                                    lanes fall on different banks; the stores are 512-byte runs of words (rows are N + 1 words: only 8-byte aligned, as in
 //                                    tlwe_pack_transpose_kernel).  The staged polynomial is 1 / rows of the bytes the workgroup writes.
 //                                    ldc = 1 (the tiles' inT [N + 1][Bp], ldi = Bp): the lanes run along c; o and j come from c, so a run of 64 lanes may cross inputs
-//                                    (per = 5 still writes full runs); for one i the lanes of one input read consecutive words, ascending.  No LDS.
+//                                    (per = 5 still writes full runs); for one i the lanes of one input read consecutive words, ascending (words `stride` apart with a
+//                                    geometry: the 2N words of an input stay in the caches).  No LDS.
 //   ks_words_entries_packed_kernel   ks_words_entries_kernel (keyswitch_words_kernels.h) from packed samples: the same entries and bvals, but the ciphertexts are already on
 //                                    the fast index of the source, so no tile goes through LDS.
 // No atomics, nothing to initialise: a replayed graph gives the same words.
@@ -34,8 +37,8 @@ __device__ __forceinline__ uint64_t unpack_mask_word(const uint64_t *__restrict_
 }
 
 // ldi == 1: grid inputs the call touches x ceil(per / rows), dynamic LDS N words.  ldc == 1: grid (ceil(count / 256), ceil((N + 1) / UNPACK_COL_WORDS)), no LDS.
-__global__ __launch_bounds__(UNPACK_THREADS) void trlwe_unpack_kernel(uint64_t *__restrict__ out, const uint64_t *__restrict__ in, int N, int per, int first, int count,
-                                                                      size_t ldc, size_t ldi, int rows) {
+__global__ __launch_bounds__(UNPACK_THREADS) void trlwe_unpack_kernel(uint64_t *__restrict__ out, const uint64_t *__restrict__ in, int N, int per, int first, int off,
+                                                                      int stride, int count, size_t ldc, size_t ldi, int rows) {
   extern __shared__ uint64_t unpack_poly[];   // [N] (row-major form)
   const int tid = threadIdx.x;
   if (ldi == 1) {
@@ -50,18 +53,19 @@ __global__ __launch_bounds__(UNPACK_THREADS) void trlwe_unpack_kernel(uint64_t *
       const long long c = (long long)o * per + j - first;   // the call's ciphertext index
       if (j >= per || c >= count) break;
       if (c < 0) continue;
+      const int jc = off + j * stride;   // the coefficient sample j sits at
       uint64_t *__restrict__ row = out + (size_t)c * ldc;
       for (int i = tid; i < N; i += UNPACK_THREADS) {
-        const uint64_t v = unpack_poly[(j - i) & (N - 1)];
-        row[i] = i <= j ? v : (uint64_t)0 - v;
+        const uint64_t v = unpack_poly[(jc - i) & (N - 1)];
+        row[i] = i <= jc ? v : (uint64_t)0 - v;
       }
-      if (tid == 0) row[N] = a[N + j];
+      if (tid == 0) row[N] = a[N + jc];
     }
     return;
   }
   const int c = (int)blockIdx.x * UNPACK_THREADS + tid;
   if (c >= count) return;
-  const int g = first + c, o = g / per, j = g - o * per;
+  const int g = first + c, o = g / per, j = off + (g - o * per) * stride;
   const uint64_t *__restrict__ a = in + (size_t)o * 2 * N;
   const int i0 = (int)blockIdx.y * UNPACK_COL_WORDS;
 #pragma unroll 4
@@ -74,12 +78,12 @@ __global__ __launch_bounds__(UNPACK_THREADS) void trlwe_unpack_kernel(uint64_t *
 
 // entries [n_in = N][chunks][ctwaves][JB][64] uint16 and bvals [count], as ks_words_entries_kernel writes them (padding ciphertexts: digit 0).
 // grid (ctwaves, ceil(N / 64)), block (64, 4): lane tx = ciphertext, ty strides the 64 input words of the block
-__global__ __launch_bounds__(256) void ks_words_entries_packed_kernel(const uint64_t *__restrict__ in, int N, int per, int first, int count, int t, int base_bit, int JB,
-                                                                     int ctwaves, uint16_t *__restrict__ entries, uint64_t *__restrict__ bvals) {
+__global__ __launch_bounds__(256) void ks_words_entries_packed_kernel(const uint64_t *__restrict__ in, int N, int per, int first, int off, int stride, int count, int t,
+                                                                     int base_bit, int JB, int ctwaves, uint16_t *__restrict__ entries, uint64_t *__restrict__ bvals) {
   const int tx = threadIdx.x, ty = threadIdx.y;
   const int c = (int)blockIdx.x * 64 + tx, i0 = (int)blockIdx.y * 64;
   const bool live = c < count;
-  const int g = first + (live ? c : 0), o = g / per, j = g - o * per;
+  const int g = first + (live ? c : 0), o = g / per, j = off + (g - o * per) * stride;
   const uint64_t *__restrict__ a = in + (size_t)o * 2 * N;
   if (blockIdx.y == 0 && ty == 0 && live) bvals[c] = a[N + j];
   const uint64_t round_off = 1ull << (63 - base_bit * t);

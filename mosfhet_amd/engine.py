@@ -181,6 +181,14 @@ def set_tlwe_pack_workspace(nbytes):
     _check(lib().mosfhet_hip_set_tlwe_pack_workspace(C.c_longlong(int(nbytes))))
 
 
+def _c_int(x):
+    """x as a C int, refused here when it does not fit one (ctypes would wrap it silently)"""
+    x = int(x)
+    if not -2 ** 31 <= x < 2 ** 31:
+        raise MosfhetHipError("argument %d does not fit a C int" % x)
+    return x
+
+
 KS_FORMS = ("small", "words", "tiles_256", "tiles_512")
 
 
@@ -192,6 +200,16 @@ def trlwe_unpack_plan(N, n_out=0, t=0, base_bit=0, total=0, per=None, compressed
     include/mosfhet_hip.h: mosfhet_hip_trlwe_unpack_plan."""
     plan = (C.c_longlong * 8)()
     _check(lib().mosfhet_hip_trlwe_unpack_plan(int(N), int(n_out), int(t), int(base_bit), int(bool(compressed)), int(total), int(N if per is None else per), int(cus), plan))
+    return dict(outputs=int(plan[0]), form=KS_FORMS[plan[1]], pieces=int(plan[2]), prepass_workgroups=int(plan[3]), prepass_bytes=int(plan[4]), saved_bytes=int(plan[5]),
+                pool_bytes=int(plan[6]), rows_per_workgroup=int(plan[7]))
+
+
+def trlwe_unpack_strided_plan(N, n_out=0, t=0, base_bit=0, total=0, per=None, first=0, stride=1, compressed=False, cus=256):
+    """trlwe_unpack_plan for a call with a geometry: sample j of an input is the coefficient first + j stride.  The geometry is checked as the calls check it (first in
+    0 .. N - 1, stride >= 1, first + (per - 1) stride <= N - 1) and changes no field.  include/mosfhet_hip.h: mosfhet_hip_trlwe_unpack_strided_plan."""
+    plan = (C.c_longlong * 8)()
+    _check(lib().mosfhet_hip_trlwe_unpack_strided_plan(int(N), int(n_out), int(t), int(base_bit), int(bool(compressed)), int(total), int(N if per is None else per),
+                                                       C.c_int(_c_int(first)), C.c_int(_c_int(stride)), int(cus), plan))
     return dict(outputs=int(plan[0]), form=KS_FORMS[plan[1]], pieces=int(plan[2]), prepass_workgroups=int(plan[3]), prepass_bytes=int(plan[4]), saved_bytes=int(plan[5]),
                 pool_bytes=int(plan[6]), rows_per_workgroup=int(plan[7]))
 
@@ -1207,6 +1225,59 @@ class Engine:
             out = self.empty(max(total, 0), bsk.N + 1) if extract else self.empty(max(total, 0), 2, bsk.N)
         _check(lib().mosfhet_hip_unpack_keyswitch_functional_bootstrap_batch(self.h, ksk.h, bsk.h, _ptr(out) if total else None, _ptr(tv), self._tv(tv, bsk, total),
                                                                              _ptr(trlwe) if total else None, total, per, torus_base, int(extract), self._stream()))
+        return out
+
+    # ---- ... at an offset and a stride: sample j of an input is the coefficient first + j stride (mosfhet_hip_trlwe_unpack_strided_batch) ----
+    def _unpack_strided_shape(self, trlwe, total, per, ksk=None):
+        outputs, two, N = trlwe.shape
+        assert two == 2
+        if ksk is not None and ksk.n_in != N:   # (the C call takes N from the key: it cannot see the tensor's)
+            raise MosfhetHipError("trlwe_unpack_strided_keyswitch: the key switches from n_in = %d words, the packed samples have N = %d" % (ksk.n_in, N))
+        per = int(per)
+        total = outputs * per if total is None else int(total)
+        assert total <= outputs * max(per, 0), "total = %d: %d packed samples of %d hold %d" % (total, outputs, per, outputs * per)
+        return N, total, per
+
+    def trlwe_unpack_strided(self, trlwe, total, per, first, stride, out=None):
+        """trlwe_extract_tlwe at the coefficients first + j stride, j < per, of every input: trlwe [outputs][2][N] -> [total][N + 1], sample o per + j =
+        extract(trlwe[o], first + j stride); first + (per - 1) stride <= N - 1.  total = None: outputs * per."""
+        N, total, per = self._unpack_strided_shape(trlwe, total, per)
+        if out is None:
+            out = self.empty(max(total, 0), N + 1)
+        _check(lib().mosfhet_hip_trlwe_unpack_strided_batch(self.h, _ptr(out) if total else None, _ptr(trlwe) if total else None, N, total, per, _c_int(first),
+                                                            _c_int(stride), self._stream()))
+        return out
+
+    def trlwe_unpack_strided_keyswitch(self, ksk, trlwe, total, per, first, stride, out=None):
+        """tlwe_keyswitch of trlwe_unpack_strided's samples without writing them: trlwe [outputs][2][N] -> [total][n_out + 1]; ksk an LWE -> LWE key with n_in == N."""
+        N, total, per = self._unpack_strided_shape(trlwe, total, per, ksk)
+        if out is None:
+            out = self.empty(max(total, 0), ksk.n_out + 1)
+        _check(lib().mosfhet_hip_trlwe_unpack_strided_keyswitch_batch(self.h, ksk.h, _ptr(out) if total else None, _ptr(trlwe) if total else None, total, per,
+                                                                      _c_int(first), _c_int(stride), self._stream()))
+        return out
+
+    def unpack_strided_keyswitch_functional_bootstrap(self, ksk, bsk, tv, trlwe, total, per, first, stride, torus_base, extract=True, out=None):
+        """trlwe_unpack_strided_keyswitch followed by functional_bootstrap[_wo_extract] in one call: trlwe [outputs][2][N] -> [total][N + 1] (extract) or [total][2][N];
+        tv one test vector or one per sample."""
+        N, total, per = self._unpack_strided_shape(trlwe, total, per, ksk)
+        if out is None:
+            out = self.empty(max(total, 0), bsk.N + 1) if extract else self.empty(max(total, 0), 2, bsk.N)
+        _check(lib().mosfhet_hip_unpack_strided_keyswitch_functional_bootstrap_batch(self.h, ksk.h, bsk.h, _ptr(out) if total else None, _ptr(tv),
+                                                                                     self._tv(tv, bsk, total), _ptr(trlwe) if total else None, total, per, _c_int(first),
+                                                                                     _c_int(stride), torus_base, int(extract), self._stream()))
+        return out
+
+    def trlwe_linear_unpack_keyswitch_functional_bootstrap(self, lin, ksk, bsk, tv, ct, per, first, stride, torus_base, extract=True, out=None):
+        """trlwe_linear, then unpack_strided_keyswitch_functional_bootstrap on its count * rows_out results, per samples of each, in one call: ct
+        [count][rows_in][2][N] -> [count * rows_out * per][N + 1] (extract) or [count * rows_out * per][2][N]; tv one test vector or one per sample."""
+        count, per = ct.shape[0], int(per)
+        samples = count * lin.rows_out * max(per, 0)
+        if out is None:
+            out = self.empty(samples, bsk.N + 1) if extract else self.empty(samples, 2, bsk.N)
+        _check(lib().mosfhet_hip_trlwe_linear_unpack_keyswitch_functional_bootstrap_batch(self.h, lin.h, ksk.h, bsk.h, _ptr(out), _ptr(tv), self._tv(tv, bsk, samples),
+                                                                                          _ptr(ct), per, _c_int(first), _c_int(stride), count, torus_base, int(extract),
+                                                                                          self._stream()))
         return out
 
     # ---- key switch ----
