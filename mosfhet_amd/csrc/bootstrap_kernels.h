@@ -27,7 +27,7 @@
 #pragma once
 #include <type_traits>
 
-#include "negacyclic_fft.h"
+#include "cmux_steps.h"
 
 namespace mosfhet {
 
@@ -100,29 +100,6 @@ __device__ __forceinline__ void pace_teams(unsigned int *pace, unsigned int roun
   workgroup_sync();
 }
 
-// src/misc.c:18-22 with log_scale = log2(2N)
-template <int LOG2N>
-__device__ __forceinline__ uint32_t modswitch(uint64_t x) {
-  return (uint32_t)((x + (1ull << (63 - LOG2N))) >> (64 - LOG2N));
-}
-
-// src/bootstrap.c:213-217
-__device__ __forceinline__ uint64_t pbs_pre(uint64_t x, const PbsParams &p, int log2N2) {
-  if (!p.pre) return x;
-  const uint64_t rnd = 1ull << (64 - log2N2 + p.theta - 1);
-  const uint64_t msk = ~((1ull << (64 - log2N2 + p.theta)) - 1);
-  return ((x << p.kappa) + rnd) & msk;
-}
-
-// coefficient i of poly * X^a  (a in [0, 2N)), poly in LDS/global; src/polynomial.c:184-199
-template <int N>
-__device__ __forceinline__ uint64_t rot_coeff(const uint64_t *poly, int i, int a_lo, bool flip) {
-  const int src = i - a_lo;
-  const bool neg = (src < 0) != flip;
-  const uint64_t v = poly[src & (N - 1)];
-  return neg ? (0 - v) : v;
-}
-
 // Gadget decomposition state of a lane's coefficient pair (j, j + M): the top L*Bg bits of (d + offset), from
 // which digit lv is a bit-field (src/polynomial.c:74-89: ((d + off) >> (64 - (lv+1) Bg)) & (2^Bg - 1)) - 2^(Bg-1)).
 //   mode PACKED (Bg compile-time, L*Bg <= 32): one 32-bit word per coefficient holding exactly those bits;
@@ -131,11 +108,6 @@ __device__ __forceinline__ uint64_t rot_coeff(const uint64_t *poly, int i, int a
 //   mode WIDE   (run-time Bg or anything else): the full 64-bit words;
 //   mode RAW    (Bg = 2^8, asked for by the caller: SET_1's throughput bootstrap, cmux_digits<.., SF>): the high dword of (d + offset) as it is -- no shift, no
 //               flip; digit lv is the reference's formula on byte 3 - lv, one byte-selecting add and the conversion.
-template <int X>
-struct kCeilLog2 { static constexpr int value = X <= 1 ? 0 : 1 + kCeilLog2<(X + 1) / 2>::value; };
-template <>
-struct kCeilLog2<1> { static constexpr int value = 0; };
-
 template <int L, int BG, bool RAW = false>
 struct Digits {
   static_assert(!RAW || (BG == 8 && L * BG <= 32), "the raw layout: byte fields of the high dword");
@@ -339,10 +311,7 @@ __device__ __forceinline__ void cmux_rows(const typename Digits<L, BG>::word_t (
 #pragma unroll
         for (int m = 0; m < 8; m++) kk[m] = row[c * M + m * T + t];
 #pragma unroll
-        for (int m = 0; m < 8; m++) {
-          o_re[c][m] = __builtin_fma(-im[m], kk[m].y, __builtin_fma(re[m], kk[m].x, o_re[c][m]));
-          o_im[c][m] = __builtin_fma(im[m], kk[m].x, __builtin_fma(re[m], kk[m].y, o_im[c][m]));
-        }
+        for (int m = 0; m < 8; m++) cmac(o_re[c][m], o_im[c][m], re[m], im[m], kk[m]);
       }
       continue;
     }
@@ -353,14 +322,10 @@ __device__ __forceinline__ void cmux_rows(const typename Digits<L, BG>::word_t (
 #pragma unroll
     for (int m = 0; m < 8; m++) {
       k1[m] = row[M + m * T + t];
-      o_re[0][m] = __builtin_fma(-im[m], k0[m].y, __builtin_fma(re[m], k0[m].x, o_re[0][m]));
-      o_im[0][m] = __builtin_fma(im[m], k0[m].x, __builtin_fma(re[m], k0[m].y, o_im[0][m]));
+      cmac(o_re[0][m], o_im[0][m], re[m], im[m], k0[m]);
     }
 #pragma unroll
-    for (int m = 0; m < 8; m++) {
-      o_re[1][m] = __builtin_fma(-im[m], k1[m].y, __builtin_fma(re[m], k1[m].x, o_re[1][m]));
-      o_im[1][m] = __builtin_fma(im[m], k1[m].x, __builtin_fma(re[m], k1[m].y, o_im[1][m]));
-    }
+    for (int m = 0; m < 8; m++) cmac(o_re[1][m], o_im[1][m], re[m], im[m], k1[m]);
   }
 }
 
@@ -401,18 +366,12 @@ __device__ __forceinline__ void cmux_rows2(const typename Digits<L, BG>::word_t 
 #pragma unroll
     for (int m = 0; m < 8; m++) kB[m] = row_x[M + m * T + t];
 #pragma unroll
-    for (int m = 0; m < 8; m++) {
-      o_re[0][m] = __builtin_fma(-xi[m], kA[m].y, __builtin_fma(xr[m], kA[m].x, o_re[0][m]));
-      o_im[0][m] = __builtin_fma(xi[m], kA[m].x, __builtin_fma(xr[m], kA[m].y, o_im[0][m]));
-    }
+    for (int m = 0; m < 8; m++) cmac(o_re[0][m], o_im[0][m], xr[m], xi[m], kA[m]);
     asm volatile("" ::: "memory");   // the next request reuses the registers the products above have consumed
 #pragma unroll
     for (int m = 0; m < 8; m++) kA[m] = row_y[m * T + t];
 #pragma unroll
-    for (int m = 0; m < 8; m++) {
-      o_re[1][m] = __builtin_fma(-xi[m], kB[m].y, __builtin_fma(xr[m], kB[m].x, o_re[1][m]));
-      o_im[1][m] = __builtin_fma(xi[m], kB[m].x, __builtin_fma(xr[m], kB[m].y, o_im[1][m]));
-    }
+    for (int m = 0; m < 8; m++) cmac(o_re[1][m], o_im[1][m], xr[m], xi[m], kB[m]);
     asm volatile("" ::: "memory");
     fft.forward2_fetch(yr, yi, xch, t);
     fft.pass_d_fwd(yr, yi);
@@ -421,15 +380,9 @@ __device__ __forceinline__ void cmux_rows2(const typename Digits<L, BG>::word_t 
     for (int m = 0; m < 8; m++) kB[m] = row_y[M + m * T + t];
     F::forward2_done();
 #pragma unroll
-    for (int m = 0; m < 8; m++) {
-      o_re[0][m] = __builtin_fma(-yi[m], kA[m].y, __builtin_fma(yr[m], kA[m].x, o_re[0][m]));
-      o_im[0][m] = __builtin_fma(yi[m], kA[m].x, __builtin_fma(yr[m], kA[m].y, o_im[0][m]));
-    }
+    for (int m = 0; m < 8; m++) cmac(o_re[0][m], o_im[0][m], yr[m], yi[m], kA[m]);
 #pragma unroll
-    for (int m = 0; m < 8; m++) {
-      o_re[1][m] = __builtin_fma(-yi[m], kB[m].y, __builtin_fma(yr[m], kB[m].x, o_re[1][m]));
-      o_im[1][m] = __builtin_fma(yi[m], kB[m].x, __builtin_fma(yr[m], kB[m].y, o_im[1][m]));
-    }
+    for (int m = 0; m < 8; m++) cmac(o_re[1][m], o_im[1][m], yr[m], yi[m], kB[m]);
   }
 }
 
@@ -480,7 +433,7 @@ template <int L, int BG>
 __global__ __launch_bounds__(64 * 2 * L) void pbs_team_kernel(PbsParams p) {
   using F = Fft1024;
   constexpr int N = F::N, M = F::M, T = F::THREADS, LOG2N2 = F::LOGM + 2, R = 2 * L, TEAM = T * R;
-  constexpr bool kReduce = !(BG > 0 && kCeilLog2<2 * L>::value + (F::LOGM + 1) + BG - 1 + 63 < 83);   // see pbs_kernel
+  constexpr bool kReduce = kProductNeedsReduce<F, L, BG>;
   __shared__ __attribute__((aligned(16))) d2 xch[R][F::XCH_SLOTS];     // transposes; after the forward transform: D_w (slots m T + t)
   __shared__ __attribute__((aligned(16))) d2 xinv[2][F::XCH_SLOTS];    // transposes of the two inverse transforms
   __shared__ __attribute__((aligned(16))) uint64_t acc[2][N];
@@ -496,16 +449,12 @@ __global__ __launch_bounds__(64 * 2 * L) void pbs_team_kernel(PbsParams p) {
   } else {
     const uint64_t *__restrict__ tv = p.tv + b * (size_t)p.tv_stride;
     const uint32_t bbar = modswitch<LOG2N2>(pbs_pre(ct[p.n], p, LOG2N2) + p.prec_offset);
-    const int rot = (2 * N - (int)bbar) & (2 * N - 1);
-    const int a_lo = rot & (N - 1);
-    const bool flip = (rot & N) != 0;
+    const auto [a_lo, flip] = first_rotation(bbar, N);
     for (int x = tid; x < 2 * N; x += TEAM) acc[x >> 10][x & (N - 1)] = rot_coeff<N>(tv + (x >> 10) * N, x & (N - 1), a_lo, flip);
   }
   workgroup_sync();
-  uint64_t off = 1ull << (63 - L * Bg_bit);
-#pragma unroll
-  for (int i = 0; i < L; i++) off += 1ull << (63 - i * Bg_bit);
-  const RoundCtx scale(0x1p-64 / (double)M);
+  const uint64_t off = GADGET_OFFSET(L, Bg_bit);
+  const RoundCtx scale = round_scale<M>();
   const size_t row_sz = (size_t)2 * L * 2 * M;
   const int q = w / L, shift = 64 - (w % L + 1) * Bg_bit;   // this wavefront's row: component q, level w % L
   const uint32_t mask = (1u << Bg_bit) - 1;
@@ -514,8 +463,7 @@ __global__ __launch_bounds__(64 * 2 * L) void pbs_team_kernel(PbsParams p) {
     const int abar = (int)modswitch<LOG2N2>(pbs_pre(ct[i], p, LOG2N2));
     if (!abar) continue;   // src/bootstrap.c:114 (uniform over the workgroup)
     const d2 *__restrict__ bkrow = p.bk + (size_t)i * row_sz;
-    const int a_lo = abar & (N - 1);
-    const bool flip = (abar & N) != 0;
+    const auto [a_lo, flip] = split_rotation(abar, N);
     // wavefronts 0 and 1 fetch their component of all R key rows now, under the digit extraction and the forward transform
     d2 kk[R][8];
     if (w < 2) {
@@ -546,8 +494,7 @@ __global__ __launch_bounds__(64 * 2 * L) void pbs_team_kernel(PbsParams p) {
 #pragma unroll
         for (int m = 0; m < 8; m++) {
           const d2 d = xch[r][m * T + t], k = kk[r][m];
-          o_re[m] = __builtin_fma(-d.y, k.y, __builtin_fma(d.x, k.x, o_re[m]));
-          o_im[m] = __builtin_fma(d.y, k.x, __builtin_fma(d.x, k.y, o_im[m]));
+          cmac(o_re[m], o_im[m], d.x, d.y, k);
         }
       }
       fft.inverse(o_re, o_im, xinv[w], t);
@@ -562,7 +509,7 @@ __global__ __launch_bounds__(64 * 2 * L) void pbs_team_kernel(PbsParams p) {
   if (p.extract) {
     // src/trlwe.c:540-552 at idx = 0
     uint64_t *dst = p.out + b * (size_t)(N + 1);
-    for (int j = tid; j < N; j += TEAM) dst[j] = (j == 0) ? acc[0][0] : (0 - acc[0][N - j]);
+    for (int j = tid; j < N; j += TEAM) dst[j] = extract0_coeff(acc[0], j, N);
     if (tid == 0) dst[N] = acc[1][0];
   } else {
     uint64_t *dst = p.out + b * (size_t)(2 * N);
@@ -590,7 +537,7 @@ __global__ __launch_bounds__(F::THREADS * WideTeams<L>::value) void pbs_wide_tea
   constexpr int N = F::N, M = F::M, T = F::THREADS, LOG2N2 = F::LOGM + 2, R = 2 * L, TEAMS = WideTeams<L>::value, PHASES = (R + TEAMS - 1) / TEAMS, WG = T * TEAMS;
   constexpr int KPRE = TEAMS == 4 ? 3 : TEAMS;   // key rows requested ahead of each phase's forward transform (what the registers hold without spilling)
   static_assert(TEAMS >= 2, "teams 0 and 1 own the two output components");
-  constexpr bool kReduce = !(BG > 0 && kCeilLog2<2 * L>::value + (F::LOGM + 1) + BG - 1 + 63 < 83);   // see pbs_kernel
+  constexpr bool kReduce = kProductNeedsReduce<F, L, BG>;
   extern __shared__ __attribute__((aligned(16))) unsigned char wide_lds[];
   d2 *xch_all = reinterpret_cast<d2 *>(wide_lds);                                                     // [TEAMS][F::XCH_SLOTS]
   uint64_t *acc = reinterpret_cast<uint64_t *>(wide_lds + sizeof(d2) * (size_t)TEAMS * F::XCH_SLOTS);  // [2][N]
@@ -607,16 +554,12 @@ __global__ __launch_bounds__(F::THREADS * WideTeams<L>::value) void pbs_wide_tea
   } else {
     const uint64_t *__restrict__ tv = p.rows > 1 ? p.tv + (b % (size_t)p.rows) * (size_t)(2 * N) : p.tv + b * (size_t)p.tv_stride;
     const uint32_t bbar = modswitch<LOG2N2>(pbs_pre(ct[p.n], p, LOG2N2) + p.prec_offset);
-    const int rot = (2 * N - (int)bbar) & (2 * N - 1);
-    const int a_lo = rot & (N - 1);
-    const bool flip = (rot & N) != 0;
+    const auto [a_lo, flip] = first_rotation(bbar, N);
     for (int x = tid; x < 2 * N; x += WG) acc[x] = rot_coeff<N>(tv + (x / N) * N, x & (N - 1), a_lo, flip);
   }
   workgroup_sync();
-  uint64_t off = 1ull << (63 - L * Bg_bit);
-#pragma unroll
-  for (int i = 0; i < L; i++) off += 1ull << (63 - i * Bg_bit);
-  const RoundCtx scale(0x1p-64 / (double)M);
+  const uint64_t off = GADGET_OFFSET(L, Bg_bit);
+  const RoundCtx scale = round_scale<M>();
   const size_t row_sz = (size_t)2 * L * 2 * M;
   const uint32_t mask = (1u << Bg_bit) - 1;
   const int half = 1 << (Bg_bit - 1);
@@ -625,8 +568,7 @@ __global__ __launch_bounds__(F::THREADS * WideTeams<L>::value) void pbs_wide_tea
     const int abar = (int)modswitch<LOG2N2>(pbs_pre(ct[i], p, LOG2N2));
     if (!abar) continue;   // src/bootstrap.c:114 (uniform over the workgroup)
     const d2 *__restrict__ bkrow = p.bk + (size_t)i * row_sz;
-    const int a_lo = abar & (N - 1);
-    const bool flip = (abar & N) != 0;
+    const auto [a_lo, flip] = split_rotation(abar, N);
     double o_re[8], o_im[8];
 #pragma unroll
     for (int m = 0; m < 8; m++) { o_re[m] = 0.0; o_im[m] = 0.0; }
@@ -676,8 +618,7 @@ __global__ __launch_bounds__(F::THREADS * WideTeams<L>::value) void pbs_wide_tea
             d2 k;
             if (r < KPRE) k = kk[r < KPRE ? r : 0][m];
             else k = bkrow[(size_t)(ph * TEAMS + r) * (2 * M) + (size_t)team * M + m * T + t];
-            o_re[m] = __builtin_fma(-d.y, k.y, __builtin_fma(d.x, k.x, o_re[m]));
-            o_im[m] = __builtin_fma(d.y, k.x, __builtin_fma(d.x, k.y, o_im[m]));
+            cmac(o_re[m], o_im[m], d.x, d.y, k);
           }
         }
       }
@@ -699,7 +640,7 @@ __global__ __launch_bounds__(F::THREADS * WideTeams<L>::value) void pbs_wide_tea
   if (p.extract) {
     // src/trlwe.c:540-552 at idx = 0
     uint64_t *dst = p.out + b * (size_t)(N + 1);
-    for (int j = tid; j < N; j += WG) dst[j] = (j == 0) ? acc[0] : (0 - acc[N - j]);
+    for (int j = tid; j < N; j += WG) dst[j] = extract0_coeff(acc, j, N);
     if (tid == 0) dst[N] = acc[N];
   } else {
     uint64_t *dst = p.out + b * (size_t)(2 * N);
@@ -721,7 +662,7 @@ template <class F, int L, int BG>
 __global__ __launch_bounds__(2 * F::THREADS) void pbs_wide_pair_kernel(PbsParams p) {
   static_assert(F::kForward2 && F::kLtw && L % 2 == 0, "row pairs need the pipelined forward pair and an even gadget length");
   constexpr int N = F::N, M = F::M, T = F::THREADS, LOG2N2 = F::LOGM + 2, R = 2 * L, DPH = R / 4, WG = 2 * T;
-  constexpr bool kReduce = !(BG > 0 && kCeilLog2<2 * L>::value + (F::LOGM + 1) + BG - 1 + 63 < 83);   // see pbs_kernel
+  constexpr bool kReduce = kProductNeedsReduce<F, L, BG>;
   extern __shared__ __attribute__((aligned(16))) unsigned char wide_lds[];
   d2 *xch_all = reinterpret_cast<d2 *>(wide_lds);                                   // [2][F::XCH_SLOTS]
   d2 *hand = xch_all + (size_t)2 * F::XCH_SLOTS;                                    // [4][M]: row r of the double phase
@@ -739,16 +680,12 @@ __global__ __launch_bounds__(2 * F::THREADS) void pbs_wide_pair_kernel(PbsParams
   } else {
     const uint64_t *__restrict__ tv = p.rows > 1 ? p.tv + (b % (size_t)p.rows) * (size_t)(2 * N) : p.tv + b * (size_t)p.tv_stride;
     const uint32_t bbar = modswitch<LOG2N2>(pbs_pre(ct[p.n], p, LOG2N2) + p.prec_offset);
-    const int rot = (2 * N - (int)bbar) & (2 * N - 1);
-    const int a_lo = rot & (N - 1);
-    const bool flip = (rot & N) != 0;
+    const auto [a_lo, flip] = first_rotation(bbar, N);
     for (int x = tid; x < 2 * N; x += WG) acc[x] = rot_coeff<N>(tv + (x / N) * N, x & (N - 1), a_lo, flip);
   }
   workgroup_sync();
-  uint64_t off = 1ull << (63 - L * Bg_bit);
-#pragma unroll
-  for (int i = 0; i < L; i++) off += 1ull << (63 - i * Bg_bit);
-  const RoundCtx scale(0x1p-64 / (double)M);
+  const uint64_t off = GADGET_OFFSET(L, Bg_bit);
+  const RoundCtx scale = round_scale<M>();
   const size_t row_sz = (size_t)2 * L * 2 * M;
   const uint32_t mask = (1u << Bg_bit) - 1;
   const int half = 1 << (Bg_bit - 1);
@@ -756,8 +693,7 @@ __global__ __launch_bounds__(2 * F::THREADS) void pbs_wide_pair_kernel(PbsParams
     const int abar = (int)modswitch<LOG2N2>(pbs_pre(ct[i], p, LOG2N2));
     if (!abar) continue;   // src/bootstrap.c:114 (uniform over the workgroup)
     const d2 *__restrict__ bkrow = p.bk + (size_t)i * row_sz;
-    const int a_lo = abar & (N - 1);
-    const bool flip = (abar & N) != 0;
+    const auto [a_lo, flip] = split_rotation(abar, N);
     double o_re[8], o_im[8];
 #pragma unroll
     for (int m = 0; m < 8; m++) { o_re[m] = 0.0; o_im[m] = 0.0; }
@@ -802,8 +738,7 @@ __global__ __launch_bounds__(2 * F::THREADS) void pbs_wide_pair_kernel(PbsParams
 #pragma unroll
         for (int m = 0; m < 8; m++) {
           const d2 d = dr[m * T + t], k = kk[r][m];
-          o_re[m] = __builtin_fma(-d.y, k.y, __builtin_fma(d.x, k.x, o_re[m]));
-          o_im[m] = __builtin_fma(d.y, k.x, __builtin_fma(d.x, k.y, o_im[m]));
+          cmac(o_re[m], o_im[m], d.x, d.y, k);
         }
       }
       workgroup_sync();
@@ -813,8 +748,7 @@ __global__ __launch_bounds__(2 * F::THREADS) void pbs_wide_pair_kernel(PbsParams
 #pragma unroll
         for (int m = 0; m < 8; m++) {
           const d2 d = dr[m * T + t], k = kk[r][m];
-          o_re[m] = __builtin_fma(-d.y, k.y, __builtin_fma(d.x, k.x, o_re[m]));
-          o_im[m] = __builtin_fma(d.y, k.x, __builtin_fma(d.x, k.y, o_im[m]));
+          cmac(o_re[m], o_im[m], d.x, d.y, k);
         }
       }
       workgroup_sync();   // the hand-over buffers are consumed
@@ -830,7 +764,7 @@ __global__ __launch_bounds__(2 * F::THREADS) void pbs_wide_pair_kernel(PbsParams
   }
   if (p.extract) {
     uint64_t *dst = p.out + b * (size_t)(N + 1);
-    for (int j = tid; j < N; j += WG) dst[j] = (j == 0) ? acc[0] : (0 - acc[N - j]);
+    for (int j = tid; j < N; j += WG) dst[j] = extract0_coeff(acc, j, N);
     if (tid == 0) dst[N] = acc[N];
   } else {
     uint64_t *dst = p.out + b * (size_t)(2 * N);
@@ -902,7 +836,7 @@ __global__ __launch_bounds__(2 * F::THREADS) void pbs_split_kernel(PbsParams p, 
                 "the l rows of one accumulator component: l / 4 double phases of pbs_wide_pair_kernel (two pipelined rows per team) and, for l = 2 and 6, one row per team");
   constexpr int QUADS = L / 4, TAIL = L % 4;   // TAIL = 2: the last two levels go one row per team
   constexpr int N = F::N, M = F::M, T = F::THREADS, LOG2N2 = F::LOGM + 2, WG = 2 * T;
-  constexpr bool kReduce = !(BG > 0 && kCeilLog2<2 * L>::value + (F::LOGM + 1) + BG - 1 + 63 < 83);   // see pbs_kernel
+  constexpr bool kReduce = kProductNeedsReduce<F, L, BG>;
   extern __shared__ __attribute__((aligned(16))) unsigned char wide_lds[];
   d2 *xch_all = reinterpret_cast<d2 *>(wide_lds);                                   // [2][F::XCH_SLOTS]
   d2 *hand = xch_all + (size_t)2 * F::XCH_SLOTS;                                    // [4][M]: row r of the double phase
@@ -957,16 +891,12 @@ __global__ __launch_bounds__(2 * F::THREADS) void pbs_split_kernel(PbsParams p, 
   } else {
     const uint64_t *__restrict__ tv = p.rows > 1 ? p.tv + (b % (size_t)p.rows) * (size_t)(2 * N) : p.tv + b * (size_t)p.tv_stride;
     const uint32_t bbar = modswitch<LOG2N2>(pbs_pre(ct[p.n], p, LOG2N2) + p.prec_offset);
-    const int rot = (2 * N - (int)bbar) & (2 * N - 1);
-    const int a_lo = rot & (N - 1);
-    const bool flip = (rot & N) != 0;
+    const auto [a_lo, flip] = first_rotation(bbar, N);
     for (int x = tid; x < 2 * N; x += WG) acc[x] = rot_coeff<N>(tv + (x / N) * N, x & (N - 1), a_lo, flip);
   }
   workgroup_sync();
-  uint64_t off = 1ull << (63 - L * Bg_bit);
-#pragma unroll
-  for (int i = 0; i < L; i++) off += 1ull << (63 - i * Bg_bit);
-  const RoundCtx scale(0x1p-64 / (double)M);
+  const uint64_t off = GADGET_OFFSET(L, Bg_bit);
+  const RoundCtx scale = round_scale<M>();
   const size_t row_sz = (size_t)2 * L * 2 * M;
   const uint32_t mask = (1u << Bg_bit) - 1;
   const int half = 1 << (Bg_bit - 1);
@@ -975,8 +905,7 @@ __global__ __launch_bounds__(2 * F::THREADS) void pbs_split_kernel(PbsParams p, 
     const int abar = (int)modswitch<LOG2N2>(pbs_pre(ct[i], p, LOG2N2));
     if (!abar) continue;   // src/bootstrap.c:114 (uniform over both workgroups of a pair)
     const d2 *__restrict__ bkrow = p.bk + (size_t)i * row_sz;
-    const int a_lo = abar & (N - 1);
-    const bool flip = (abar & N) != 0;
+    const auto [a_lo, flip] = split_rotation(abar, N);
     double s_re[8], s_im[8];   // this team's output component: sum of the components' partial sums, component 0's first
 #pragma unroll 1
     for (int dp = dp_lo; dp < dp_hi; dp++) {
@@ -1020,8 +949,7 @@ __global__ __launch_bounds__(2 * F::THREADS) void pbs_split_kernel(PbsParams p, 
 #pragma unroll
           for (int m = 0; m < 8; m++) {
             const d2 d = dr[m * T + t], k = kk[r][m];
-            o_re[m] = __builtin_fma(-d.y, k.y, __builtin_fma(d.x, k.x, o_re[m]));
-            o_im[m] = __builtin_fma(d.y, k.x, __builtin_fma(d.x, k.y, o_im[m]));
+            cmac(o_re[m], o_im[m], d.x, d.y, k);
           }
         }
         workgroup_sync();
@@ -1031,8 +959,7 @@ __global__ __launch_bounds__(2 * F::THREADS) void pbs_split_kernel(PbsParams p, 
 #pragma unroll
           for (int m = 0; m < 8; m++) {
             const d2 d = dr[m * T + t], k = kk[r][m];
-            o_re[m] = __builtin_fma(-d.y, k.y, __builtin_fma(d.x, k.x, o_re[m]));
-            o_im[m] = __builtin_fma(d.y, k.x, __builtin_fma(d.x, k.y, o_im[m]));
+            cmac(o_re[m], o_im[m], d.x, d.y, k);
           }
         }
         if (q + 1 < QUADS || TAIL) workgroup_sync();   // the hand-over buffers are consumed (the last phase's barrier stands behind the sum below)
@@ -1064,8 +991,7 @@ __global__ __launch_bounds__(2 * F::THREADS) void pbs_split_kernel(PbsParams p, 
 #pragma unroll
           for (int m = 0; m < 8; m++) {
             const d2 d = dr[m * T + t], k = kk[r][m];
-            o_re[m] = __builtin_fma(-d.y, k.y, __builtin_fma(d.x, k.x, o_re[m]));
-            o_im[m] = __builtin_fma(d.y, k.x, __builtin_fma(d.x, k.y, o_im[m]));
+            cmac(o_re[m], o_im[m], d.x, d.y, k);
           }
         }
       }
@@ -1125,7 +1051,7 @@ __global__ __launch_bounds__(2 * F::THREADS) void pbs_split_kernel(PbsParams p, 
   if (p.extract) {
     // src/trlwe.c:540-552 at idx = 0: the mask comes from component 0, the body from component 1
     uint64_t *dst = p.out + b * (size_t)(N + 1);
-    if (mine0) for (int j = tid; j < N; j += WG) dst[j] = (j == 0) ? acc[0] : (0 - acc[N - j]);
+    if (mine0) for (int j = tid; j < N; j += WG) dst[j] = extract0_coeff(acc, j, N);
     if (mine1 && tid == 0) dst[N] = acc[N];
   } else {
     uint64_t *dst = p.out + b * (size_t)(2 * N);
@@ -1266,10 +1192,8 @@ __global__ __launch_bounds__(F::THREADS, 2) void pbs_ga_kernel(GaParams g) {
   const int Bg_bit = BG > 0 ? BG : p.Bg_bit;
   F fft;
   fft_setup(fft, p.tw, t);
-  uint64_t off = 1ull << (63 - L * Bg_bit);
-#pragma unroll
-  for (int i = 0; i < L; i++) off += 1ull << (63 - i * Bg_bit);
-  const RoundCtx scale(0x1p-64 / (double)M);
+  const uint64_t off = GADGET_OFFSET(L, Bg_bit);
+  const RoundCtx scale = round_scale<M>();
   const size_t row_sz = (size_t)2 * L * 2 * M, ak_sz = (size_t)L * 2 * M;
   uint64_t al[8], ah[8];
 
@@ -1301,9 +1225,7 @@ __global__ __launch_bounds__(F::THREADS, 2) void pbs_ga_kernel(GaParams g) {
       // src/bootstrap_ga.c:64-65: acc = tv * X^(2N - bbar)
       const uint64_t *__restrict__ tv = p.tv + b * (size_t)p.tv_stride;
       const uint32_t bbar = modswitch<LOG2N2>(ct[p.n] + p.prec_offset);
-      const int rot = (2 * N - (int)bbar) & (2 * N - 1);
-      const int a_lo = rot & (N - 1);
-      const bool flip = (rot & N) != 0;
+      const auto [a_lo, flip] = first_rotation(bbar, N);
 #pragma unroll
       for (int m = 0; m < 8; m++) {
         al[m] = rot_coeff<N>(tv, m * T + t, a_lo, flip);
@@ -1345,7 +1267,7 @@ __global__ __launch_bounds__(F::THREADS, 2) void pbs_ga_kernel(GaParams g) {
     }
     F::sync();
     uint64_t *dst = p.out + b * (size_t)(N + 1);
-    for (int j = t; j < N; j += T) dst[j] = (j == 0) ? st[0] : (0 - st[N - j]);
+    for (int j = t; j < N; j += T) dst[j] = extract0_coeff(st, j, N);
     if (t == 0) dst[N] = acc1[0];
   } else {
     uint64_t *dst = p.out + b * (size_t)(2 * N);
@@ -1413,8 +1335,7 @@ struct GaWide {
 #pragma unroll
         for (int m = 0; m < 8; m++) {
           const d2 d = dr[m * T + t], k = kk[r][m];
-          o_re[m] = __builtin_fma(-d.y, k.y, __builtin_fma(d.x, k.x, o_re[m]));
-          o_im[m] = __builtin_fma(d.y, k.x, __builtin_fma(d.x, k.y, o_im[m]));
+          cmac(o_re[m], o_im[m], d.x, d.y, k);
         }
       }
       workgroup_sync();
@@ -1481,9 +1402,8 @@ __global__ __launch_bounds__(2 * F::THREADS) void pbs_ga_wide_kernel(GaParams g,
   const int Bg_bit = p.Bg_bit;
   F fft;
   fft.init(p.tw, t);
-  uint64_t off = 1ull << (63 - l * Bg_bit);
-  for (int i = 0; i < l; i++) off += 1ull << (63 - i * Bg_bit);
-  const RoundCtx scale(0x1p-64 / (double)M);
+  const uint64_t off = GADGET_OFFSET(l, Bg_bit);
+  const RoundCtx scale = round_scale<M>();
   const size_t row_sz = (size_t)2 * l * 2 * M, ak_sz = (size_t)l * 2 * M;
   const uint64_t *__restrict__ ct = p.in + b * (size_t)(p.n + 1);
   if (p.skip_init) {
@@ -1492,9 +1412,7 @@ __global__ __launch_bounds__(2 * F::THREADS) void pbs_ga_wide_kernel(GaParams g,
   } else {
     const uint64_t *__restrict__ tv = p.tv + b * (size_t)p.tv_stride;
     const uint32_t bbar = modswitch<LOG2N2>(ct[p.n] + p.prec_offset);
-    const int rot = (2 * N - (int)bbar) & (2 * N - 1);
-    const int a_lo = rot & (N - 1);
-    const bool flip = (rot & N) != 0;
+    const auto [a_lo, flip] = first_rotation(bbar, N);
     for (int x = tid; x < 2 * N; x += WG) acc[x] = rot_coeff<N>(tv + (x / N) * N, x & (N - 1), a_lo, flip);
   }
   workgroup_sync();
@@ -1519,7 +1437,7 @@ __global__ __launch_bounds__(2 * F::THREADS) void pbs_ga_wide_kernel(GaParams g,
   }
   if (p.extract) {
     uint64_t *dst = p.out + b * (size_t)(N + 1);
-    for (int j = tid; j < N; j += WG) dst[j] = (j == 0) ? acc[0] : (0 - acc[N - j]);
+    for (int j = tid; j < N; j += WG) dst[j] = extract0_coeff(acc, j, N);
     if (tid == 0) dst[N] = acc[N];
   } else {
     uint64_t *dst = p.out + b * (size_t)(2 * N);
@@ -1597,16 +1515,12 @@ __global__ __launch_bounds__(2 * F::THREADS) void pbs_ga_split_kernel(GaParams g
   } else {
     const uint64_t *__restrict__ tv = p.tv + b * (size_t)p.tv_stride;
     const uint32_t bbar = modswitch<LOG2N2>(ct[p.n] + p.prec_offset);
-    const int rot = (2 * N - (int)bbar) & (2 * N - 1);
-    const int a_lo = rot & (N - 1);
-    const bool flip = (rot & N) != 0;
+    const auto [a_lo, flip] = first_rotation(bbar, N);
     for (int x = tid; x < 2 * N; x += WG) acc[x] = rot_coeff<N>(tv + (x / N) * N, x & (N - 1), a_lo, flip);
   }
   workgroup_sync();
-  uint64_t off = 1ull << (63 - L * Bg_bit);
-#pragma unroll
-  for (int i = 0; i < L; i++) off += 1ull << (63 - i * Bg_bit);
-  const RoundCtx scale(0x1p-64 / (double)M);
+  const uint64_t off = GADGET_OFFSET(L, Bg_bit);
+  const RoundCtx scale = round_scale<M>();
   const size_t row_sz = (size_t)2 * L * 2 * M, ak_sz = (size_t)L * 2 * M;
   const uint32_t dmask = (1u << Bg_bit) - 1;
   const int half = 1 << (Bg_bit - 1);
@@ -1647,8 +1561,7 @@ __global__ __launch_bounds__(2 * F::THREADS) void pbs_ga_split_kernel(GaParams g
 #pragma unroll
       for (int m = 0; m < 8; m++) {
         const d2 d = dr[m * T + t], k = kk[r][m];
-        o_re[m] = __builtin_fma(-d.y, k.y, __builtin_fma(d.x, k.x, o_re[m]));
-        o_im[m] = __builtin_fma(d.y, k.x, __builtin_fma(d.x, k.y, o_im[m]));
+        cmac(o_re[m], o_im[m], d.x, d.y, k);
       }
     }
     workgroup_sync();
@@ -1658,8 +1571,7 @@ __global__ __launch_bounds__(2 * F::THREADS) void pbs_ga_split_kernel(GaParams g
 #pragma unroll
       for (int m = 0; m < 8; m++) {
         const d2 d = dr[m * T + t], k = kk[r][m];
-        o_re[m] = __builtin_fma(-d.y, k.y, __builtin_fma(d.x, k.x, o_re[m]));
-        o_im[m] = __builtin_fma(d.y, k.x, __builtin_fma(d.x, k.y, o_im[m]));
+        cmac(o_re[m], o_im[m], d.x, d.y, k);
       }
     }
     workgroup_sync();   // the hand-over buffers are consumed
@@ -1800,7 +1712,7 @@ __global__ __launch_bounds__(2 * F::THREADS) void pbs_ga_split_kernel(GaParams g
   const bool mine0 = alone || h == 0, mine1 = alone || h == 1;
   if (p.extract) {
     uint64_t *dst = p.out + b * (size_t)(N + 1);
-    if (mine0) for (int j = tid; j < N; j += WG) dst[j] = (j == 0) ? acc[0] : (0 - acc[N - j]);
+    if (mine0) for (int j = tid; j < N; j += WG) dst[j] = extract0_coeff(acc, j, N);
     if (mine1 && tid == 0) dst[N] = acc[N];
   } else {
     uint64_t *dst = p.out + b * (size_t)(2 * N);
@@ -1840,14 +1752,10 @@ __device__ __forceinline__ void ks_rows_rt(const uint64_t (&dd_lo)[8], const uin
 #pragma unroll
     for (int m = 0; m < 8; m++) {
       k1[m] = row[M + m * T + tid];
-      o_re[0][m] = __builtin_fma(-im[m], k0[m].y, __builtin_fma(re[m], k0[m].x, o_re[0][m]));
-      o_im[0][m] = __builtin_fma(im[m], k0[m].x, __builtin_fma(re[m], k0[m].y, o_im[0][m]));
+      cmac(o_re[0][m], o_im[0][m], re[m], im[m], k0[m]);
     }
 #pragma unroll
-    for (int m = 0; m < 8; m++) {
-      o_re[1][m] = __builtin_fma(-im[m], k1[m].y, __builtin_fma(re[m], k1[m].x, o_re[1][m]));
-      o_im[1][m] = __builtin_fma(im[m], k1[m].x, __builtin_fma(re[m], k1[m].y, o_im[1][m]));
-    }
+    for (int m = 0; m < 8; m++) cmac(o_re[1][m], o_im[1][m], re[m], im[m], k1[m]);
   }
 }
 
@@ -1877,9 +1785,8 @@ __global__ __launch_bounds__(F::THREADS, 1) void trlwe_fft_keyswitch_kernel(cons
   uint64_t *o = out + (size_t)blockIdx.x * out_stride;
   F fft;
   fft.init(tw, tid);
-  uint64_t off = 1ull << (63 - t * base_bit);
-  for (int i = 0; i < t; i++) off += 1ull << (63 - i * base_bit);
-  const RoundCtx scale(0x1p-64 / (double)M);
+  const uint64_t off = GADGET_OFFSET(t, base_bit);
+  const RoundCtx scale = round_scale<M>();
   uint64_t res_a_lo[8], res_a_hi[8], res_b_lo[8], res_b_hi[8];
 #pragma unroll
   for (int m = 0; m < 8; m++) {
@@ -1975,7 +1882,7 @@ __global__ __launch_bounds__(F::THREADS) void torus_to_dft_kernel(const void *__
     for (int m = 0; m < 8; m++) { const d2 v = src[m * T + t]; re[m] = v.x; im[m] = v.y; }
     fft.inverse(re, im, xch, t);
     uint64_t *dst = static_cast<uint64_t *>(out) + (size_t)blockIdx.x * N;
-    const RoundCtx scale(0x1p-64 / (double)M);
+    const RoundCtx scale = round_scale<M>();
 #pragma unroll
     for (int m = 0; m < 8; m++) {
       dst[m * T + t] = round_mod_2_64(re[m], scale);
@@ -2024,17 +1931,14 @@ __global__ __launch_bounds__(F::THREADS, 2) void external_product_kernel(const d
                                                                        const uint64_t *in0 = nullptr, d2 *__restrict__ out_dft = nullptr) {   // out may alias in0 (CMUX in place): neither is __restrict__
   constexpr int N = F::N, M = F::M, T = F::THREADS;
   using D = Digits<L, BG>;
-  // rounding without the reduction mod 1 where the gadget bounds the sums (see pbs_kernel)
-  constexpr bool kReduce = !(BG > 0 && kCeilLog2<2 * L>::value + (F::LOGM + 1) + BG - 1 + 63 < 83);
+  constexpr bool kReduce = kProductNeedsReduce<F, L, BG>;
   __shared__ __attribute__((aligned(16))) d2 xch[F::XCH_SLOTS];
   const int t = threadIdx.x;
   const int Bg_bit = BG > 0 ? BG : Bg_bit_rt;
   F fft;
   fft_setup(fft, tw, t);
-  uint64_t off = 1ull << (63 - L * Bg_bit);
-#pragma unroll
-  for (int i = 0; i < L; i++) off += 1ull << (63 - i * Bg_bit);
-  const RoundCtx scale(0x1p-64 / (double)M);
+  const uint64_t off = GADGET_OFFSET(L, Bg_bit);
+  const RoundCtx scale = round_scale<M>();
   // rows two at a time + the software-pipelined unit loop: transforms with the pass twiddles in LDS (Fft2048L: the registers that makes free are what
   // both need); the launcher picks that type for the gadgets where the build has no scratch
   constexpr bool kPairs = F::kForward2 && F::kLtw && L % 2 == 0;
@@ -2167,7 +2071,7 @@ __global__ __launch_bounds__(512, 2) void external_product_ldskey_kernel(const d
   using F = Fft1024;
   constexpr int N = F::N, M = F::M, T = 64, TEAMS = 8;
   using D = Digits<L, BG>;
-  constexpr bool kReduce = !(BG > 0 && kCeilLog2<2 * L>::value + (F::LOGM + 1) + BG - 1 + 63 < 83);
+  constexpr bool kReduce = kProductNeedsReduce<F, L, BG>;
   __shared__ __attribute__((aligned(16))) d2 key[2 * L * 2 * M];
   __shared__ __attribute__((aligned(16))) d2 xch_all[TEAMS][F::XCH_SLOTS];
   const int w = threadIdx.x >> 6, t = threadIdx.x & 63;
@@ -2176,10 +2080,8 @@ __global__ __launch_bounds__(512, 2) void external_product_ldskey_kernel(const d
   const int Bg_bit = BG > 0 ? BG : Bg_bit_rt;
   F fft;
   fft.init(tw, t);
-  uint64_t off = 1ull << (63 - L * Bg_bit);
-#pragma unroll
-  for (int i = 0; i < L; i++) off += 1ull << (63 - i * Bg_bit);
-  const RoundCtx scale(0x1p-64 / (double)M);
+  const uint64_t off = GADGET_OFFSET(L, Bg_bit);
+  const RoundCtx scale = round_scale<M>();
   workgroup_sync();
   const size_t first = (size_t)blockIdx.x * TEAMS + w, stride = (size_t)gridDim.x * TEAMS;
 
@@ -2305,8 +2207,7 @@ __global__ void dft_mul_kernel(d2 *out, const d2 *a, const d2 *b, size_t count, 
   if (i >= count) return;
   const d2 x = a[i], y = b[i];
   d2 o = addto ? out[i] : d2{0.0, 0.0};
-  o.x = __builtin_fma(-x.y, y.y, __builtin_fma(x.x, y.x, o.x));
-  o.y = __builtin_fma(x.y, y.x, __builtin_fma(x.x, y.y, o.y));
+  cmac(o, x.x, x.y, y);
   out[i] = o;
 }
 

@@ -59,13 +59,10 @@ __global__ __launch_bounds__(F::THREADS, 2) void public_mux_kernel(const uint64_
         fft.forward(re, im, xch, tid);
       }
 #pragma unroll
-      for (int m = 0; m < 8; m++) {
-        o_re[c][m] = __builtin_fma(-im[m], k[m].y, __builtin_fma(re[m], k[m].x, o_re[c][m]));
-        o_im[c][m] = __builtin_fma(im[m], k[m].x, __builtin_fma(re[m], k[m].y, o_im[c][m]));
-      }
+      for (int m = 0; m < 8; m++) cmac(o_re[c][m], o_im[c][m], re[m], im[m], k[m]);
     }
   }
-  const RoundCtx scale(0x1p-64 / (double)M);
+  const RoundCtx scale = round_scale<M>();
 #pragma unroll
   for (int c = 0; c < 2; c++) {
     fft.inverse(o_re[c], o_im[c], xch, tid);
@@ -177,7 +174,7 @@ __global__ __launch_bounds__(F::THREADS, 2) void trlwe_tensor_prod_kernel(const 
   F fft;
   fft.init(tw, tid);
   const int hp1 = 64 - (64 - precision) / 2, hp2 = 64 - (64 - precision + 1) / 2;
-  const RoundCtx scale(0x1p-64 / (double)M);
+  const RoundCtx scale = round_scale<M>();
   auto load = [&](const uint64_t *src, int hp, double (&re)[8], double (&im)[8]) {
 #pragma unroll
     for (int m = 0; m < 8; m++) {   // torus2int(x, hp) = (x + 2^(63-hp)) >> (64-hp)   [src/misc.c:18-22]
@@ -199,8 +196,8 @@ __global__ __launch_bounds__(F::THREADS, 2) void trlwe_tensor_prod_kernel(const 
   load(c2, hp2, a2r, a2i);
 #pragma unroll
   for (int m = 0; m < 8; m++) {      // T = A1 A2
-    xr[m] = __builtin_fma(-a1i[m], a2i[m], __builtin_fma(a1r[m], a2r[m], 0.0));
-    xi[m] = __builtin_fma(a1i[m], a2r[m], __builtin_fma(a1r[m], a2i[m], 0.0));
+    xr[m] = 0.0; xi[m] = 0.0;
+    cmac(xr[m], xi[m], a1r[m], a1i[m], d2{a2r[m], a2i[m]});
   }
   store(tt, xr, xi);
 #pragma unroll
@@ -210,16 +207,15 @@ __global__ __launch_bounds__(F::THREADS, 2) void trlwe_tensor_prod_kernel(const 
   load(c2 + N, hp2, b2r, b2i);
 #pragma unroll
   for (int m = 0; m < 8; m++) {      // A = A1 B2 + B1 A2
-    xr[m] = __builtin_fma(-a1i[m], b2i[m], __builtin_fma(a1r[m], b2r[m], 0.0));
-    xi[m] = __builtin_fma(a1i[m], b2r[m], __builtin_fma(a1r[m], b2i[m], 0.0));
-    xr[m] = __builtin_fma(-b1i[m], a2i[m], __builtin_fma(b1r[m], a2r[m], xr[m]));
-    xi[m] = __builtin_fma(b1i[m], a2r[m], __builtin_fma(b1r[m], a2i[m], xi[m]));
+    xr[m] = 0.0; xi[m] = 0.0;
+    cmac(xr[m], xi[m], a1r[m], a1i[m], d2{b2r[m], b2i[m]});
+    cmac(xr[m], xi[m], b1r[m], b1i[m], d2{a2r[m], a2i[m]});
   }
   store(r, xr, xi);
 #pragma unroll
   for (int m = 0; m < 8; m++) {      // B = B1 B2
-    xr[m] = __builtin_fma(-b1i[m], b2i[m], __builtin_fma(b1r[m], b2r[m], 0.0));
-    xi[m] = __builtin_fma(b1i[m], b2r[m], __builtin_fma(b1r[m], b2i[m], 0.0));
+    xr[m] = 0.0; xi[m] = 0.0;
+    cmac(xr[m], xi[m], b1r[m], b1i[m], d2{b2r[m], b2i[m]});
   }
   store(r + N, xr, xi);
 }
@@ -262,9 +258,7 @@ __global__ __launch_bounds__(F::THREADS) void pbs_unfolded_kernel(UnfoldParams p
   {
     const uint64_t *__restrict__ tv = p.tv + b * (size_t)p.tv_stride;
     const uint32_t bbar = modswitch<LOG2N2>(ct[p.n] + p.prec_offset);
-    const int rot = (2 * N - (int)bbar) & (2 * N - 1);
-    const int a_lo = rot & (N - 1);
-    const bool flip = (rot & N) != 0;
+    const auto [a_lo, flip] = first_rotation(bbar, N);
 #pragma unroll
     for (int c = 0; c < 2; c++)
 #pragma unroll
@@ -274,11 +268,10 @@ __global__ __launch_bounds__(F::THREADS) void pbs_unfolded_kernel(UnfoldParams p
       }
   }
   const int l = p.l, Bg = p.Bg_bit, u = p.unfolding, key_exp = 1 << u, final_exp = key_exp / u;
-  uint64_t off = 1ull << (63 - l * Bg);
-  for (int i = 0; i < l; i++) off += 1ull << (63 - i * Bg);
+  const uint64_t off = GADGET_OFFSET(l, Bg);
   const uint32_t mask = (1u << Bg) - 1;
   const int half = 1 << (Bg - 1);
-  const RoundCtx scale(0x1p-64 / (double)M);
+  const RoundCtx scale = round_scale<M>();
   const size_t trgsw_sz = (size_t)2 * l * 2 * N;
 #pragma unroll 1
   for (int i = 0; i < p.n; i += u) {
@@ -309,8 +302,7 @@ __global__ __launch_bounds__(F::THREADS) void pbs_unfolded_kernel(UnfoldParams p
           for (int bb = 0; bb < u; bb++)
             if ((j >> bb) & 1) a_i += ct[i + bb];
           const int rot = j ? (int)modswitch<LOG2N2>(a_i) : 0;
-          const int a_lo = rot & (N - 1);
-          const bool flip = (rot & N) != 0;
+          const auto [a_lo, flip] = split_rotation(rot, N);
           const uint64_t *__restrict__ src = p.su + ((size_t)i * final_exp + j) * trgsw_sz + ((size_t)q * 2 + c) * N;
 #pragma unroll
           for (int m = 0; m < 8; m++) {
@@ -324,8 +316,8 @@ __global__ __launch_bounds__(F::THREADS) void pbs_unfolded_kernel(UnfoldParams p
         fft.forward(kr, ki, xch, t);
 #pragma unroll
         for (int m = 0; m < 8; m++) {
-          const double re = __builtin_fma(-di[m], ki[m], __builtin_fma(dr[m], kr[m], c ? o_re[1][m] : o_re[0][m]));
-          const double im = __builtin_fma(di[m], kr[m], __builtin_fma(dr[m], ki[m], c ? o_im[1][m] : o_im[0][m]));
+          double re = c ? o_re[1][m] : o_re[0][m], im = c ? o_im[1][m] : o_im[0][m];
+          cmac(re, im, dr[m], di[m], d2{kr[m], ki[m]});
           if (c) { o_re[1][m] = re; o_im[1][m] = im; } else { o_re[0][m] = re; o_im[0][m] = im; }
         }
       }
@@ -401,8 +393,7 @@ __global__ __launch_bounds__(F::THREADS) void ubr_phase1_kernel(const uint64_t *
     for (int bb = 0; bb < unfolding; bb++)
       if ((j >> bb) & 1) a_i += ct[bb];
     const int rot = j ? (int)modswitch<LOG2N2>(a_i) : 0;
-    const int a_lo = rot & (N - 1);
-    const bool flip = (rot & N) != 0;
+    const auto [a_lo, flip] = split_rotation(rot, N);
     const uint64_t *__restrict__ src = su + ((size_t)g * key_exp + j) * trgsw_sz + (size_t)qc * N;
 #pragma unroll
     for (int m = 0; m < 8; m++) {
@@ -437,9 +428,7 @@ __global__ __launch_bounds__(F::THREADS) void ubr_phase2_kernel(const d2 *__rest
   uint64_t acc[2][2][8];
   {
     const uint32_t bbar = modswitch<LOG2N2>(ct[n] + prec_offset);
-    const int rot = (2 * N - (int)bbar) & (2 * N - 1);
-    const int a_lo = rot & (N - 1);
-    const bool flip = (rot & N) != 0;
+    const auto [a_lo, flip] = first_rotation(bbar, N);
 #pragma unroll
     for (int c = 0; c < 2; c++)
 #pragma unroll
@@ -448,11 +437,10 @@ __global__ __launch_bounds__(F::THREADS) void ubr_phase2_kernel(const d2 *__rest
         acc[c][1][m] = rot_coeff<N>(tv + c * N, M + m * T + t, a_lo, flip);
       }
   }
-  uint64_t off = 1ull << (63 - l * Bg_bit);
-  for (int i = 0; i < l; i++) off += 1ull << (63 - i * Bg_bit);
+  const uint64_t off = GADGET_OFFSET(l, Bg_bit);
   const uint32_t mask = (1u << Bg_bit) - 1;
   const int half = 1 << (Bg_bit - 1);
-  const RoundCtx scale(0x1p-64 / (double)M);
+  const RoundCtx scale = round_scale<M>();
   const size_t key_sz = (size_t)2 * l * 2 * M;
 #pragma unroll 1
   for (int g = 0; g < groups; g++) {
@@ -477,10 +465,8 @@ __global__ __launch_bounds__(F::THREADS) void ubr_phase2_kernel(const d2 *__rest
 #pragma unroll
       for (int m = 0; m < 8; m++) {
         const d2 k0 = row[m * T + t], k1 = row[M + m * T + t];
-        o_re[0][m] = __builtin_fma(-di[m], k0.y, __builtin_fma(dr[m], k0.x, o_re[0][m]));
-        o_im[0][m] = __builtin_fma(di[m], k0.x, __builtin_fma(dr[m], k0.y, o_im[0][m]));
-        o_re[1][m] = __builtin_fma(-di[m], k1.y, __builtin_fma(dr[m], k1.x, o_re[1][m]));
-        o_im[1][m] = __builtin_fma(di[m], k1.x, __builtin_fma(dr[m], k1.y, o_im[1][m]));
+        cmac(o_re[0][m], o_im[0][m], dr[m], di[m], k0);
+        cmac(o_re[1][m], o_im[1][m], dr[m], di[m], k1);
       }
     }
 #pragma unroll
@@ -524,17 +510,14 @@ __global__ __launch_bounds__(2 * F::THREADS) void ubr_phase2_wide_kernel(const d
   fft.init(tw, t);
   {
     const uint32_t bbar = modswitch<LOG2N2>(ct[n] + prec_offset);
-    const int rot = (2 * N - (int)bbar) & (2 * N - 1);
-    const int a_lo = rot & (N - 1);
-    const bool flip = (rot & N) != 0;
+    const auto [a_lo, flip] = first_rotation(bbar, N);
     for (int x = tid; x < 2 * N; x += WG) acc[x] = rot_coeff<N>(tv + (x / N) * N, x & (N - 1), a_lo, flip);
   }
   workgroup_sync();
-  uint64_t off = 1ull << (63 - l * Bg_bit);
-  for (int i = 0; i < l; i++) off += 1ull << (63 - i * Bg_bit);
+  const uint64_t off = GADGET_OFFSET(l, Bg_bit);
   const uint32_t mask = (1u << Bg_bit) - 1;
   const int half = 1 << (Bg_bit - 1);
-  const RoundCtx scale(0x1p-64 / (double)M);
+  const RoundCtx scale = round_scale<M>();
   const size_t key_sz = (size_t)2 * l * 2 * M;
 #pragma unroll 1
   for (int g = 0; g < groups; g++) {
@@ -567,8 +550,7 @@ __global__ __launch_bounds__(2 * F::THREADS) void ubr_phase2_wide_kernel(const d
 #pragma unroll
         for (int m = 0; m < 8; m++) {
           const d2 d = dr[m * T + t], k = kk[r][m];
-          o_re[m] = __builtin_fma(-d.y, k.y, __builtin_fma(d.x, k.x, o_re[m]));
-          o_im[m] = __builtin_fma(d.y, k.x, __builtin_fma(d.x, k.y, o_im[m]));
+          cmac(o_re[m], o_im[m], d.x, d.y, k);
         }
       }
       workgroup_sync();

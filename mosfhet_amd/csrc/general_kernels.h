@@ -102,24 +102,21 @@ __global__ __launch_bounds__(GEN_THREADS) void pbs_general_kernel(GeneralParams 
     // src/bootstrap.c:194-195: acc = tv * X^(2N - bbar)
     const uint64_t *__restrict__ tv = p.tv + b * (size_t)p.tv_stride;
     const int rot = (2 * N - modsw(pre(ct[p.n]) + p.prec_offset)) & (2 * N - 1);
-    const int a_lo = rot & (N - 1);
-    const bool flip = (rot & N) != 0;
+    const auto [a_lo, flip] = split_rotation(rot, N);
     for (int x = threadIdx.x; x < (k + 1) * N; x += GEN_THREADS) {
       const int c = x / N, i = x - c * N;
       acc[x] = rot_coeff_rt(tv + (size_t)c * N, i, a_lo, flip, N);
     }
   }
   workgroup_sync();
-  uint64_t off = 1ull << (63 - l * Bg);
-  for (int i = 0; i < l; i++) off += 1ull << (63 - i * Bg);
+  const uint64_t off = GADGET_OFFSET(l, Bg);
   const RoundCtx scale(p.logM);
   const size_t trgsw_sz = (size_t)(k + 1) * l * (k + 1) * M;
   for (int i = 0; i < p.n; i++) {
     const int abar = modsw(pre(ct[i]));
     if (abar == 0) continue;   // src/bootstrap.c:114
     const d2 *__restrict__ bkrow = p.bk + (size_t)i * trgsw_sz;
-    const int a_lo = abar & (N - 1);
-    const bool flip = (abar & N) != 0;
+    const auto [a_lo, flip] = split_rotation(abar, N);
     for (int q = 0; q <= k; q++) {
       const uint64_t *src = acc + (size_t)q * N;
       for (int j = 0; j < l; j++) {
@@ -136,8 +133,7 @@ __global__ __launch_bounds__(GEN_THREADS) void pbs_general_kernel(GeneralParams 
           for (int x = threadIdx.x; x < M; x += GEN_THREADS) {
             const d2 d = z[x], kk = row[(size_t)c * M + x];
             d2 o = first ? d2{0.0, 0.0} : prod[(size_t)c * M + x];
-            o.x = __builtin_fma(-d.y, kk.y, __builtin_fma(d.x, kk.x, o.x));
-            o.y = __builtin_fma(d.y, kk.x, __builtin_fma(d.x, kk.y, o.y));
+            cmac(o, d.x, d.y, kk);
             prod[(size_t)c * M + x] = o;     // same thread reads and writes slot x of every row: no cross-thread hazard in global memory
           }
         workgroup_sync();
@@ -162,7 +158,7 @@ __global__ __launch_bounds__(GEN_THREADS) void pbs_general_kernel(GeneralParams 
     for (int x = threadIdx.x; x < k * N; x += GEN_THREADS) {
       const int c = x / N, j = x - c * N;
       const uint64_t *a = acc + (size_t)c * N;
-      dst[x] = j == 0 ? a[0] : (0 - a[N - j]);
+      dst[x] = extract0_coeff(a, j, N);
     }
     if (threadIdx.x == 0) dst[(size_t)k * N] = acc[(size_t)k * N];
   }
@@ -181,8 +177,7 @@ __global__ __launch_bounds__(GEN_THREADS) void external_product_general_kernel(c
   const uint64_t *base_all = in0 ? in0 + b * (size_t)(k + 1) * N : nullptr;
   d2 *prod = prod_all + b * (size_t)(k + 1) * M;
   const d2 *__restrict__ g = trgsw + b * key_stride;
-  uint64_t off = 1ull << (63 - l * Bg);
-  for (int i = 0; i < l; i++) off += 1ull << (63 - i * Bg);
+  const uint64_t off = GADGET_OFFSET(l, Bg);
   const RoundCtx scale(logM);
   for (int q = 0; q <= k; q++) {
     const uint64_t *src = src_all + (size_t)q * N;
@@ -200,8 +195,7 @@ __global__ __launch_bounds__(GEN_THREADS) void external_product_general_kernel(c
         for (int x = threadIdx.x; x < M; x += GEN_THREADS) {
           const d2 d = z[x], kk = row[(size_t)c * M + x];
           d2 o = first ? d2{0.0, 0.0} : prod[(size_t)c * M + x];
-          o.x = __builtin_fma(-d.y, kk.y, __builtin_fma(d.x, kk.x, o.x));
-          o.y = __builtin_fma(d.y, kk.x, __builtin_fma(d.x, kk.y, o.y));
+          cmac(o, d.x, d.y, kk);
           prod[(size_t)c * M + x] = o;
         }
       workgroup_sync();

@@ -51,12 +51,8 @@ struct LutParams {
   int pack_log;                      // lut_tables_finish_kernel: an entry is m = 2^pack_log adjacent coefficients; step i rotates by m 2^i, m extractions; out is [count][out_tables][m][N + 1]
 };
 
-// 2^(63 - l Bg) + sum_i 2^(63 - i Bg): the rounding offset of polynomial_decompose_i for all l digits at once (pbs_kernel's `off`)
-__device__ __forceinline__ uint64_t lut_gadget_offset(int l, int Bg_bit) {
-  uint64_t off = 1ull << (63 - l * Bg_bit);
-  for (int i = 0; i < l; i++) off += 1ull << (63 - i * Bg_bit);
-  return off;
-}
+// GADGET_OFFSET as a function: these kernels have always taken it through one, and the loop compiles differently as text in the kernel (cmux_steps.h)
+__device__ __forceinline__ uint64_t lut_gadget_offset(int l, int Bg_bit) { return GADGET_OFFSET(l, Bg_bit); }
 
 // Table preparation: block (j, r = q l + lv) of table blockIdx.y writes D[table][j][r] = DFT(digit lv of (table[j + half0] - table[j]).component q), slot order [m][thread].
 template <class F>
@@ -95,7 +91,7 @@ __global__ __launch_bounds__(F::THREADS, 2) void lut_level0_kernel(LutParams p) 
   const size_t b = blockIdx.y;
   F fft;
   fft_setup(fft, p.tw, t);
-  const RoundCtx scale(0x1p-64 / (double)M);
+  const RoundCtx scale = round_scale<M>();
   const d2 *__restrict__ sel = p.sel + (((size_t)p.first + b) * p.size + (size_t)(p.size - 1)) * ((size_t)rows * 2 * M);
   const int nodes = p.tables * p.half0;
   for (int u = blockIdx.x; u < nodes; u += gridDim.x) {
@@ -117,15 +113,9 @@ __global__ __launch_bounds__(F::THREADS, 2) void lut_level0_kernel(LutParams p) 
 #pragma unroll
       for (int m = 0; m < 8; m++) k1[m] = row[M + m * T + t];
 #pragma unroll
-      for (int m = 0; m < 8; m++) {
-        o_re[0][m] = __builtin_fma(-x[m].y, k0[m].y, __builtin_fma(x[m].x, k0[m].x, o_re[0][m]));
-        o_im[0][m] = __builtin_fma(x[m].y, k0[m].x, __builtin_fma(x[m].x, k0[m].y, o_im[0][m]));
-      }
+      for (int m = 0; m < 8; m++) cmac(o_re[0][m], o_im[0][m], x[m].x, x[m].y, k0[m]);
 #pragma unroll
-      for (int m = 0; m < 8; m++) {
-        o_re[1][m] = __builtin_fma(-x[m].y, k1[m].y, __builtin_fma(x[m].x, k1[m].x, o_re[1][m]));
-        o_im[1][m] = __builtin_fma(x[m].y, k1[m].x, __builtin_fma(x[m].x, k1[m].y, o_im[1][m]));
-      }
+      for (int m = 0; m < 8; m++) cmac(o_re[1][m], o_im[1][m], x[m].x, x[m].y, k1[m]);
     }
     fft.inverse2(o_re[0], o_im[0], o_re[1], o_im[1], xch, t);
     const uint64_t *__restrict__ base = p.lut + (size_t)tb * p.lut_stride + (size_t)j * 2 * N;
@@ -183,8 +173,7 @@ __device__ __forceinline__ void lut_team_product(const uint64_t *home, bool rota
 #pragma unroll
       for (int m = 0; m < 8; m++) {
         const d2 d = dr[m * T + t], k = kk[r][m];
-        o_re[m] = __builtin_fma(-d.y, k.y, __builtin_fma(d.x, k.x, o_re[m]));
-        o_im[m] = __builtin_fma(d.y, k.x, __builtin_fma(d.x, k.y, o_im[m]));
+        cmac(o_re[m], o_im[m], d.x, d.y, k);
       }
     }
     workgroup_sync();   // the transformed digits are consumed: the buffers are free for the next phase's exchanges / the inverse
@@ -212,7 +201,7 @@ __global__ __launch_bounds__(2 * F::THREADS, 2) void lut_cmux_kernel(LutParams p
   F fft;
   fft_setup(fft, p.tw, t);
   const uint64_t off = lut_gadget_offset(l, Bg_bit);
-  const RoundCtx scale(0x1p-64 / (double)M);
+  const RoundCtx scale = round_scale<M>();
   const size_t sel_sz = (size_t)2 * l * 2 * M;   // one selector, in complex slots
   double o_re[8], o_im[8];
 
@@ -241,8 +230,8 @@ __global__ __launch_bounds__(2 * F::THREADS, 2) void lut_cmux_kernel(LutParams p
   for (int w = tid; w < 2 * N; w += WG) acc[w] = src[w];
   workgroup_sync();
   for (int i = 0; i < p.steps; i++) {
-    const int abar = 2 * N - (1 << i);
-    lut_team_product(acc, true, abar & (N - 1), (abar & N) != 0, p.sel + (((size_t)p.first + b) * p.size + (size_t)i) * sel_sz, l, Bg_bit, off, fft, xch_all, team, t,
+    const Rotation step = split_rotation(2 * N - (1 << i), N);
+    lut_team_product(acc, true, step.a_lo, step.flip, p.sel + (((size_t)p.first + b) * p.size + (size_t)i) * sel_sz, l, Bg_bit, off, fft, xch_all, team, t,
                      o_re, o_im);
     // (every read of the old accumulator stands in front of the last phase's barriers: the update below is this thread's own 16 words)
     uint64_t *ac = acc + (size_t)team * N;
@@ -255,7 +244,7 @@ __global__ __launch_bounds__(2 * F::THREADS, 2) void lut_cmux_kernel(LutParams p
   }
   // src/trlwe.c:540-552 at idx = 0: a[0] = acc_a[0], a[j] = -acc_a[N - j]; b = acc_b[0]
   uint64_t *dst = p.out + ((size_t)p.first + b) * (size_t)(N + 1);
-  for (int j = tid; j < N; j += WG) dst[j] = (j == 0) ? acc[0] : (0 - acc[N - j]);
+  for (int j = tid; j < N; j += WG) dst[j] = extract0_coeff(acc, j, N);
   if (tid == 0) dst[N] = acc[N];
 }
 
@@ -292,7 +281,7 @@ __global__ __launch_bounds__(2 * F::THREADS, 2) void lut_tables_finish_kernel(Lu
   F fft;
   fft_setup(fft, p.tw, t);
   const uint64_t off = lut_gadget_offset(l, Bg_bit);
-  const RoundCtx scale(0x1p-64 / (double)M);
+  const RoundCtx scale = round_scale<M>();
   const size_t sel_sz = (size_t)2 * l * 2 * M;   // one selector, in complex slots
   double o_re[8], o_im[8];
 
@@ -302,12 +291,12 @@ __global__ __launch_bounds__(2 * F::THREADS, 2) void lut_tables_finish_kernel(Lu
   }
   workgroup_sync();
   for (int i = 0; i < p.steps; i++) {
-    const int abar = 2 * N - (1 << (i + p.pack_log));   // (the launcher keeps i + pack_log < log2 N)
+    const Rotation step = split_rotation(2 * N - (1 << (i + p.pack_log)), N);   // (the launcher keeps i + pack_log < log2 N)
     const d2 *__restrict__ sel = p.sel + (((size_t)p.first + b) * p.size + (size_t)i) * sel_sz;
 #pragma unroll 1
     for (int k = 0; k < nt; k++) {
       uint64_t *acc = accs + (size_t)k * 2 * N;
-      lut_team_product(acc, true, abar & (N - 1), (abar & N) != 0, sel, l, Bg_bit, off, fft, xch_all, team, t, o_re, o_im);
+      lut_team_product(acc, true, step.a_lo, step.flip, sel, l, Bg_bit, off, fft, xch_all, team, t, o_re, o_im);
       // (every read of the old accumulator stands in front of the last phase's barriers: the update below is this thread's own 16 words)
       uint64_t *ac = acc + (size_t)team * N;
 #pragma unroll

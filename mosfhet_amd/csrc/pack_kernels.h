@@ -71,9 +71,8 @@ __global__ __launch_bounds__(F::THREADS, 1) void tlwe_pack_kernel(PackParams p, 
   const int e1 = e0 + p.part_entries < p.n_in ? e0 + p.part_entries : p.n_in;
   F fft;
   fft.init(tw, tid);
-  uint64_t off = 1ull << (63 - t * base_bit);
-  for (int i = 0; i < t; i++) off += 1ull << (63 - i * base_bit);
-  const RoundCtx scale(0x1p-64 / (double)M);
+  const uint64_t off = GADGET_OFFSET(t, base_bit);
+  const RoundCtx scale = round_scale<M>();
   const size_t entry_sz = (size_t)t * 2 * M;
   double o_re[2][8], o_im[2][8];
 #pragma unroll

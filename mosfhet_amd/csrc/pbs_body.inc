@@ -3,10 +3,7 @@
   static_assert(!BYC || (F::N == 2048 && L % 2 == 0), "the by-component order exists where pbs_split_kernel does");
   static_assert(G == 1 || (F::THREADS == 64 && !BYC), "several teams per workgroup: their transforms must not use workgroup barriers");
   constexpr int N = F::N, M = F::M, T = F::THREADS, LOG2N2 = F::LOGM + 2;
-  // Every output of the external product is a sum of 2L * N products digit * key coefficient with |digit| <= 2^(BG-1) and |key| <= 2^63
-  // (the key is (double)(int64_t) of torus words): |sum| <= 2^(ceil log2(2L) + log2 N + BG - 1 + 63).  Below 2^83 the rounding needs no
-  // reduction mod 1 in front (add_rounded); that holds for SET_1's 2 x 2^8 gadget at N = 1024 (2^82) and is decided at compile time.
-  constexpr bool kReduce = !(BG > 0 && kCeilLog2<2 * L>::value + (F::LOGM + 1) + BG - 1 + 63 < 83);
+  constexpr bool kReduce = kProductNeedsReduce<F, L, BG>;
   // SET_1's instantiation (G = 1 and G > 1) keeps both accumulator components NEGATED, -acc mod 2^64, from the first load to the last store: the digits then take
   // rot(acc) + (-acc[j]) + off and the step's tail (-acc) + (-increment), each by one carry-free 64-bit add, where +acc needs a 64-bit subtract for the digits and a
   // carry chain for the tail (cmux_digits: NEG; neg_rounded).  Component b's add is done by the LDS unit (a 64-bit DS add without return, on the team's own slice:
@@ -55,8 +52,7 @@
     const uint32_t bbar = modswitch<LOG2N2>(pbs_pre(ct[p.n], p, LOG2N2) + p.prec_offset);
     // (kNegAcc: -(tv X^r) = tv X^(r + N))
     const int rot = (2 * N - (int)bbar + (kNegAcc ? N : 0)) & (2 * N - 1);
-    const int a_lo = rot & (N - 1);
-    const bool flip = (rot & N) != 0;
+    const auto [a_lo, flip] = split_rotation(rot, N);
 #pragma unroll
     for (int m = 0; m < 8; m++) {
       al[m] = rot_coeff<N>(tv, m * T + t, a_lo, flip);
@@ -67,10 +63,8 @@
   }
   F::sync();
 
-  uint64_t off = 1ull << (63 - L * Bg_bit);
-#pragma unroll
-  for (int i = 0; i < L; i++) off += 1ull << (63 - i * Bg_bit);
-  const RoundCtx scale(0x1p-64 / (double)M);
+  const uint64_t off = GADGET_OFFSET(L, Bg_bit);
+  const RoundCtx scale = round_scale<M>();
   const size_t row_sz = (size_t)2 * L * 2 * M;
 
   int next_meet = __builtin_amdgcn_readfirstlane(G > 1 && p.phase_every > 0 ? 0 : -1);
@@ -87,8 +81,9 @@
     if constexpr (G > 1) asm volatile("" : "+s"(abar));   // (the skip test on the scalar unit: as a 64-bit compare against a constant it holds two vector registers over the loop)
     if (abar == 0) continue;  // src/bootstrap.c:114
     const d2 *__restrict__ bkrow = p.bk + (size_t)i * row_sz;
-    const int a_lo = abar & (N - 1);
-    const bool flip = ((abar & N) != 0) != kNegAcc;   // (kNegAcc: what is rotated is -acc, the digits want +rot(acc))
+    const Rotation step = split_rotation(abar, N);
+    const int a_lo = step.a_lo;
+    const bool flip = step.flip != kNegAcc;   // (kNegAcc: what is rotated is -acc, the digits want +rot(acc))
     double o_re[2][8], o_im[2][8];
 #pragma unroll
     for (int c = 0; c < 2; c++)
@@ -182,7 +177,7 @@
       for (int j = te; j < N; j += T) dst[j] = (j == 0) ? (0 - st[0]) : st[N - j];
       if (te == 0) dst[N] = 0 - acc1[0];
     } else {
-      for (int j = te; j < N; j += T) dst[j] = (j == 0) ? st[0] : (0 - st[N - j]);
+      for (int j = te; j < N; j += T) dst[j] = extract0_coeff(st, j, N);
       if (te == 0) dst[N] = acc1[0];
     }
   } else {

@@ -135,9 +135,8 @@ __device__ __forceinline__ void trace_pack_body(d2 *xch, uint64_t *acc1, const F
   constexpr int N = F::N, M = F::M, T = F::THREADS, LOGN = F::LOGM + 1;
   static_assert(F::XCH_SLOTS * sizeof(d2) >= N * sizeof(uint64_t), "the exchange buffer stages one polynomial of torus words");
   const int t = p.t, base_bit = p.base_bit;
-  uint64_t off = 1ull << (63 - t * base_bit);
-  for (int i = 0; i < t; i++) off += 1ull << (63 - i * base_bit);
-  const RoundCtx scale(0x1p-64 / (double)M);
+  const uint64_t off = GADGET_OFFSET(t, base_bit);
+  const RoundCtx scale = round_scale<M>();
   const size_t entry_sz = (size_t)t * 2 * M;
   uint64_t al[8], ah[8];   // component a, coefficient x = m T + tid resp. M + m T + tid
   int steps = LOGN;
@@ -147,7 +146,7 @@ __device__ __forceinline__ void trace_pack_body(d2 *xch, uint64_t *acc1, const F
 #pragma unroll
     for (int m = 0; m < 8; m++) {
       const int x = m * T + tid;
-      al[m] = x == 0 ? c[0] : 0 - c[N - x];
+      al[m] = extract0_coeff(c, x, N);
       ah[m] = 0 - c[M - x];           // coefficient M + x: N - (M + x)
       acc1[x] = x == 0 ? c[N] : 0;
       acc1[M + x] = 0;
@@ -167,8 +166,8 @@ __device__ __forceinline__ void trace_pack_body(d2 *xch, uint64_t *acc1, const F
 #pragma unroll
       for (int m = 0; m < 8; m++) {
         const int x = m * T + tid;
-        const uint64_t e_lo = (x == 0 ? c0[0] : 0 - c0[N - x]) & k0, e_hi = (0 - c0[M - x]) & k0;
-        const uint64_t o_lo = c1[M - x] & k1, o_hi = (x == 0 ? c1[0] : 0 - c1[N - x]) & k1;
+        const uint64_t e_lo = extract0_coeff(c0, x, N) & k0, e_hi = (0 - c0[M - x]) & k0;
+        const uint64_t o_lo = c1[M - x] & k1, o_hi = extract0_coeff(c1, x, N) & k1;
         const uint64_t eb = x == 0 ? c0[N] & k0 : 0, ob = x == 0 ? c1[N] & k1 : 0;
         al[m] = e_lo + o_lo; va_lo[m] = e_lo - o_lo;
         ah[m] = e_hi + o_hi; va_hi[m] = e_hi - o_hi;
@@ -215,9 +214,8 @@ __device__ __forceinline__ void rlwe_priv_keyswitch_body(d2 *xch, const F &fft, 
                                                          int t, int base_bit, d2 *__restrict__ sel, int l, int tid) {
   constexpr int N = F::N, M = F::M, T = F::THREADS;
   const uint64_t *c = in + (size_t)blockIdx.x * (2 * N);
-  uint64_t off = 1ull << (63 - t * base_bit);
-  for (int i = 0; i < t; i++) off += 1ull << (63 - i * base_bit);
-  const RoundCtx scale(0x1p-64 / (double)M);
+  const uint64_t off = GADGET_OFFSET(t, base_bit);
+  const RoundCtx scale = round_scale<M>();
   uint64_t res_a_lo[8], res_a_hi[8], res_b_lo[8], res_b_hi[8];
 #pragma unroll
   for (int m = 0; m < 8; m++) { res_a_lo[m] = 0; res_a_hi[m] = 0; res_b_lo[m] = 0; res_b_hi[m] = 0; }
@@ -303,13 +301,11 @@ __device__ __forceinline__ void polylinear_body(d2 *xch, const F &fft, const Tra
     for (int m = 0; m < 8; m++) { wv[m] = w[m * T + tid]; a[m] = xa[m * T + tid]; bb[m] = xa[M + m * T + tid]; }
 #pragma unroll
     for (int m = 0; m < 8; m++) {
-      o_re[0][m] = __builtin_fma(-a[m].y, wv[m].y, __builtin_fma(a[m].x, wv[m].x, o_re[0][m]));
-      o_im[0][m] = __builtin_fma(a[m].y, wv[m].x, __builtin_fma(a[m].x, wv[m].y, o_im[0][m]));
-      o_re[1][m] = __builtin_fma(-bb[m].y, wv[m].y, __builtin_fma(bb[m].x, wv[m].x, o_re[1][m]));
-      o_im[1][m] = __builtin_fma(bb[m].y, wv[m].x, __builtin_fma(bb[m].x, wv[m].y, o_im[1][m]));
+      cmac(o_re[0][m], o_im[0][m], a[m].x, a[m].y, wv[m]);
+      cmac(o_re[1][m], o_im[1][m], bb[m].x, bb[m].y, wv[m]);
     }
   }
-  const RoundCtx scale(0x1p-64 / (double)M);
+  const RoundCtx scale = round_scale<M>();
   const uint64_t *bias = p.bias ? p.bias + (size_t)j * N : nullptr;
   const int idx = p.idx;
   uint64_t *o = p.out + (size_t)blockIdx.x * (idx < 0 ? (size_t)2 * N : (size_t)N + 1);

@@ -28,6 +28,7 @@ __device__ __forceinline__ d2 unfold2_factor(const d2 &base, unsigned e, int m, 
   if (m == 0) return base;
   const unsigned r3 = ((m & 1) << 2) | (m & 2) | ((m >> 2) & 1);     // bitrev3(m), a constant once unrolled
   const d2 kp = wtab[((r3 * e) & 7u) * (unsigned)(F::N / 4)];
+  // (a complex PRODUCT, the order of oracle_ext.c: a rounded multiplication inside each fma, not cmac's chain from an accumulator)
   return d2{__builtin_fma(-base.y, kp.y, base.x * kp.x), __builtin_fma(base.y, kp.x, base.x * kp.y)};
 }
 
@@ -55,10 +56,7 @@ __device__ __forceinline__ void unfold2_select(d2 (&sel)[COMPS][CNT], const d2 *
     for (int i = 0; i < CNT; i++) {
       const d2 f = unfold2_factor<F>(base[j - 1], e[j - 1], M0 + i, wtab);
 #pragma unroll
-      for (int c = 0; c < COMPS; c++) {
-        sel[c][i].x = __builtin_fma(-f.y, kk[c][i].y, __builtin_fma(f.x, kk[c][i].x, sel[c][i].x));
-        sel[c][i].y = __builtin_fma(f.y, kk[c][i].x, __builtin_fma(f.x, kk[c][i].y, sel[c][i].y));
-      }
+      for (int c = 0; c < COMPS; c++) cmac(sel[c][i], f.x, f.y, kk[c][i]);
     }
   }
 }
@@ -106,8 +104,7 @@ __device__ __forceinline__ void unfold2_mac(double (&o_re)[2][8], double (&o_im)
 #pragma unroll
     for (int i = 0; i < 2; i++) {
       const int m = M0 + i;
-      o_re[c][m] = __builtin_fma(-im[m], sel[c][i].y, __builtin_fma(re[m], sel[c][i].x, o_re[c][m]));
-      o_im[c][m] = __builtin_fma(im[m], sel[c][i].x, __builtin_fma(re[m], sel[c][i].y, o_im[c][m]));
+      cmac(o_re[c][m], o_im[c][m], re[m], im[m], sel[c][i]);
     }
 }
 
@@ -133,9 +130,7 @@ __global__ __launch_bounds__(F::THREADS, 2) void pbs_unfold2_kernel(Unfold2Param
     // src/bootstrap.c:194-195: acc = tv * X^(2N - bbar)
     const uint64_t *__restrict__ tv = p.tv + b * (size_t)p.tv_stride;
     const uint32_t bbar = modswitch<LOG2N2>(pbs_pre(ct[p.n], p, LOG2N2) + p.prec_offset);
-    const int rot = (2 * N - (int)bbar) & (2 * N - 1);
-    const int a_lo = rot & (N - 1);
-    const bool flip = (rot & N) != 0;
+    const auto [a_lo, flip] = first_rotation(bbar, N);
 #pragma unroll
     for (int m = 0; m < 8; m++) {
       al[m] = rot_coeff<N>(tv, m * T + t, a_lo, flip);
@@ -145,10 +140,8 @@ __global__ __launch_bounds__(F::THREADS, 2) void pbs_unfold2_kernel(Unfold2Param
     }
   }
   F::sync();
-  uint64_t off = 1ull << (63 - L * Bg_bit);
-#pragma unroll
-  for (int i = 0; i < L; i++) off += 1ull << (63 - i * Bg_bit);
-  const RoundCtx scale(0x1p-64 / (double)M);
+  const uint64_t off = GADGET_OFFSET(L, Bg_bit);
+  const RoundCtx scale = round_scale<M>();
   const size_t sample_sz = (size_t)2 * L * 2 * M;                                     // one TRGSW sample in complex slots
   const uint32_t mask = (1u << Bg_bit) - 1;
   const int half = 1 << (Bg_bit - 1);
@@ -216,7 +209,7 @@ __global__ __launch_bounds__(F::THREADS, 2) void pbs_unfold2_kernel(Unfold2Param
     }
     F::sync();
     uint64_t *dst = p.out + b * (size_t)(N + 1);
-    for (int j = t; j < N; j += T) dst[j] = (j == 0) ? st[0] : (0 - st[N - j]);
+    for (int j = t; j < N; j += T) dst[j] = extract0_coeff(st, j, N);
     if (t == 0) dst[N] = acc1[0];
   } else {
     uint64_t *dst = p.out + b * (size_t)(2 * N);

@@ -1,6 +1,6 @@
 // pbs_sign_forms.cpp -- the gadget digits of SET_1's CMUX step (N = 1024, l = 2, Bg = 2^8, negated resident accumulators) in their two integer forms, on the
 // host (no GPU, no HIP): plain C++ copies of
-//   * the form as it was (bootstrap_kernels.h: rot_coeff, digit_source<.., NEG>, Digits<2, 8>::pack and digit): a compare for the rotation's sign, a conditional
+//   * the form as it was (cmux_steps.h: rot_coeff; bootstrap_kernels.h: digit_source<.., NEG>, Digits<2, 8>::pack and digit): a compare for the rotation's sign, a conditional
 //     64-bit negate, the home word and the offset added, the top 16 bits flipped by 0x8080 and cut by signed bit-field extracts;
 //   * the sign-free form (cmux_digits<.., SF>, digit_source_hi, Digits<2, 8, RAW>): sign and index from ONE 11-bit subtraction, the sign applied by two XORs around
 //     one carry-free 64-bit add, the high dword kept raw and digit lv taken as (byte 3 - lv) - 128;

@@ -160,6 +160,83 @@ def test_kernel_table_of_the_build(native_lib):
     assert len(rows) < 330, "%d kernel instantiations" % len(rows)
 
 
+def test_source_hash_covers_every_included_file():
+    """Every file the device source includes by a quoted name is in the build's source hash (mosfhet_amd/build.py: DEPS): a header that is not would leave a stale
+    library in place after it changes."""
+    from mosfhet_amd import build
+    csrc = os.path.join(ROOT, "mosfhet_amd", "csrc")
+    hashed = set(os.path.normpath(os.path.join(csrc, f)) for f in build.HIP_SOURCES + build.DEPS)
+    assert os.path.join(csrc, "cmux_steps.h") in hashed
+    for name in os.listdir(csrc):
+        if name.endswith((".h", ".inc", ".hip")):
+            for inc in re.findall(r'^\s*#include\s+"([^"]+)"', open(os.path.join(csrc, name)).read(), flags=re.M):
+                assert os.path.normpath(os.path.join(csrc, inc)) in hashed, "%s includes %s, which is not in DEPS" % (name, inc)
+
+
+def test_kernel_listing_diff_tool():
+    """tools/kernel_listing_diff.py on two synthetic three-kernel listings: identical; different only in what two builds of the same source differ in (comments,
+    .loc / .file / .ident, the __hip_cuid_* symbol, the function index of local labels); one instruction changed in one kernel; one kernel missing."""
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import kernel_listing_diff as kld
+
+    def kernel(name, index, body, vgprs=8, note="", loc=""):
+        return "\n".join(["\t.text", "\t.protected\t%s ; -- Begin function %s" % (name, name), "\t.globl\t%s" % name, "\t.type\t%s,@function" % name, "%s:%s; @%s" % (name, " " * 24, name),
+                          loc + "\ts_load_dwordx2 s[0:1], s[4:5], 0x0", "\ts_cbranch_execz .LBB%d_2 %s" % (index, note)] + body +
+                         [".LBB%d_2:" % index, "\ts_endpgm", "\t.section\t.rodata,\"a\",@progbits", "\t.amdhsa_kernel %s" % name, "\t\t.amdhsa_next_free_vgpr %d" % vgprs,
+                          "\t.end_amdhsa_kernel", "\t.text", ".Lfunc_end%d:" % index, "\t.size\t%s, .Lfunc_end%d-%s" % (name, index, name), "\t; NumVgprs: %d" % vgprs])
+
+    def listing(kernels, cuid="0123abcd", ident="clang 1", file_line=""):
+        return "\n".join([file_line + "\t.amdgcn_target \"amdgcn-amd-amdhsa--gfx950\""] + kernels +
+                         ["\t.type\t__hip_cuid_%s,@object" % cuid, "__hip_cuid_%s:" % cuid, "\t.byte\t0", "\t.ident\t\"%s\"" % ident, "\t.amdgpu_metadata", "---", "...", ""])
+
+    add = ["\tv_add_u32_e32 v1, v2, v3"]
+    names = ["_Z5firstPm", "_Z6secondPm", "_Z5thirdPm"]
+    parent = listing([kernel(n, i, add) for i, n in enumerate(names)])
+    assert list(kld.kernels(parent)) == names
+    assert "s_cbranch_execz .LBB_2" in kld.kernels(parent)[names[1]] and ".amdhsa_next_free_vgpr 8" in kld.kernels(parent)[names[1]]
+
+    report, same = kld.compare(parent, parent)
+    assert same and report[0] == "kernels: 3 in the parent listing, 3 in the new one" and "kernels that differ: 0" in report
+
+    # another function index (a kernel's place in the file), other comments, debug lines, another cuid and compiler name
+    ignored = listing([kernel(n, i + 7, add, note="; taken", loc="\t.loc\t1 %d 0\n" % i) for i, n in enumerate(names)], cuid="feedbeef", ident="clang 2",
+                      file_line="\t.file\t\"other.hip\"\n")
+    assert ignored != parent
+    report, same = kld.compare(parent, ignored)
+    assert same, report
+
+    changed = listing([kernel(n, i, ["\tv_sub_u32_e32 v1, v2, v3"] if i == 1 else add) for i, n in enumerate(names)])
+    report, same = kld.compare(parent, changed)
+    assert not same and "kernels that differ: 1" in report
+    text = "\n".join(report)
+    assert "second(unsigned long*)" in text and "first(" not in text and "third(" not in text
+    assert "parent: v_add_u32_e32 v1, v2, v3" in text and "new: v_sub_u32_e32 v1, v2, v3" in text
+    # ... the resource block is part of a kernel's text, and the name filter selects by demangled name
+    report, same = kld.compare(parent, listing([kernel(n, i, add, vgprs=16 if i == 2 else 8) for i, n in enumerate(names)]))
+    assert not same and "third(unsigned long*)" in "\n".join(report) and ".amdhsa_next_free_vgpr 16" in "\n".join(report)
+    report, same = kld.compare(parent, changed, "first")
+    assert same and report[0] == "kernels: 1 in the parent listing, 1 in the new one"
+
+    missing = listing([kernel(n, i, add) for i, n in enumerate(names[:2])])
+    report, same = kld.compare(parent, missing)
+    assert not same and report[0] == "kernels: 3 in the parent listing, 2 in the new one" and "only in the parent listing: third(unsigned long*)" in report
+    report, same = kld.compare(missing, parent)
+    assert not same and "only in the new listing: third(unsigned long*)" in report
+
+    # the command line: exit status 0 only for equal kernel sets with no difference
+    import subprocess
+    import tempfile
+    with tempfile.TemporaryDirectory() as tmp:
+        paths = {}
+        for key, text in (("parent", parent), ("ignored", ignored), ("changed", changed), ("missing", missing)):
+            paths[key] = os.path.join(tmp, key + ".s")
+            with open(paths[key], "w") as fh:
+                fh.write(text)
+        tool = [sys.executable, os.path.join(ROOT, "tools", "kernel_listing_diff.py"), paths["parent"]]
+        assert [subprocess.run(tool + [paths[k]], capture_output=True).returncode for k in ("parent", "ignored", "changed", "missing")] == [0, 0, 1, 1]
+
+
 def test_no_lds_reads_emitted_behind_a_workgroup_barrier():
     """The root cause of the "wrong units" of rounds 3 - 5 (experiments/README.md, Round 5) was the COMPILER moving LDS reads that the source places in front of a
     workgroup barrier behind it (machine sinking into the block after a conditional branch; S_BARRIER is no store to that pass).  Every barrier of the library now goes
