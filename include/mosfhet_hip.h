@@ -297,7 +297,7 @@ int mosfhet_hip_ksk_export_rows(mosfhet_hip_ksk_t ksk, size_t first_row, size_t 
 int mosfhet_hip_trlwe_table_ksk_generate_compressed(mosfhet_hip_ctx_t ctx, mosfhet_hip_ksk_t *out, int kind, const uint64_t *h_s_out, int N,
                                                     const uint64_t *h_s_in, int n, int t, int base_bit, double sigma, uint64_t seed);
 /* tlwe_keyswitch_no_precomp (src/tlwe.c:305-320): key = plain device rows [n_in][t][n_out + 1], one sample per (input word, digit position), multiplied by the
- * digit in the kernel (the reference's double rounding offset included) */
+ * digit in the kernel (the reference's double rounding offset included).  count <= 65535 (MOSFHET_HIP_EINVAL beyond it, before any device call). */
 int mosfhet_hip_tlwe_keyswitch_no_precomp_batch(mosfhet_hip_ctx_t ctx, const uint64_t *d_rows, uint64_t *d_out, const uint64_t *d_in, int count, int n_in, int n_out,
                                                 int t, int base_bit, void *stream);
 /* LUT-packing key switch (trlwe_new_packing_KS_key / trlwe_packing_keyswitch, src/keyswitch.c:214-241,346-366): `torus_base` LWE samples into the `torus_base`

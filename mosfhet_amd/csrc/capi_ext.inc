@@ -796,6 +796,7 @@ extern "C" int mosfhet_hip_tlwe_keyswitch_no_precomp_batch(mosfhet_hip_ctx_t ctx
   if (!ctx || count < 0 || n_in < 1 || n_out < 1 || t < 1 || base_bit < 1 || base_bit > 16 || t * base_bit >= 63) return fail(MOSFHET_HIP_EINVAL, "keyswitch_no_precomp: bad argument");
   if (count == 0) return MOSFHET_HIP_OK;
   if (!d_rows || !d_out || !d_in) return fail(MOSFHET_HIP_EINVAL, "keyswitch_no_precomp: null buffer");
+  if (count > 65535) return fail(MOSFHET_HIP_EINVAL, "keyswitch_no_precomp: count = %d (at most 65535 samples per call: the kernels index the batch by gridDim.z and gridDim.y)", count);
   HIP_TRY(hipSetDevice(ctx->device));
   HIP_TRY(launch_tlwe_keyswitch_scaled(d_rows, d_out, (size_t)n_out + 1, d_in, (size_t)n_in + 1, count, n_in, n_out + 1, t, base_bit, tl_ws(ctx->device), pick(ctx, stream)));
   return MOSFHET_HIP_OK;

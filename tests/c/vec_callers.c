@@ -1,8 +1,8 @@
 /*
  * GPU test of the host-struct face of the digit-parallel radix-integer callers (include/mosfhet_compat.h: mosfhet_vec_*): a plain C program in the shape of the
  * reference application's callers -- integers as arrays of TLWE digits (ufhe_integer's `digits`, applications/multi-ciphertext-arith/include/ufhe.h:18-22), the keys
- * of its ufhe_public_keyset -- that runs add, sub, ReLU, comparison, encrypted and cleartext look-up and the 8 x 8 -> 32 bit multiplication over ALL rows of
- * tests/golden/ufhe_vectors.npz in one call each and must decrypt to what the REFERENCE application decrypted on the reference's own library (the fixture's result
+ * of its ufhe_public_keyset -- that runs add, sub, ReLU, comparison, encrypted and cleartext look-up, the 8 x 8 -> 32 bit multiplication and the shifted addition (one call per pair
+ * of shifts) over ALL rows of tests/golden/ufhe_vectors.npz in one call each and must decrypt to what the REFERENCE application decrypted on the reference's own library (the fixture's result
  * columns; tests/golden/make_ufhe_golden.py).  The rows arrive as text: argv[1] (written by tests/test_gpu_parity.py::test_vector_callers_through_the_c_api).
  * Parameters: the application's ring and gadget (src/ufhe.c:18-20: N = 2048, l = 6, Bg = 2^7, key switch t = 6 base 2^2, radix 4) over a shortened LWE key.
  */
@@ -36,7 +36,7 @@ static TLWE **integers(int M, int digits) {
 int main(int argc, char **argv) {
   if (argc < 2) { fprintf(stderr, "usage: %s rows.txt\n", argv[0]); return 2; }
   static long a[MAXROWS], b[MAXROWS], sel[MAXROWS], table[MAXROWS][16], r_add[MAXROWS], r_sub[MAXROWS], r_relu[MAXROWS], r_lut[MAXROWS], r_cmp_s[MAXROWS], r_cmp_u[MAXROWS],
-      r_lut_ct[MAXROWS], r_mul_s[MAXROWS], r_mul_u[MAXROWS];
+      r_lut_ct[MAXROWS], r_mul_s[MAXROWS], r_mul_u[MAXROWS], r_sl_s[MAXROWS], r_sl_u[MAXROWS], sl_g[MAXROWS], sl_h[MAXROWS];
   FILE *f = fopen(argv[1], "r");
   int M = 0;
   if (!f || fscanf(f, "%d", &M) != 1 || M < 1 || M > MAXROWS) { fprintf(stderr, "cannot read %s\n", argv[1]); return 2; }
@@ -44,6 +44,7 @@ int main(int argc, char **argv) {
     int ok = fscanf(f, "%ld %ld %ld", &a[m], &b[m], &sel[m]) == 3;
     for (int j = 0; j < 16; j++) ok = ok && fscanf(f, "%ld", &table[m][j]) == 1;
     ok = ok && fscanf(f, "%ld %ld %ld %ld %ld %ld %ld %ld %ld", &r_add[m], &r_sub[m], &r_relu[m], &r_lut[m], &r_cmp_s[m], &r_cmp_u[m], &r_lut_ct[m], &r_mul_s[m], &r_mul_u[m]) == 9;
+    ok = ok && fscanf(f, "%ld %ld %ld %ld", &r_sl_s[m], &r_sl_u[m], &sl_g[m], &sl_h[m]) == 4;
     if (!ok) { fprintf(stderr, "row %d of %s is short\n", m, argv[1]); return 2; }
   }
   fclose(f);
@@ -108,6 +109,25 @@ int main(int argc, char **argv) {
   mosfhet_vec_mul_integers(v, xw, DC, xa, D, xb, D, false, M);
   for (int m = 0; m < M; m++) CHECK((long)(uint32_t)decrypt(xw[m], DC) == r_mul_u[m], "unsigned product row %d: %ld, reference %ld", m, (long)(uint32_t)decrypt(xw[m], DC), r_mul_u[m]);
   printf("mul ok\n");
+  /* c = a B^g + b B^h (ufhe_sl_add_integer, test_int_sl_add: test/tests.c:97-116): every row carries its own pair of shifts, one call takes one pair -- the rows of a
+   * pair go through one call, signed (a's four digits, then the sign) and unsigned (exact) into 32 bits */
+  for (int g = 0; g < 4; g++)
+    for (int h = 0; h < 4; h++) {
+      TLWE *pa[MAXROWS], *pb[MAXROWS], *pc[MAXROWS];
+      int row[MAXROWS], cnt = 0;
+      for (int m = 0; m < M; m++)
+        if (sl_g[m] == g && sl_h[m] == h) { pa[cnt] = xa[m]; pb[cnt] = xb[m]; pc[cnt] = xw[m]; row[cnt++] = m; }
+      if (!cnt) continue;
+      mosfhet_vec_sl_add_integers(v, pc, DC, pa, D, g, pb, D, h, true, cnt);
+      for (int i = 0; i < cnt; i++)
+        CHECK((long)(int32_t)(uint32_t)decrypt(pc[i], DC) == r_sl_s[row[i]], "signed shifted addition row %d (g = %d, h = %d): %ld, reference %ld", row[i], g, h,
+              (long)(int32_t)(uint32_t)decrypt(pc[i], DC), r_sl_s[row[i]]);
+      mosfhet_vec_sl_add_integers(v, pc, DC, pa, D, g, pb, D, h, false, cnt);
+      for (int i = 0; i < cnt; i++)
+        CHECK((long)(uint32_t)decrypt(pc[i], DC) == r_sl_u[row[i]], "unsigned shifted addition row %d (g = %d, h = %d): %ld, reference %ld", row[i], g, h,
+              (long)(uint32_t)decrypt(pc[i], DC), r_sl_u[row[i]]);
+    }
+  printf("sl_add ok\n");
   mosfhet_vec_free(v);
   printf("%d failures over %d rows\n", failures, M);
   return failures ? 1 : 0;
