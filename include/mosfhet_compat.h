@@ -358,6 +358,15 @@ void mosfhet_trlwe_linear(TRLWE *out /*[count * rows_out]*/, TRLWE *in /*[count 
 /* ... followed by trlwe_extract_tlwe(., idx) (src/trlwe.c:540-552; new; mosfhet_hip_trlwe_linear_extract_batch): out[b rows_out + j] of dimension N. */
 void mosfhet_trlwe_linear_extract(TLWE *out /*[count * rows_out]*/, TRLWE *in /*[count * rows_in]*/, const int64_t *W, const Torus *bias /* or NULL */, int rows_out,
                                   int rows_in, int count, int idx);
+/* The same layer with ENCRYPTED weights (new; mosfhet_hip_trlwe_gsw_linear_batch): W [rows_out * rows_in] TRGSW samples of one gadget, W[j rows_in + i] the weight of
+ * input i in output j; out[b rows_out + j] = (0, bias[j]) + sum_i W[j rows_in + i] x in[b rows_in + i], the external products of trgsw_mul_trlwe_DFT
+ * (src/trgsw.c:385-423) summed in the DFT domain and rounded once per row.  With rows_in = 1 and no bias: trgsw_to_DFT, trgsw_mul_trlwe_DFT and trlwe_from_DFT word for
+ * word.  k = 1, N = 1024, 2048 or 4096, l <= 6.  One upload, one call, one download; synchronous; aborts on error; primary device. */
+void mosfhet_trlwe_gsw_linear(TRLWE *out /*[count * rows_out]*/, TRLWE *in /*[count * rows_in]*/, TRGSW *W /*[rows_out * rows_in]*/, const Torus *bias /* or NULL */,
+                              int rows_out, int rows_in, int count);
+/* ... followed by trlwe_extract_tlwe(., idx) (new; mosfhet_hip_trlwe_gsw_linear_extract_batch): out[b rows_out + j] of dimension N. */
+void mosfhet_trlwe_gsw_linear_extract(TLWE *out /*[count * rows_out]*/, TRLWE *in /*[count * rows_in]*/, TRGSW *W /*[rows_out * rows_in]*/, const Torus *bias /* or NULL */,
+                                      int rows_out, int rows_in, int count, int idx);
 /* The weight polynomial of an inner product over `per` packed values (new; pure host integer code): poly[0] = w[0], poly[N - c stride] = -w[c] for 1 <= c < per, zero
  * elsewhere, so that coefficient 0 of the negacyclic product with a sample that holds value x[c] at coefficient c stride is sum_c w[c] x[c].  stride = 1 suits the
  * outputs of mosfhet_tlwe_pack; stride = N / 2^L suits those of mosfhet_tlwe_trace_pack_many with log_per = L, whose phases carry the trace's factor N (the sum is then

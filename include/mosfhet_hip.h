@@ -536,6 +536,60 @@ int mosfhet_hip_trlwe_linear_keyswitch_functional_bootstrap_batch(mosfhet_hip_ct
  * rounded up) } */
 int mosfhet_hip_trlwe_linear_plan(int N, int rows_out, int rows_in, long long nnz, int count, int extract, int cus, long long workspace_bytes, long long plan[8]);
 
+/* ---- ENCRYPTED polynomial-weight linear layers on batches of PACKED TRLWE samples (capi_gswlinear.inc; kernels: gsw_digits_body, gsw_sum_body, trace_kernels.h) ----
+ * The layer above with the operands' roles exchanged: every weight is a TRGSW sample (private-model inference; encrypted filters, rotations and selections of packed
+ * slots; products with the selectors mosfhet_hip_trgsw_from_gadget_batch and mosfhet_hip_circuit_bootstrap_3_dft_batch leave on the device), and a row of the layer
+ * is a SUM of the reference's trgsw_mul_trlwe_DFT (src/trgsw.c:385-423) with one rounding.  Ring N in {1024, 2048, 4096}, k = 1, gadget (l, Bg_bit) given at creation.
+ * A handle holds, per output row j, an ordered list of entries (col_e, W_e) -- W_e a TRGSW_DFT sample [2l][2][N/2] complex in the engine's slot order, rows 0 .. l - 1
+ * multiplying the digits of component a and rows l .. 2l - 1 those of component b, the row order of trgsw_mul_trlwe_DFT -- and an optional bias polynomial of N torus
+ * words.  With F = polynomial_torus_to_DFT, G = polynomial_DFT_to_torus with the general rounding, dec_i = polynomial_decompose_i and mul_addto =
+ * polynomial_mul_addto_DFT (two FMAs per part, digit first, row second):
+ *     acc_a = acc_b = +0.0
+ *     for e in the entries of row j, in the stored order:   for c in (a, b):   for i in 0 .. l - 1:
+ *         d = F(dec_i(in[b][col_e].c, Bg_bit, l, i));   acc_a = mul_addto(acc_a, d, W_e[c l + i].a);   acc_b = mul_addto(acc_b, d, W_e[c l + i].b)
+ *     out[b][j] = (G(acc_a), G(acc_b) + bias[j])           (mod 2^64)
+ * With one entry and no bias that is trgsw_mul_trlwe_DFT followed by trlwe_from_DFT, word for word (mosfhet_hip_external_product_batch at MOSFHET_HIP_ORDER_REFERENCE).
+ * No word depends on count, a sample's position in the batch, the workspace, the rounds, the device, the launch geometry or on whether the handle was made dense, sparse
+ * or from selectors with the same ordered entries.
+ * The gadget: 1 <= l <= 6, 1 <= Bg_bit <= 31 and l * Bg_bit <= 63, else MOSFHET_HIP_EINVAL -- the range on which the digit rule of the kernels is exact: a digit is the
+ * 32-bit field (uint32_t)(word >> (64 - (i + 1) Bg_bit)) & (2^Bg_bit - 1) of the word plus the gadget offset, re-centred by 2^(Bg_bit - 1) as an int, and the offset's
+ * rounding term is 2^(63 - l Bg_bit). */
+typedef struct mosfhet_hip_gswlinear *mosfhet_hip_gswlinear_t;
+/* a dense layer: h_W [rows_out][rows_in][2l][2][N] torus words (TRGSW samples as trgsw_sample writes them), h_bias [rows_out][N] or NULL; row j's entries are col =
+ * 0 .. rows_in - 1 ascending.  The rows are transformed on the device at creation exactly as mosfhet_hip_torus_to_dft_batch transforms them. */
+int mosfhet_hip_gswlinear_create_dense(mosfhet_hip_ctx_t ctx, mosfhet_hip_gswlinear_t *out, const uint64_t *h_W, const uint64_t *h_bias, int rows_out, int rows_in, int N,
+                                       int l, int Bg_bit);
+/* a sparse map: CSR over TRGSW blocks, h_row_ptr [rows_out+1] (row_ptr[0] = 0, monotone), h_col [nnz], h_W [nnz][2l][2][N]; the rules of
+ * mosfhet_hip_polylinear_create_sparse: columns may be unsorted and may repeat within a row (they add, in the stored order), rows may be empty ((0, bias)), columns outside
+ * [0, rows_in) are refused */
+int mosfhet_hip_gswlinear_create_sparse(mosfhet_hip_ctx_t ctx, mosfhet_hip_gswlinear_t *out, const int *h_row_ptr, const int *h_col, const uint64_t *h_W,
+                                        const uint64_t *h_bias, int rows_out, int rows_in, int N, int l, int Bg_bit);
+/* the same map over weights that are already on the device: d_sel_dft [nnz][2l][2][N/2] complex as mosfhet_hip_trgsw_from_gadget_batch,
+ * mosfhet_hip_circuit_bootstrap_3_dft_batch or mosfhet_hip_torus_to_dft_batch wrote them; they are copied into the handle's own image (synchronises the device's null
+ * stream: work that writes the selectors on another stream must have finished) */
+int mosfhet_hip_gswlinear_create_from_selectors(mosfhet_hip_ctx_t ctx, mosfhet_hip_gswlinear_t *out, const double *d_sel_dft, const int *h_row_ptr, const int *h_col,
+                                                const uint64_t *h_bias, int rows_out, int rows_in, int N, int l, int Bg_bit);
+int mosfhet_hip_gswlinear_destroy(mosfhet_hip_gswlinear_t lin);
+/* info: rows_out, rows_in, nnz (-1 dense), N, l, Bg_bit, device bytes, form (0 dense, 1 sparse, 2 from selectors) */
+int mosfhet_hip_gswlinear_info(mosfhet_hip_gswlinear_t lin, long long info[8]);
+/* a copy for another context (device), after the pattern of mosfhet_hip_polylinear_clone */
+int mosfhet_hip_gswlinear_clone(mosfhet_hip_ctx_t ctx_other, mosfhet_hip_gswlinear_t lin, mosfhet_hip_gswlinear_t *out);
+/* d_in [count][rows_in][2][N] -> d_out [count][rows_out][2][N].  Asynchronous on `stream`, never synchronises; the digit transforms of a round ([rows_in][2l][N/2]
+ * complex per batch element: made once, read by all rows_out teams) live in the calling thread's pool (one stream per host thread; capturable once a call of the same
+ * size has run), bounded by mosfhet_hip_set_tlwe_pack_workspace: a larger batch runs in rounds of whole batch elements.  count == 0 is OK.  MOSFHET_HIP_EINVAL, before any
+ * HIP call: null ctx / lin, count < 0, null buffers with count > 0, lin of another context, d_out overlapping d_in, a round whose teams do not fit one launch, a workspace
+ * bound below one batch element. */
+int mosfhet_hip_trlwe_gsw_linear_batch(mosfhet_hip_ctx_t ctx, mosfhet_hip_gswlinear_t lin, uint64_t *d_out /*[count][rows_out][2][N]*/,
+                                       const uint64_t *d_in /*[count][rows_in][2][N]*/, int count, void *stream);
+/* The same words followed by trlwe_extract_tlwe(., idx) (src/trlwe.c:540-552), 0 <= idx < N (else MOSFHET_HIP_EINVAL).  The TRLWE result is never written; d_out is the
+ * [..][N+1] layout mosfhet_hip_keyswitch_functional_bootstrap_batch takes next on the same stream. */
+int mosfhet_hip_trlwe_gsw_linear_extract_batch(mosfhet_hip_ctx_t ctx, mosfhet_hip_gswlinear_t lin, uint64_t *d_out /*[count][rows_out][N+1]*/, const uint64_t *d_in, int idx,
+                                               int count, void *stream);
+/* What a call will do (pure; no device; the function the launcher decides with).  nnz = -1: dense.  `cus` is reserved (checked >= 1).  workspace_bytes = 0: the current
+ * setting.  plan = { teams of the main launch of a round, batch elements per round, rounds, pool bytes per round, forward transforms per call = count * rows_in * 2l,
+ * inverse transforms per call = count * rows_out * 2, weight bytes one team reads, digit bytes one team reads (sparse: of the mean row, rounded up) } */
+int mosfhet_hip_trlwe_gsw_linear_plan(int N, int l, int rows_out, int rows_in, long long nnz, int count, int extract, int cus, long long workspace_bytes, long long plan[8]);
+
 /* ---- batches of LWE samples packed into TRLWE samples: trlwe_full_packing_keyswitch over a batch (src/keyswitch.c:195-227) ----
  * pk: an FFT key-switch key set with entries = n_in (mosfhet_hip_trlwe_ksk_create / _generate; entry i switches from the constant polynomial s_in[i] -- the key
  * trlwe_new_full_packing_KS_key makes), any t and base_bit, N in {1024, 2048, 4096}.

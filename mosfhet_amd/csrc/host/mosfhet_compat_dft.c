@@ -691,6 +691,60 @@ void mosfhet_trlwe_linear_extract(TLWE *out, TRLWE *in, const int64_t *W, const 
   trlwe_linear("mosfhet_trlwe_linear_extract", NULL, out, in, W, bias, rows_out, rows_in, count, idx);
 }
 
+/* y = W x + bias with ENCRYPTED polynomial weights (TRGSW samples, W[j rows_in + i]) on `count` independent packed inputs (mosfhet_hip_trlwe_gsw_linear_batch /
+ * _extract_batch: a sum of trgsw_mul_trlwe_DFT, src/trgsw.c:385-423, with one rounding per row): idx < 0: out_trlwe[b rows_out + j]; else out_tlwe[b rows_out + j] =
+ * trlwe_extract_tlwe(., idx).  One upload, one call, one download. */
+static void trlwe_gsw_linear(const char *name, TRLWE *out_trlwe, TLWE *out_tlwe, TRLWE *in, TRGSW *W, const Torus *bias, int rows_out, int rows_in, int count, int idx) {
+  const int N = in[0]->b->N, l = W[0]->l, Bg_bit = W[0]->Bg_bit, rows = 2 * l;
+  const size_t ins = (size_t)count * (size_t)rows_in, outs = (size_t)count * (size_t)rows_out, one = idx < 0 ? (size_t)2 * N : (size_t)N + 1;
+  const size_t in_w = ins * 2 * (size_t)N, out_w = outs * one, entries = (size_t)rows_out * (size_t)rows_in, esz = (size_t)rows * 2 * (size_t)N;
+  Torus *h = (Torus *)mc_hstage_alloc(sizeof(Torus) * (in_w > out_w ? in_w : out_w)), *d = (Torus *)mc_stage_alloc(sizeof(Torus) * (in_w + out_w));
+  Torus *w = (Torus *)mc_xmalloc(sizeof(Torus) * entries * esz);
+  for (size_t e = 0; e < entries; e++) {
+    need_of(W[e]->l == l && W[e]->Bg_bit == Bg_bit, name, "a weight has another gadget than the first weight");
+    for (int r = 0; r < rows; r++) {
+      need_of(W[e]->samples[r]->k == 1 && W[e]->samples[r]->b->N == N, name, "a weight is not a k = 1 TRGSW sample of the inputs' ring");
+      mc_trlwe_to_flat(w + e * esz + (size_t)r * 2 * (size_t)N, W[e]->samples[r]);
+    }
+  }
+  for (size_t o = 0; o < ins; o++) {
+    need_of(in[o]->k == 1 && in[o]->b->N == N, name, "an input is not a k = 1 TRLWE sample of the first input's ring");
+    mc_trlwe_to_flat(h + o * 2 * (size_t)N, in[o]);
+  }
+  mc_dev_copy(d, h, sizeof(Torus) * in_w, HIP_H2D);
+  mosfhet_hip_gswlinear_t lin = NULL;
+  check_rc(mosfhet_hip_gswlinear_create_dense(ectx(), &lin, w, bias, rows_out, rows_in, N, l, Bg_bit), name);
+  free(w);
+  if (idx < 0)
+    check_rc(mosfhet_hip_trlwe_gsw_linear_batch(ectx(), lin, d + in_w, d, count, NULL), name);
+  else
+    check_rc(mosfhet_hip_trlwe_gsw_linear_extract_batch(ectx(), lin, d + in_w, d, idx, count, NULL), name);
+  mc_dev_copy(h, d + in_w, sizeof(Torus) * out_w, HIP_D2H);   /* (synchronous: the handle is idle when it is destroyed) */
+  mosfhet_hip_gswlinear_destroy(lin);
+  for (size_t o = 0; o < outs; o++) {
+    const Torus *r = h + o * one;
+    if (idx < 0) {
+      need_of(out_trlwe[o]->k == 1 && out_trlwe[o]->b->N == N, name, "an output is not a k = 1 TRLWE sample of the inputs' ring");
+      mc_trlwe_from_flat(out_trlwe[o], r);
+    } else {
+      need_of(out_tlwe[o]->n == N, name, "an output sample has the wrong dimension (N)");
+      memcpy(out_tlwe[o]->a, r, sizeof(Torus) * (size_t)N);
+      out_tlwe[o]->b = r[N];
+    }
+  }
+  mc_hstage_free(h);
+}
+
+void mosfhet_trlwe_gsw_linear(TRLWE *out, TRLWE *in, TRGSW *W, const Torus *bias, int rows_out, int rows_in, int count) {
+  need(out && in && W && rows_out >= 1 && rows_in >= 1 && count >= 1, "mosfhet_trlwe_gsw_linear: bad argument");
+  trlwe_gsw_linear("mosfhet_trlwe_gsw_linear", out, NULL, in, W, bias, rows_out, rows_in, count, -1);
+}
+
+void mosfhet_trlwe_gsw_linear_extract(TLWE *out, TRLWE *in, TRGSW *W, const Torus *bias, int rows_out, int rows_in, int count, int idx) {
+  need(out && in && W && rows_out >= 1 && rows_in >= 1 && count >= 1 && idx >= 0, "mosfhet_trlwe_gsw_linear_extract: bad argument");
+  trlwe_gsw_linear("mosfhet_trlwe_gsw_linear_extract", NULL, out, in, W, bias, rows_out, rows_in, count, idx);
+}
+
 /* pure host integer code: X^(N - c stride) * X^(c stride) = X^N = -1, so the entry at N - c stride is negated */
 int mosfhet_polylinear_dot_layout(int64_t *poly, const int64_t *w, int per, int N, int stride) {
   if (!poly || !w || per < 1 || stride < 1 || N < 1 || (N & (N - 1)) || (long long)per * stride > N) return -1;

@@ -36,6 +36,15 @@
 //                                  own: the only barriers are the inverse transforms'.  It lives here because this kernel already holds what it needs -- row
 //                                  multiply-accumulate from global memory, the two inverse transforms, the general rounding -- and its register need (two
 //                                  accumulator pairs and three operands) is below the other kinds': the kernel's allocation does not move.
+//   gsw_digits_body<F>,          kinds 5 and 6 (mosfhet_hip_trlwe_gsw_linear_batch / _extract_batch; sums of trgsw_mul_trlwe_DFT, src/trgsw.c:385-423, with ONE rounding, then
+//   gsw_sum_body<F>                trlwe_from_DFT / trlwe_extract_tlwe): the layer of kind 4 with the operands' roles exchanged -- the weights are TRGSW_DFT samples
+//                                  [2l][2][M], the input is decomposed.  Kind 5, one team per (batch element, input sample): the 2N words plus the gadget offset,
+//                                  then per component and level the digit polynomial formed as ks_rows_rt forms it, fft.forward, and the M complex values stored 16
+//                                  bytes per lane into the pool [b][rows_in][2l][M] -- every digit transform is made once and read by all rows_out teams.  Kind 6, one
+//                                  team per (batch element, output row): per entry and row r < 2l the digit transform and the two halves of weight row r, 16 bytes
+//                                  per lane, two cmacs per point (digit first, row second) into the accumulator pair; then polylinear_finish, the tail kind 4 runs.
+//                                  Registers: kind 5 holds one component's digit words and one transform, kind 6 two accumulator pairs and three operand rows --
+//                                  what kind 4 holds.
 // Launch bound 1 like trlwe_fft_keyswitch_kernel: digit words, accumulator and the two product pairs are live together.
 #pragma once
 #include <stdint.h>
@@ -45,7 +54,8 @@
 
 namespace mosfhet {
 
-enum { TRACE_KIND_PACK = 0, TRACE_KIND_PRIV = 1, TRACE_KIND_GADGET = 2, TRACE_KIND_MANY = 3, TRACE_KIND_POLYLINEAR = 4 };
+enum { TRACE_KIND_PACK = 0, TRACE_KIND_PRIV = 1, TRACE_KIND_GADGET = 2, TRACE_KIND_MANY = 3, TRACE_KIND_POLYLINEAR = 4, TRACE_KIND_GSW_DIGITS = 5,
+       TRACE_KIND_GSW_SUM = 6 };
 
 struct TraceParams {
   const d2 *__restrict__ key;   // the first entry the call uses: [log2 N or 2][t][2][M] complex
@@ -63,6 +73,8 @@ struct TraceParams {
   const int *__restrict__ col;       // [entries]
   const uint64_t *__restrict__ bias; // [rows_out][N] or null
   int rows_out, rows_in, idx;        // idx < 0: the TRLWE sample; else trlwe_extract_tlwe(., idx)
+  // kind 5: in = the inputs of the round [count][rows_in][2][N], sel = the pool [count][rows_in][2l][M] complex, (l, base_bit) = the gadget
+  // kind 6: key = the weights [entries][2l][2][M] complex, xin = the pool, l; row_ptr, col, bias, rows_out, rows_in, idx, out as kind 4
 };
 
 // One step on the accumulator (a in al / ah, b in acc1):  acc += KeySwitch_entry(v(X^gen)).  The permutation of ga_eval_automorphism (scatter through LDS, signs by bit N
@@ -280,31 +292,18 @@ __device__ __forceinline__ void rlwe_priv_keyswitch_body(d2 *xch, const F &fft, 
   }
 }
 
-// out[b][j] = G(sum_e F(in[b][col_e]) (.) F(val_e)) + (0, bias[j]), the sum in the stored order of row j's entries from +0.0; blockIdx.x = b rows_out + j
+// An entry of a layer handle's lists (row_ptr, col) through the constant address space: the handle's image is not written while a kernel runs, so the word is a
+// scalar load whatever else the kernel's other kinds store -- as a vector load the column costs the entry loop a vmcnt wait of its own in front of its operand loads.
+__device__ __forceinline__ int list_word(const int *list, int i) {
+  typedef const int __attribute__((address_space(4))) *const_ints_t;
+  return ((const_ints_t)list)[i];
+}
+
+// The tail of a linear layer on packed samples, defined once for kinds 4 and 6: the accumulator pair of team blockIdx.x = b rows_out + j through two inverse transforms
+// and the general rounding, the bias on component b, and either the TRLWE sample or trlwe_extract_tlwe(., idx) written straight from the registers.
 template <class F>
-__device__ __forceinline__ void polylinear_body(d2 *xch, const F &fft, const TraceParams &p, int tid) {
+__device__ __forceinline__ void polylinear_finish(double (&o_re)[2][8], double (&o_im)[2][8], d2 *xch, const F &fft, const TraceParams &p, unsigned j, int tid) {
   constexpr int N = F::N, M = F::M, T = F::THREADS;
-  const unsigned b = blockIdx.x / (unsigned)p.rows_out, j = blockIdx.x % (unsigned)p.rows_out;
-  const d2 *__restrict__ x = p.xin + (size_t)b * p.rows_in * (2 * M);
-  double o_re[2][8], o_im[2][8];
-#pragma unroll
-  for (int cc = 0; cc < 2; cc++)
-#pragma unroll
-    for (int m = 0; m < 8; m++) { o_re[cc][m] = 0.0; o_im[cc][m] = 0.0; }
-  const int end = p.row_ptr[j + 1];
-#pragma unroll 1
-  for (int e = p.row_ptr[j]; e < end; e++) {
-    const d2 *__restrict__ w = p.key + (size_t)e * M;
-    const d2 *__restrict__ xa = x + (size_t)p.col[e] * (2 * M);
-    d2 wv[8], a[8], bb[8];
-#pragma unroll
-    for (int m = 0; m < 8; m++) { wv[m] = w[m * T + tid]; a[m] = xa[m * T + tid]; bb[m] = xa[M + m * T + tid]; }
-#pragma unroll
-    for (int m = 0; m < 8; m++) {
-      cmac(o_re[0][m], o_im[0][m], a[m].x, a[m].y, wv[m]);
-      cmac(o_re[1][m], o_im[1][m], bb[m].x, bb[m].y, wv[m]);
-    }
-  }
   const RoundCtx scale = round_scale<M>();
   const uint64_t *bias = p.bias ? p.bias + (size_t)j * N : nullptr;
   const int idx = p.idx;
@@ -338,6 +337,102 @@ __device__ __forceinline__ void polylinear_body(d2 *xch, const F &fft, const Tra
   }
 }
 
+// out[b][j] = G(sum_e F(in[b][col_e]) (.) F(val_e)) + (0, bias[j]), the sum in the stored order of row j's entries from +0.0; blockIdx.x = b rows_out + j
+template <class F>
+__device__ __forceinline__ void polylinear_body(d2 *xch, const F &fft, const TraceParams &p, int tid) {
+  constexpr int M = F::M, T = F::THREADS;
+  const unsigned b = blockIdx.x / (unsigned)p.rows_out, j = blockIdx.x % (unsigned)p.rows_out;
+  const d2 *__restrict__ x = p.xin + (size_t)b * p.rows_in * (2 * M);
+  double o_re[2][8], o_im[2][8];
+#pragma unroll
+  for (int cc = 0; cc < 2; cc++)
+#pragma unroll
+    for (int m = 0; m < 8; m++) { o_re[cc][m] = 0.0; o_im[cc][m] = 0.0; }
+  const int end = list_word(p.row_ptr, j + 1);
+#pragma unroll 1
+  for (int e = list_word(p.row_ptr, j); e < end; e++) {
+    const d2 *__restrict__ w = p.key + (size_t)e * M;
+    const d2 *__restrict__ xa = x + (size_t)list_word(p.col, e) * (2 * M);
+    d2 wv[8], a[8], bb[8];
+#pragma unroll
+    for (int m = 0; m < 8; m++) { wv[m] = w[m * T + tid]; a[m] = xa[m * T + tid]; bb[m] = xa[M + m * T + tid]; }
+#pragma unroll
+    for (int m = 0; m < 8; m++) {
+      cmac(o_re[0][m], o_im[0][m], a[m].x, a[m].y, wv[m]);
+      cmac(o_re[1][m], o_im[1][m], bb[m].x, bb[m].y, wv[m]);
+    }
+  }
+  polylinear_finish<F>(o_re, o_im, xch, fft, p, j, tid);
+}
+
+// kind 5: pool[blockIdx.x][c l + i] = F(dec_i(in[blockIdx.x].c)), blockIdx.x = b rows_in + input; the digit is ks_rows_rt's: an unsigned field of the word plus
+// GADGET_OFFSET, re-centred
+template <class F>
+__device__ __forceinline__ void gsw_digits_body(d2 *xch, const F &fft, const TraceParams &p, int tid) {
+  constexpr int N = F::N, M = F::M, T = F::THREADS;
+  const int l = p.l, base_bit = p.base_bit;
+  const uint64_t *c = p.in + (size_t)blockIdx.x * (2 * N);
+  d2 *__restrict__ dst = p.sel + (size_t)blockIdx.x * 2 * l * M;
+  const uint64_t off = GADGET_OFFSET(l, base_bit);
+  const uint32_t mask = (1u << base_bit) - 1;
+  const int half = 1 << (base_bit - 1);
+#pragma unroll 1
+  for (int cc = 0; cc < 2; cc++) {
+    uint64_t dd_lo[8], dd_hi[8];
+#pragma unroll
+    for (int m = 0; m < 8; m++) { dd_lo[m] = c[cc * N + m * T + tid] + off; dd_hi[m] = c[cc * N + M + m * T + tid] + off; }
+#pragma unroll 1
+    for (int i = 0; i < l; i++) {
+      const int shift = 64 - (i + 1) * base_bit;
+      double re[8], im[8];
+#pragma unroll
+      for (int m = 0; m < 8; m++) {
+        re[m] = (double)((int)((uint32_t)(dd_lo[m] >> shift) & mask) - half);
+        im[m] = (double)((int)((uint32_t)(dd_hi[m] >> shift) & mask) - half);
+      }
+      fft.forward(re, im, xch, tid);
+#pragma unroll
+      for (int m = 0; m < 8; m++) dst[m * T + tid] = d2{re[m], im[m]};
+      dst += M;
+    }
+  }
+}
+
+// kind 6: out[b][j] = G(sum_e sum_r pool[b][col_e][r] (.) W_e[r]) + (0, bias[j]), one chain per component over the entries in the stored order and the rows r = 0 .. 2l - 1
+// from +0.0; blockIdx.x = b rows_out + j
+template <class F>
+__device__ __forceinline__ void gsw_sum_body(d2 *xch, const F &fft, const TraceParams &p, int tid) {
+  constexpr int M = F::M, T = F::THREADS;
+  const unsigned b = blockIdx.x / (unsigned)p.rows_out, j = blockIdx.x % (unsigned)p.rows_out;
+  const int rows = 2 * p.l;
+  const d2 *__restrict__ x = p.xin + (size_t)b * p.rows_in * rows * M;
+  double o_re[2][8], o_im[2][8];
+#pragma unroll
+  for (int cc = 0; cc < 2; cc++)
+#pragma unroll
+    for (int m = 0; m < 8; m++) { o_re[cc][m] = 0.0; o_im[cc][m] = 0.0; }
+  const int end = list_word(p.row_ptr, j + 1);
+#pragma unroll 1
+  for (int e = list_word(p.row_ptr, j); e < end; e++) {
+    const d2 *__restrict__ w = p.key + (size_t)e * rows * (2 * M);
+    const d2 *__restrict__ dg = x + (size_t)list_word(p.col, e) * rows * M;
+#pragma unroll 1
+    for (int r = 0; r < rows; r++) {
+      d2 d[8], k0[8], k1[8];
+#pragma unroll
+      for (int m = 0; m < 8; m++) { d[m] = dg[m * T + tid]; k0[m] = w[m * T + tid]; k1[m] = w[M + m * T + tid]; }
+#pragma unroll
+      for (int m = 0; m < 8; m++) {
+        cmac(o_re[0][m], o_im[0][m], d[m].x, d[m].y, k0[m]);
+        cmac(o_re[1][m], o_im[1][m], d[m].x, d[m].y, k1[m]);
+      }
+      dg += M;
+      w += 2 * M;
+    }
+  }
+  polylinear_finish<F>(o_re, o_im, xch, fft, p, j, tid);
+}
+
 template <class F>
 __global__ __launch_bounds__(F::THREADS, 1) void trace_conversions_kernel(TraceParams p) {
   __shared__ __attribute__((aligned(16))) d2 xch[F::XCH_SLOTS];
@@ -347,6 +442,8 @@ __global__ __launch_bounds__(F::THREADS, 1) void trace_conversions_kernel(TraceP
   fft.init(p.tw, tid);
   if (p.kind == TRACE_KIND_PACK || p.kind == TRACE_KIND_MANY) trace_pack_body<F>(xch, acc1, fft, p, tid);
   else if (p.kind == TRACE_KIND_POLYLINEAR) polylinear_body<F>(xch, fft, p, tid);
+  else if (p.kind == TRACE_KIND_GSW_DIGITS) gsw_digits_body<F>(xch, fft, p, tid);
+  else if (p.kind == TRACE_KIND_GSW_SUM) gsw_sum_body<F>(xch, fft, p, tid);
   else rlwe_priv_keyswitch_body<F>(xch, fft, p.key, p.key + (size_t)p.t * 2 * F::M, p.in, p.out, p.t, p.base_bit, p.kind == TRACE_KIND_GADGET ? p.sel : nullptr, p.l, tid);
 }
 

@@ -271,6 +271,41 @@ class PolyLinearMap:
     free = close
 
 
+def trlwe_gsw_linear_plan(N, l, rows_out, rows_in, count, nnz=-1, extract=False, cus=256, workspace_bytes=0):
+    """What a trlwe_gsw_linear / trlwe_gsw_linear_extract call will do (no device needed; the launcher's own decision): dict(teams, per_round, rounds, pool_bytes,
+    forwards, inverses, weight_bytes, digit_bytes) -- teams of a round's main launch (one per batch element and output row), batch elements per round of the pool, rounds,
+    pool bytes of a round, forward (count * rows_in * 2l) and inverse (count * rows_out * 2) transforms per call, weight and digit bytes one team reads (sparse: of the
+    mean row).  workspace_bytes = 0: the current set_tlwe_pack_workspace.  include/mosfhet_hip.h: mosfhet_hip_trlwe_gsw_linear_plan."""
+    plan = (C.c_longlong * 8)()
+    _check(lib().mosfhet_hip_trlwe_gsw_linear_plan(int(N), int(l), int(rows_out), int(rows_in), C.c_longlong(int(nnz)), int(count), int(bool(extract)), int(cus),
+                                                   C.c_longlong(int(workspace_bytes)), plan))
+    return dict(teams=int(plan[0]), per_round=int(plan[1]), rounds=int(plan[2]), pool_bytes=int(plan[3]), forwards=int(plan[4]), inverses=int(plan[5]),
+                weight_bytes=int(plan[6]), digit_bytes=int(plan[7]))
+
+
+class GswLinearMap:
+    """The encrypted polynomial weights (TRGSW_DFT samples) of y = W x + bias on packed TRLWE samples, on the device (mosfhet_hip_gswlinear_t): made by
+    Engine.gswlinear_create_dense / _sparse / _from_selectors."""
+
+    def __init__(self, engine, handle):
+        self.engine, self.h = engine, handle
+        i = self.info()
+        self.rows_out, self.rows_in, self.N, self.l, self.Bg_bit = i["rows_out"], i["rows_in"], i["N"], i["l"], i["Bg_bit"]
+
+    def info(self):
+        v = (C.c_longlong * 8)()
+        _check(lib().mosfhet_hip_gswlinear_info(self.h, v))
+        return dict(rows_out=int(v[0]), rows_in=int(v[1]), nnz=int(v[2]), N=int(v[3]), l=int(v[4]), Bg_bit=int(v[5]), nbytes=int(v[6]),
+                    form=("dense", "sparse", "selectors")[v[7]])
+
+    def close(self):
+        if self.h:
+            lib().mosfhet_hip_gswlinear_destroy(self.h)
+            self.h = None
+
+    free = close
+
+
 class LinearMap:
     """The cleartext weights of y = W x + bias on the device (mosfhet_hip_linear_t): made by Engine.linear_dense / Engine.linear_sparse."""
 
@@ -1137,6 +1172,69 @@ class Engine:
             out = self.empty(count, lin.rows_out, bsk.k * bsk.N + 1) if extract else self.empty(count, lin.rows_out, bsk.k + 1, bsk.N)
         _check(lib().mosfhet_hip_trlwe_linear_keyswitch_functional_bootstrap_batch(self.h, lin.h, ksk.h, bsk.h, _ptr(out), _ptr(tv), self._tv(tv, bsk, samples), _ptr(ct),
                                                                                    int(idx), count, torus_base, int(extract), self._stream()))
+        return out
+
+    # ---- encrypted polynomial-weight linear layers on packed TRLWE samples (include/mosfhet_hip.h: mosfhet_hip_gswlinear_*, mosfhet_hip_trlwe_gsw_linear_batch) ----
+    def gswlinear_create_dense(self, W, Bg_bit, bias=None):
+        """Handle of a dense layer: W [rows_out][rows_in][2l][2][N] torus words (TRGSW samples), bias [rows_out][N] torus words or None."""
+        W = np.ascontiguousarray(np.asarray(W).astype(np.uint64, copy=False))
+        assert W.ndim == 5 and W.shape[3] == 2 and W.shape[2] % 2 == 0
+        keep, pb = self._poly_bias(bias, W.shape[0], W.shape[4])
+        h = C.c_void_p()
+        _check(lib().mosfhet_hip_gswlinear_create_dense(self.h, C.byref(h), W.ctypes.data_as(C.c_void_p), pb, int(W.shape[0]), int(W.shape[1]), int(W.shape[4]),
+                                                        int(W.shape[2] // 2), int(Bg_bit)))
+        return GswLinearMap(self, h)
+
+    def gswlinear_create_sparse(self, row_ptr, col, W, rows_in, N, l, Bg_bit, bias=None):
+        """Handle of a sparse map in CSR over TRGSW blocks: row_ptr [rows_out + 1], col [nnz], W [nnz][2l][2][N] torus words (columns may be unsorted or repeat
+        within a row -- they add in the stored order; rows may be empty)."""
+        row_ptr = np.ascontiguousarray(row_ptr, dtype=np.int32)
+        col = np.ascontiguousarray(col, dtype=np.int32)
+        W = np.ascontiguousarray(np.asarray(W).astype(np.uint64, copy=False)).reshape(-1, 2 * int(l), 2, int(N))
+        rows_out = len(row_ptr) - 1
+        assert len(col) == len(W) and (rows_out < 0 or len(col) >= row_ptr[-1])
+        keep, pb = self._poly_bias(bias, rows_out, int(N))
+        h = C.c_void_p()
+        _check(lib().mosfhet_hip_gswlinear_create_sparse(self.h, C.byref(h), row_ptr.ctypes.data_as(C.c_void_p), col.ctypes.data_as(C.c_void_p),
+                                                         W.ctypes.data_as(C.c_void_p), pb, int(rows_out), int(rows_in), int(N), int(l), int(Bg_bit)))
+        return GswLinearMap(self, h)
+
+    def gswlinear_create_from_selectors(self, sel_dft, row_ptr, col, rows_in, Bg_bit, bias=None):
+        """The same map over weights already on the device: sel_dft [nnz][2l][2][N] float64 (TRGSW_DFT samples in the engine's slot order, as trgsw_from_gadget,
+        circuit_bootstrap_3_dft or torus_to_dft wrote them), copied into the handle."""
+        row_ptr, col = np.ascontiguousarray(row_ptr, dtype=np.int32), np.ascontiguousarray(col, dtype=np.int32)
+        nnz, rows, two, N = sel_dft.shape
+        assert two == 2 and rows % 2 == 0 and sel_dft.dtype == self.torch.float64 and sel_dft.is_contiguous()
+        rows_out = len(row_ptr) - 1
+        assert len(col) == nnz and (rows_out < 0 or nnz >= row_ptr[-1])
+        keep, pb = self._poly_bias(bias, rows_out, int(N))
+        h = C.c_void_p()
+        _check(lib().mosfhet_hip_gswlinear_create_from_selectors(self.h, C.byref(h), _ptr(sel_dft) if nnz else None, row_ptr.ctypes.data_as(C.c_void_p),
+                                                                 col.ctypes.data_as(C.c_void_p), pb, int(rows_out), int(rows_in), int(N), int(rows // 2), int(Bg_bit)))
+        return GswLinearMap(self, h)
+
+    def clone_gswlinear(self, lin):
+        """A copy of a GswLinearMap of another engine for this one (mosfhet_hip_gswlinear_clone)."""
+        h = C.c_void_p()
+        _check(lib().mosfhet_hip_gswlinear_clone(self.h, lin.h, C.byref(h)))
+        return GswLinearMap(self, h)
+
+    def trlwe_gsw_linear(self, lin, ct, out=None):
+        """out[b][j] = (0, bias[j]) + sum_e W_e x ct[b][col_e], external products summed in the DFT domain in the stored order and rounded once: ct
+        [count][rows_in][2][N] -> [count][rows_out][2][N]."""
+        count = ct.shape[0]
+        if out is None:
+            out = self.empty(count, lin.rows_out, 2, lin.N)
+        _check(lib().mosfhet_hip_trlwe_gsw_linear_batch(self.h, lin.h, _ptr(out) if count else None, _ptr(ct) if count else None, count, self._stream()))
+        return out
+
+    def trlwe_gsw_linear_extract(self, lin, ct, idx=0, out=None):
+        """trlwe_gsw_linear followed by trlwe_extract_tlwe(., idx), the TRLWE result never written: ct [count][rows_in][2][N] -> [count][rows_out][N + 1]."""
+        count = ct.shape[0]
+        if out is None:
+            out = self.empty(count, lin.rows_out, lin.N + 1)
+        _check(lib().mosfhet_hip_trlwe_gsw_linear_extract_batch(self.h, lin.h, _ptr(out) if count else None, _ptr(ct) if count else None, int(idx), count,
+                                                                self._stream()))
         return out
 
     # ---- LWE batches packed into TRLWE samples (include/mosfhet_hip.h: mosfhet_hip_tlwe_pack_batch) ----
