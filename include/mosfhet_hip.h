@@ -164,12 +164,14 @@ int mosfhet_hip_gak_create(mosfhet_hip_ctx_t ctx, mosfhet_hip_gak_t *out, const 
 int mosfhet_hip_gak_destroy(mosfhet_hip_gak_t gak);
 /* trlwe_eval_automorphism over a batch (src/trlwe.c:775-781 = polynomial_permute, src/polynomial.c:442-450, followed by the
  * FFT-based trlwe_keyswitch, src/keyswitch.c:162-193): d_out[b] = KeySwitch_{ak[(gen-1)/2]}(d_in[b](X^gen)); gen odd, < 2N.
- * With gen = 1 this is trlwe_keyswitch itself (entry 0 switches from s to s). */
+ * With gen = 1 this is trlwe_keyswitch itself (entry 0 switches from s to s).  gak may be any FFT key-switch key set
+ * (mosfhet_hip_trlwe_ksk_create) that HAS that entry: (gen - 1) / 2 >= entries returns MOSFHET_HIP_EINVAL before any HIP call. */
 int mosfhet_hip_trlwe_eval_automorphism_batch(mosfhet_hip_ctx_t ctx, mosfhet_hip_gak_t gak, uint64_t *d_out /*[count][2][N]*/,
                                               const uint64_t *d_in /*[count][2][N]*/, int gen, int count, void *stream);
 /* functional_bootstrap_ga / functional_bootstrap_wo_extract_ga over a batch (src/bootstrap_ga.c:62-76).  bsk must hold
  * BK_i = TRGSW(X^{s_i}) (new_bootstrap_key_ga, :17-20); gak must have t = l and base_bit = Bg_bit (:10).
- * extract != 0: d_out = TLWE [count][N+1]; else the rotated TRLWE [count][2][N]. */
+ * extract != 0: d_out = TLWE [count][N+1]; else the rotated TRLWE [count][2][N].  The generators come from the mask words and
+ * reach 2N - 1, so gak must be the full set: entries < N returns MOSFHET_HIP_EINVAL before any HIP call. */
 int mosfhet_hip_functional_bootstrap_ga_batch(mosfhet_hip_ctx_t ctx, mosfhet_hip_bsk_t bsk, mosfhet_hip_gak_t gak, uint64_t *d_out,
                                               const uint64_t *d_tv, int tv_count, const uint64_t *d_in /*[count][n+1]*/, int count,
                                               int torus_base, int extract, void *stream);
@@ -927,7 +929,8 @@ int mosfhet_hip_external_product_dft_batch(mosfhet_hip_ctx_t ctx, const double *
 /* public_mux (src/bootstrap.c:369-389) with the selector rows in the DFT domain: d_sel_dft [count][l][2][N/2] complex */
 int mosfhet_hip_public_mux_dft_batch(mosfhet_hip_ctx_t ctx, uint64_t *d_out /*[count][2][N]*/, const uint64_t *d_p0 /*[N]*/, const uint64_t *d_p1,
                                      const double *d_sel_dft, int N, int l, int Bg_bit, int count, void *stream);
-/* blind_rotate_ga (src/bootstrap_ga.c:35-60) in place on d_acc [count][2][N]; d_in [count][n+1] (mask words) */
+/* blind_rotate_ga (src/bootstrap_ga.c:35-60) in place on d_acc [count][2][N]; d_in [count][n+1] (mask words).  gak: the full automorphism key set with t = l and
+ * base_bit = Bg_bit; entries < N returns MOSFHET_HIP_EINVAL before any HIP call (the generators reach 2N - 1, entry N - 1). */
 int mosfhet_hip_blind_rotate_ga_batch(mosfhet_hip_ctx_t ctx, mosfhet_hip_bsk_t bsk, mosfhet_hip_gak_t gak, uint64_t *d_acc, const uint64_t *d_in, int count,
                                       void *stream);
 /* polynomial_add_DFT_polynomials / _sub_ / _scale_and_add_ (src/polynomial.c:102-128) and the TRLWE_DFT / TRGSW_DFT sums built on them, over flat

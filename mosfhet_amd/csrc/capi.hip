@@ -1531,7 +1531,8 @@ constexpr bool ga_gadgets(int N, int L, int BG) { return BG == 0 || reference_ga
 
 // bounded = true below is safe for any key, a view over caller-held TRGSW_DFT sums included (blind_rotate_ga in mosfhet_compat_dft.c builds one): the Galois
 // kernels (pbs_ga_kernel, pbs_ga_wide_kernel, pbs_ga_split_kernel) always round with round_mod_2_64, whatever the instantiation
-// (tests/test_gpu_parity.py: test_unbounded_key_views_take_the_reducing_kernels).
+// (tests/test_ga_edges.py: test_extreme_accumulators_and_keys_through_blind_rotate_ga sends sums of 2^84 through each of the three and through mode 1;
+// tests/test_gpu_parity.py: test_unbounded_key_views_take_the_reducing_kernels a key view through pbs_ga_wide_kernel).
 template <class F>
 static int launch_ga_f(int l, int Bg_bit, const GaParams &g, int count, hipStream_t s, int order) {
   // (mode 1, the stand-alone automorphism, has no external product: nothing for the order to govern, and it never took the latency kernels)
@@ -1578,6 +1579,9 @@ extern "C" int mosfhet_hip_trlwe_eval_automorphism_batch(mosfhet_hip_ctx_t ctx, 
                                                          const uint64_t *d_in, int gen, int count, void *stream) {
   if (!ctx || !gak || (count > 0 && !d_out) || (count > 0 && !d_in) || count < 0) return fail(MOSFHET_HIP_EINVAL, "eval_automorphism: bad argument");
   if (gen < 1 || gen >= 2 * gak->N || !(gen & 1)) return fail(MOSFHET_HIP_EINVAL, "eval_automorphism: generator %d must be odd and < 2N", gen);
+  // the kernel reads entry (gen - 1) / 2: a shorter set (trace, packing, private, relinearisation keys share the handle type) has none
+  if ((gen - 1) / 2 >= gak->entries)
+    return fail(MOSFHET_HIP_EINVAL, "eval_automorphism: generator %d needs entry %d of a key set with entries = %d", gen, (gen - 1) / 2, gak->entries);
   if (count == 0) return MOSFHET_HIP_OK;
   HIP_TRY(hipSetDevice(ctx->device));
   GaParams g;
@@ -1605,6 +1609,9 @@ extern "C" int mosfhet_hip_functional_bootstrap_ga_batch(mosfhet_hip_ctx_t ctx, 
   if (bsk->unfolding > 1) return fail(MOSFHET_HIP_EINVAL, "functional_bootstrap_ga: needs a key without unfolding");
   if (gak->N != bsk->N || gak->t != bsk->l || gak->base_bit != bsk->Bg_bit)
     return fail(MOSFHET_HIP_EINVAL, "functional_bootstrap_ga: automorphism keys must use the bootstrap key's N, l, Bg_bit");
+  // the generators come from the mask words and reach 2N - 1: entry N - 1
+  if (gak->entries < gak->N)
+    return fail(MOSFHET_HIP_EINVAL, "functional_bootstrap_ga: needs the full automorphism key set, entries = %d < N = %d", gak->entries, gak->N);
   if (count == 0) return MOSFHET_HIP_OK;
   HIP_TRY(hipSetDevice(ctx->device));
   GaParams g;

@@ -70,6 +70,9 @@ extern "C" int mosfhet_hip_blind_rotate_ga_batch(mosfhet_hip_ctx_t ctx, mosfhet_
   if (bsk->unfolding > 1) return fail(MOSFHET_HIP_EINVAL, "blind_rotate_ga: needs a key without unfolding");
   if (gak->N != bsk->N || gak->t != bsk->l || gak->base_bit != bsk->Bg_bit)
     return fail(MOSFHET_HIP_EINVAL, "blind_rotate_ga: automorphism keys must use the bootstrap key's N, l, Bg_bit");
+  // the generators come from the mask words and reach 2N - 1: entry N - 1
+  if (gak->entries < gak->N)
+    return fail(MOSFHET_HIP_EINVAL, "blind_rotate_ga: needs the full automorphism key set, entries = %d < N = %d", gak->entries, gak->N);
   if (count == 0) return MOSFHET_HIP_OK;
   if (!d_acc || !d_in) return fail(MOSFHET_HIP_EINVAL, "blind_rotate_ga: null buffer");
   HIP_TRY(hipSetDevice(ctx->device));

@@ -248,7 +248,8 @@ void blind_rotate(TRLWE tv, Torus *a, TRGSW_DFT *s, int size) {
   if (owned) hipFree(blk);
 }
 
-/* src/bootstrap_ga.c:35-60.  `ak` must be the automorphism key set of a Bootstrap_GA_Key (entry j <-> generator 2j + 1, one device key set). */
+/* src/bootstrap_ga.c:35-60.  `ak` must be the automorphism key set of a Bootstrap_GA_Key (entry j <-> generator 2j + 1, one device key set).  The header of entry 0
+ * of a SHORTER set (packing, trace, private keys) passes the check below; mosfhet_hip_blind_rotate_ga_batch refuses it (entries < N) and check_rc ends the program. */
 void blind_rotate_ga(TRLWE tv, Torus *a, TRGSW_DFT *s, TRLWE_KS_Key *ak, int size) {
   int l, Bg_bit, N, owned;
   double *blk = key_block(s, size, &l, &Bg_bit, &N, &owned, "blind_rotate_ga: `s` must be TRGSW_DFT samples made by this library (one ring, one gadget)");

@@ -199,6 +199,15 @@ def test_trlwe_keyswitch_automorphism_and_ga_bootstrap(oracle, ref):
         mine = oracle.functional_bootstrap_ga(tv, ct, bk_dft, ak_dft, l, Bg, 4)
         assert oracle.torus_dist(mine, ref.functional_bootstrap_ga(tv, ct, h, 4)).max() < 2.0 ** 42, m
         assert oracle.torus_dist(oracle.tlwe_phase(mine, s), lut[m]) < 2.0 ** 58
+    # the edge rows of tests/test_ga_edges.py (exponents forced to 1, wrapping roundings, generators 1, N - 1, N + 1 and 2N - 1, the last key entry) with this
+    # key's 10 mask words: the same tolerance on the ciphertext
+    from ga_edges_reference import ROW_NAMES, edge_rows, entries_used
+    for torus_base in (4, 1):
+        cts = edge_rows(N, torus_base, n=n)
+        assert {0, N // 2 - 1, N // 2, N - 1} <= entries_used(cts, N)
+        for name, ct in zip(ROW_NAMES, cts):
+            mine = oracle.functional_bootstrap_ga(tv, ct, bk_dft, ak_dft, l, Bg, torus_base)
+            assert oracle.torus_dist(mine, ref.functional_bootstrap_ga(tv, ct, h, torus_base)).max() < 2.0 ** 42, (torus_base, name)
     ref.bk_ga_free(h)
 
 
