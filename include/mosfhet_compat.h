@@ -310,6 +310,14 @@ void mosfhet_eval_LUTs_packed_inputs(TLWE **out /*[count][tables * m]*/, TRGSW_D
 void mosfhet_eval_LUTs_packed_bits(TLWE **out /*[count][tables * m]*/, TLWE **in /*[count][size]*/, int size, TRLWE **LUTs /*[tables][n_luts]*/, int tables, int pack_log,
                                    int count, Bootstrap_Key key, TRLWE_KS_Key *kska, Generic_KS_Key kskb, TLWE_KS_Key ksk_out /* or NULL */);
 
+/* Encrypted memory (new; mosfhet_hip_trlwe_ram_read_batch / mosfhet_hip_trlwe_ram_write_batch): mem[b] is input b's own array of 2^size TRLWE cells, addr[b] an
+ * array of `size` samples as trgsw_alloc_new_DFT_sample_array makes it (bit i of the address at addr[b][i], least significant first), 1 <= size <= 10.
+ * Read: out[b] <- the CMUX tree over mem[b], top address bit first (T[j] = T[j] + addr[size-1-t] (.) (T[j + half] - T[j])): the cell at the address; mem is LEFT
+ * UNCHANGED.  Write: every cell i of mem[b] <- the chain over j = 0 .. size-1 of CMUXes between the cell and val[b] (bit j of i set: v = cell + addr[j] (.) (v - cell),
+ * else v = v + addr[j] (.) (cell - v), from v = val[b]): val[b] at the address, the old cell elsewhere.  Synchronous; aborts on error; primary device; N = 1024 or 2048. */
+void mosfhet_trlwe_ram_read(TRLWE *out /*[count]*/, TRGSW_DFT **addr /*[count][size]*/, int size, TRLWE **mem /*[count][2^size]*/, int count);
+void mosfhet_trlwe_ram_write(TRLWE **mem /*[count][2^size]*/, TRGSW_DFT **addr /*[count][size]*/, int size, TRLWE *val /*[count]*/, int count);
+
 /* A cleartext-weight layer on `count` independent inputs in one call (new; mosfhet_hip_tlwe_linear_batch): out[b][j] = (0, bias[j]) + sum_i W[j][i] in[b][i], the
  * loop of tlwe_scale_addto (src/tlwe.c:143-191) over the rows of W [rows_out][rows_in]; W[j][i] is the multiplier tlwe_scale takes, bias [rows_out] torus words or
  * NULL.  out[b][j] has the inputs' dimension.  Synchronous; aborts on error; primary device. */

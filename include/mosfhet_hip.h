@@ -858,6 +858,34 @@ int mosfhet_hip_lut_bits_packed_batch(mosfhet_hip_ctx_t ctx, mosfhet_hip_bsk_t b
                                       uint64_t *d_out, const uint64_t *d_luts, const uint64_t *d_in, int size, int tables, int pack_log, int count, void *stream);
 int mosfhet_hip_lut_bits_packed_plan(int N, int l, int size, int tables, int pack_log, int count, int cus, long long *plan /*[12]*/);
 
+/* Encrypted memory (the leveled RAM of the TFHE papers): every input b owns cells = 2^size TRLWE samples, read and written at an ENCRYPTED address.
+ *   d_mem      [count][cells][2][N] torus words
+ *   d_sel_dft  [count][size][2l][2][N/2] complex: exactly the layout of mosfhet_hip_leveled_lut_batch; selector j of input b encrypts bit j of b's address,
+ *              least significant first
+ * (.) below is the external product of mosfhet_hip_leveled_lut_batch: one chain over rows 0 .. 2l-1, rounded with the reduction mod 1.
+ * READ: d_out[b] is [2][N]; d_mem is never written.
+ *     T = mem[b];  for t = 0 .. size-1, half = 2^(size-1-t):  T[j] = T[j] + sel[b][size-1-t] (.) (T[j + half] - T[j]) for j < half;  out[b] = T[0]
+ *   The phase of out[b] is that of mem[b][address of b].  `size` launches per chunk of inputs: the first level reads the memory and writes a workspace of
+ *   [chunk][cells / 2][2][N] words, the last writes d_out (size = 1: one launch, no workspace).
+ * WRITE: d_val is [count][2][N]; d_mem is updated in place, every cell i of every input independently:
+ *     v = val[b];  for j = 0 .. size-1:  bit j of i set:  v = mem[b][i] + sel[b][j] (.) (v - mem[b][i]);  else:  v = v + sel[b][j] (.) (mem[b][i] - v);  mem[b][i] = v
+ *   The phase of the cell is that of val[b] where i is b's address and that of the old cell elsewhere, both with the noise of `size` products added.  One launch,
+ *   one workgroup per (input, cell), no workspace.  (Computed as e = v - mem[b][i], which gives the same words: e = sel (.) e, or e = e + sel (.) (-e).)
+ * No word depends on count, on a sample's position in the batch, on the chunking or on the workspace bound.
+ * k = 1, N in {1024, 2048}, 1 <= l <= 6, Bg_bit <= 31, l * Bg_bit < 64, 1 <= size <= MOSFHET_HIP_LUT_MAX_LEVELS, count >= 0 (0: nothing is done); d_out and d_val
+ * must not overlap d_mem as address ranges; a workspace bound (mosfhet_hip_set_leveled_lut_workspace) below one input's intermediates is refused: anything else
+ * MOSFHET_HIP_EINVAL with a message naming the argument, before any HIP call.
+ * Asynchronous on `stream`.  The read's workspace lives in the CALLING THREAD's pool: no allocation and no synchronisation from the second call of a shape on
+ * (capturable from then on) -- and therefore ONE STREAM PER HOST THREAD at a time, as for mosfhet_hip_leveled_lut_batch.  A batch whose intermediates exceed the
+ * bound runs in chunks of whole inputs.
+ * mosfhet_hip_trlwe_ram_plan says what the launchers will do, as a pure function (no GPU; `cus` sizes grids only): plan = {cells, launches, inputs per chunk,
+ * workspace bytes (chunk * cells / 2 * 2N * 8 for a read of size > 1, else 0), external products (read: count * (cells - 1); write: count * cells * size)}. */
+int mosfhet_hip_trlwe_ram_read_batch(mosfhet_hip_ctx_t ctx, uint64_t *d_out /*[count][2][N]*/, const double *d_sel_dft, const uint64_t *d_mem, int size, int N, int l,
+                                     int Bg_bit, int count, void *stream);
+int mosfhet_hip_trlwe_ram_write_batch(mosfhet_hip_ctx_t ctx, uint64_t *d_mem, const double *d_sel_dft, const uint64_t *d_val /*[count][2][N]*/, int size, int N, int l,
+                                      int Bg_bit, int count, void *stream);
+int mosfhet_hip_trlwe_ram_plan(int N, int l, int size, int count, int write, int cus, long long *plan /*[5]*/);
+
 /* Key images for the on-disk formats (save_bootstrap_key / load_new_bootstrap_key src/bootstrap.c:63-104, trlwe_save_KS_key /
  * trlwe_load_new_KS_key src/keyswitch.c:122-160, tlwe_save_KS_key / tlwe_load_new_KS_key src/tlwe.c:247-287, trlwe_save_generic_ks_key /
  * trlwe_load_new_generic_ks_key src/keyswitch.c:409-455).  DFT-domain contents are backend-defined in the reference too (src/polynomial.c:336-357):

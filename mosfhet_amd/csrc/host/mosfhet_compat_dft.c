@@ -433,6 +433,47 @@ void mosfhet_eval_LUTs_packed_bits(TLWE **out, TLWE **in, int size, TRLWE **LUTs
   eval_LUTs_bits("mosfhet_eval_LUTs_packed_bits", out, in, size, LUTs, tables, pack_log, count, key, kska, kskb, ksk_out);
 }
 
+/* Encrypted memory (mosfhet_hip_trlwe_ram_read_batch / _write_batch): mem[b] is input b's array of 2^size host TRLWEs, addr[b] its array of `size` TRGSW_DFT
+ * selectors (address bit i at addr[b][i]), other[b] the output of a read or the value of a write.  One upload, one call, one download. */
+static void trlwe_ram(const char *name, TRLWE *other, TRGSW_DFT **addr, int size, TRLWE **mem, int write, int count) {
+  int l, Bg_bit, N, gathered;
+  double *sel = lut_selectors(addr, size, count, &l, &Bg_bit, &N, &gathered, name);
+  need_of(N == 1024 || N == 2048, name, "ring degree must be 1024 or 2048");
+  need_of(size <= MOSFHET_HIP_LUT_MAX_LEVELS, name, "size must be at most MOSFHET_HIP_LUT_MAX_LEVELS");
+  const size_t cells = (size_t)1 << size, row = 2 * (size_t)N;
+  const size_t mem_w = (size_t)count * cells * row, other_w = (size_t)count * row;
+  Torus *h = (Torus *)mc_hstage_alloc(sizeof(Torus) * (mem_w + other_w)), *d = (Torus *)mc_stage_alloc(sizeof(Torus) * (mem_w + other_w));
+  for (int b = 0; b < count; b++)
+    for (size_t i = 0; i < cells; i++) mc_trlwe_to_flat(h + ((size_t)b * cells + i) * row, mem[b][i]);
+  if (write)
+    for (int b = 0; b < count; b++) mc_trlwe_to_flat(h + mem_w + (size_t)b * row, other[b]);
+  mc_dev_copy(d, h, sizeof(Torus) * (write ? mem_w + other_w : mem_w), HIP_H2D);
+  if (write) {
+    check_rc(mosfhet_hip_trlwe_ram_write_batch(ectx(), d, sel, d + mem_w, size, N, l, Bg_bit, count, NULL), name);
+    mc_dev_copy(h, d, sizeof(Torus) * mem_w, HIP_D2H);
+    for (int b = 0; b < count; b++)
+      for (size_t i = 0; i < cells; i++) mc_trlwe_from_flat(mem[b][i], h + ((size_t)b * cells + i) * row);
+  } else {
+    check_rc(mosfhet_hip_trlwe_ram_read_batch(ectx(), d + mem_w, sel, d, size, N, l, Bg_bit, count, NULL), name);
+    mc_dev_copy(h, d + mem_w, sizeof(Torus) * other_w, HIP_D2H);
+    for (int b = 0; b < count; b++) mc_trlwe_from_flat(other[b], h + (size_t)b * row);
+  }
+  mc_hstage_free(h);
+  if (gathered) hipFree(sel);
+}
+
+/* out[b] <- the cell of mem[b] at the address addr[b] encrypts: the CMUX tree over the 2^size cells, top address bit first.  mem is left unchanged. */
+void mosfhet_trlwe_ram_read(TRLWE *out, TRGSW_DFT **addr, int size, TRLWE **mem, int count) {
+  need(out && addr && mem && size >= 1 && count >= 1, "mosfhet_trlwe_ram_read: bad argument");
+  trlwe_ram("mosfhet_trlwe_ram_read", out, addr, size, mem, 0, count);
+}
+
+/* Every cell i of mem[b] <- the chain of `size` CMUXes between the cell and val[b]: val[b] where i is the address addr[b] encrypts, the old cell elsewhere. */
+void mosfhet_trlwe_ram_write(TRLWE **mem, TRGSW_DFT **addr, int size, TRLWE *val, int count) {
+  need(mem && addr && val && size >= 1 && count >= 1, "mosfhet_trlwe_ram_write: bad argument");
+  trlwe_ram("mosfhet_trlwe_ram_write", val, addr, size, mem, 1, count);
+}
+
 /* y = W x + bias with cleartext weights on `count` independent inputs (mosfhet_hip_tlwe_linear_batch; tlwe_scale_addto of src/tlwe.c:143-191 row by row):
  * in[b][i] input i of instance b, W [rows_out][rows_in], bias [rows_out] or NULL, out[b][j] of the inputs' dimension.  With a bootstrap key: the linear map, then
  * tlwe_keyswitch, then functional_bootstrap (mosfhet_hip_linear_keyswitch_functional_bootstrap_batch), out[b][j] of dimension N. */

@@ -25,6 +25,10 @@
 // is 2^(size + pack_log) / N TRLWEs.  The tree kernels do not know: they take their node count and table stride from the launcher.  The finish -- always
 // lut_tables_finish_kernel, also at one table -- rotates by m 2^i in step i, for log2 N - pack_log steps at most, and extracts the m coefficients 0 .. m-1 of the
 // rotated accumulator; both are run-time arguments (LutParams::pack_log, 0 for every other call, where they reduce to the words above).
+//
+// Memories that belong to the input (mosfhet_hip_trlwe_ram_read_batch / _write_batch, capi_ram.inc): 2^size TRLWE cells per input, the selectors its address bits.
+// Two further run-time modes of lut_cmux_kernel, no kernel of their own: mode 2 is mode 0's tree level from one place to another (memory -> workspace -> output),
+// mode 3 the chain of `size` CMUXes between a cell and the value to write, the difference in LDS across the products as mode 1 keeps its accumulator.
 #pragma once
 #include "bootstrap_kernels.h"
 
@@ -41,6 +45,10 @@ struct LutParams {
   int half0;                         // nodes of tree level 0 (0: no tree)
   int first, inputs;                 // the chunk: inputs first .. first + inputs - 1 of the batch
   int mode, half, sel_index;         // lut_cmux_kernel: mode 0 = the tree level with `half` nodes and selector `sel_index`; mode 1 = finish
+                                     // modes 2 and 3, the per-input memories of capi_ram.inc (no table, no tree of this struct's): the fields mean
+                                     //   mode 2 (a level of a read): lut = the level's source rows, lut_stride = words from one input's rows to the next;
+                                     //          out = its destination rows, half0 = destination rows per input; half, sel_index as in mode 0
+                                     //   mode 3 (a write): lut = the values [count][2][N]; out = the memories [count][2^size][2][N], updated in place
   int steps;                         // mode 1: min(size, log2 N) rotation steps
   // several tables over the same selectors (1 and unused strides for the one-table call)
   int tables;                        // tables of this pass: `lut` and `out` point at the first of them
@@ -134,9 +142,10 @@ __global__ __launch_bounds__(F::THREADS, 2) void lut_level0_kernel(LutParams p) 
 // owns row 2 ph + w (component q = row / l, digit row % l): its digits, its forward transform, the transformed digits handed over through its exchange buffer;
 // then team w multiplies the phase's two rows with ITS output component of the selector -- in row order, the fma chain of cmux_rows starting from zero --
 // and after the last phase runs the inverse transform of that component.  Critical path per product: l forward transforms + 1 inverse instead of 2l + 2.
-// `home` (LDS, [2][N]): rotate -- the accumulator, d = (X^abar - 1) home; else the difference itself.  Leaves the inverse's output (unscaled) in o_re / o_im.
+// `home` (LDS, [2][N]): rotate -- the accumulator, d = (X^abar - 1) home; else the difference itself, or with `negate` its negative (every word 0 - home[j]).
+// Leaves the inverse's output (unscaled) in o_re / o_im.
 template <class F>
-__device__ __forceinline__ void lut_team_product(const uint64_t *home, bool rotate, int a_lo, bool flip, const d2 *__restrict__ sel, int l, int Bg_bit, uint64_t off,
+__device__ __forceinline__ void lut_team_product(const uint64_t *home, bool rotate, bool negate, int a_lo, bool flip, const d2 *__restrict__ sel, int l, int Bg_bit, uint64_t off,
                                                  const F &fft, d2 *xch_all, int team, int t, double (&o_re)[8], double (&o_im)[8]) {
   constexpr int N = F::N, M = F::M, T = F::THREADS;
   d2 *xch = xch_all + (size_t)team * F::XCH_SLOTS;
@@ -158,8 +167,8 @@ __device__ __forceinline__ void lut_team_product(const uint64_t *home, bool rota
 #pragma unroll
     for (int m = 0; m < 8; m++) {
       const int j = m * T + t;
-      const uint64_t d_lo = (rotate ? rot_coeff<N>(hq, j, a_lo, flip) - hq[j] : hq[j]) + off;
-      const uint64_t d_hi = (rotate ? rot_coeff<N>(hq, j + M, a_lo, flip) - hq[j + M] : hq[j + M]) + off;
+      const uint64_t d_lo = (rotate ? rot_coeff<N>(hq, j, a_lo, flip) - hq[j] : negate ? 0 - hq[j] : hq[j]) + off;
+      const uint64_t d_hi = (rotate ? rot_coeff<N>(hq, j + M, a_lo, flip) - hq[j + M] : negate ? 0 - hq[j + M] : hq[j + M]) + off;
       re[m] = (double)((int)((uint32_t)(d_lo >> shift) & mask) - half_bg);
       im[m] = (double)((int)((uint32_t)(d_hi >> shift) & mask) - half_bg);
     }
@@ -187,6 +196,16 @@ __device__ __forceinline__ void lut_team_product(const uint64_t *home, bool rota
 // mode 1: workgroup b finishes input b: acc = T[b][0] (the table's row 0 without a tree), `steps` times acc += sel[b][i] (.) ((X^(2N - 2^i) - 1) acc)
 //         (src/bootstrap.c:107-122 with a[i] = int2torus(2N - 2^i, log2(2N)): never zero, no skipped step), then trlwe_extract_tlwe(acc, 0).
 //         Both accumulator components stay in LDS across the steps.
+// The per-input memories (capi_ram.inc; a memory is [2^size][2][N] words per input, the selectors are its address bits):
+// mode 2: a level of a read, mode 0's step from one place to another: persistent workgroups over the units (b, j), j < half,
+//         dst[b][j] = src[b][j] + sel[b][sel_index] (.) (src[b][j + half] - src[b][j]).  src = dst (a level in place in the workspace) is allowed: a unit reads
+//         rows j and j + half and writes row j, which no other unit of the level reads.
+// mode 3: a write: persistent workgroups over the units (b, cell i).  e = val[b] - cell in the [2][N] LDS words; for bit j of i, from the least significant:
+//         bit 1: e = sel[b][j] (.) e;  bit 0: e = e + sel[b][j] (.) (-e);  then cell += e.  These are the words of the CMUX chain v = val[b]; bit 1:
+//         v = cell + sel (.) (v - cell), bit 0: v = v + sel (.) (cell - v) with e = v - cell throughout (word arithmetic mod 2^64 is exact).  A thread reads its own 16
+//         words of the cell in front of the chain and again behind it, where it stores them: held in registers across the products they are 32 registers on top of
+//         the product's own, which at N = 2048 the 256 of a wavefront do not hold (28 bytes of scratch).  A unit reads and writes its own cell and reads val[b],
+//         which nobody writes.
 template <class F>
 constexpr size_t lut_cmux_lds() { return sizeof(d2) * 2 * F::XCH_SLOTS + sizeof(uint64_t) * 2 * F::N; }
 
@@ -213,7 +232,7 @@ __global__ __launch_bounds__(2 * F::THREADS, 2) void lut_cmux_kernel(LutParams p
       const uint64_t *y = x + (size_t)p.half * 2 * N;
       for (int w = tid; w < 2 * N; w += WG) acc[w] = y[w] - x[w];
       workgroup_sync();
-      lut_team_product(acc, false, 0, false, p.sel + (((size_t)p.first + b) * p.size + (size_t)p.sel_index) * sel_sz, l, Bg_bit, off, fft, xch_all, team, t, o_re, o_im);
+      lut_team_product(acc, false, false, 0, false, p.sel + (((size_t)p.first + b) * p.size + (size_t)p.sel_index) * sel_sz, l, Bg_bit, off, fft, xch_all, team, t, o_re, o_im);
       uint64_t *xc = x + (size_t)team * N;                // this team's output component
 #pragma unroll
       for (int m = 0; m < 8; m++) {
@@ -225,13 +244,69 @@ __global__ __launch_bounds__(2 * F::THREADS, 2) void lut_cmux_kernel(LutParams p
     return;
   }
 
+  if (p.mode == 2) {
+    const size_t units = (size_t)p.inputs * p.half;
+    for (size_t u = blockIdx.x; u < units; u += gridDim.x) {
+      const size_t b = u / (size_t)p.half, j = u % (size_t)p.half;
+      const uint64_t *x = p.lut + b * p.lut_stride + j * 2 * N;
+      const uint64_t *y = x + (size_t)p.half * 2 * N;
+      for (int w = tid; w < 2 * N; w += WG) acc[w] = y[w] - x[w];
+      workgroup_sync();
+      lut_team_product(acc, false, false, 0, false, p.sel + (((size_t)p.first + b) * p.size + (size_t)p.sel_index) * sel_sz, l, Bg_bit, off, fft, xch_all, team, t, o_re, o_im);
+      const uint64_t *xc = x + (size_t)team * N;          // this team's output component
+      uint64_t *dc = p.out + (b * p.half0 + j) * 2 * N + (size_t)team * N;
+#pragma unroll
+      for (int m = 0; m < 8; m++) {
+        dc[m * T + t] = add_rounded<true>(xc[m * T + t], o_re[m], scale);
+        dc[M + m * T + t] = add_rounded<true>(xc[M + m * T + t], o_im[m], scale);
+      }
+      workgroup_sync();
+    }
+    return;
+  }
+
+  if (p.mode == 3) {
+    const size_t units = (size_t)p.inputs << p.size;
+    uint64_t *ec = acc + (size_t)team * N;                // this thread's 16 words of e: [m * T + t] and [M + m * T + t]
+    for (size_t u = blockIdx.x; u < units; u += gridDim.x) {
+      const size_t b = u >> p.size;
+      const unsigned cell_index = (unsigned)(u & (((size_t)1 << p.size) - 1));
+      uint64_t *cc = p.out + u * 2 * N + (size_t)team * N;
+      const uint64_t *vc = p.lut + b * 2 * N + (size_t)team * N;
+#pragma unroll
+      for (int m = 0; m < 8; m++) {
+        ec[m * T + t] = vc[m * T + t] - cc[m * T + t];
+        ec[M + m * T + t] = vc[M + m * T + t] - cc[M + m * T + t];
+      }
+      workgroup_sync();
+      for (int i = 0; i < p.size; i++) {
+        const bool keep = (cell_index >> i) & 1;          // bit 1: e = sel (.) e;  bit 0: e = e + sel (.) (-e)
+        lut_team_product(acc, false, !keep, 0, false, p.sel + (((size_t)p.first + b) * p.size + (size_t)i) * sel_sz, l, Bg_bit, off, fft, xch_all, team, t, o_re, o_im);
+        // (every read of the old e stands in front of the last phase's barriers: the update below is this thread's own 16 words)
+#pragma unroll
+        for (int m = 0; m < 8; m++) {
+          ec[m * T + t] = add_rounded<true>(keep ? 0 : ec[m * T + t], o_re[m], scale);
+          ec[M + m * T + t] = add_rounded<true>(keep ? 0 : ec[M + m * T + t], o_im[m], scale);
+        }
+        workgroup_sync();
+      }
+#pragma unroll
+      for (int m = 0; m < 8; m++) {
+        cc[m * T + t] += ec[m * T + t];
+        cc[M + m * T + t] += ec[M + m * T + t];
+      }
+      // (the next unit's first stores to e are again this thread's own words, read last by this thread)
+    }
+    return;
+  }
+
   const size_t b = blockIdx.x;
   const uint64_t *src = p.half0 ? p.work + b * p.half0 * 2 * N : p.lut;
   for (int w = tid; w < 2 * N; w += WG) acc[w] = src[w];
   workgroup_sync();
   for (int i = 0; i < p.steps; i++) {
     const Rotation step = split_rotation(2 * N - (1 << i), N);
-    lut_team_product(acc, true, step.a_lo, step.flip, p.sel + (((size_t)p.first + b) * p.size + (size_t)i) * sel_sz, l, Bg_bit, off, fft, xch_all, team, t,
+    lut_team_product(acc, true, false, step.a_lo, step.flip, p.sel + (((size_t)p.first + b) * p.size + (size_t)i) * sel_sz, l, Bg_bit, off, fft, xch_all, team, t,
                      o_re, o_im);
     // (every read of the old accumulator stands in front of the last phase's barriers: the update below is this thread's own 16 words)
     uint64_t *ac = acc + (size_t)team * N;
@@ -296,7 +371,7 @@ __global__ __launch_bounds__(2 * F::THREADS, 2) void lut_tables_finish_kernel(Lu
 #pragma unroll 1
     for (int k = 0; k < nt; k++) {
       uint64_t *acc = accs + (size_t)k * 2 * N;
-      lut_team_product(acc, true, step.a_lo, step.flip, sel, l, Bg_bit, off, fft, xch_all, team, t, o_re, o_im);
+      lut_team_product(acc, true, false, step.a_lo, step.flip, sel, l, Bg_bit, off, fft, xch_all, team, t, o_re, o_im);
       // (every read of the old accumulator stands in front of the last phase's barriers: the update below is this thread's own 16 words)
       uint64_t *ac = acc + (size_t)team * N;
 #pragma unroll

@@ -138,6 +138,15 @@ def leveled_lut_packed_plan(N, l, size, tables, pack_log, count, cus=256):
                 steps=int(plan[6]), outputs=int(plan[7]))
 
 
+def trlwe_ram_plan(N, l, size, count, write=False, cus=256):
+    """What a trlwe_ram_read / trlwe_ram_write call will do (no device needed): dict(cells, launches, chunk, workspace_bytes, products) -- cells per input, kernel
+    launches, inputs per chunk, bytes of one chunk's intermediates (0 for a write and for size 1) and external products of the call.
+    include/mosfhet_hip.h: mosfhet_hip_trlwe_ram_plan."""
+    plan = (C.c_longlong * 5)()
+    _check(lib().mosfhet_hip_trlwe_ram_plan(int(N), int(l), int(size), int(count), int(bool(write)), int(cus), plan))
+    return dict(cells=int(plan[0]), launches=int(plan[1]), chunk=int(plan[2]), workspace_bytes=int(plan[3]), products=int(plan[4]))
+
+
 def lut_bits_packed_plan(N, l, size, tables, pack_log, count, cus=256):
     """What a lut_bits_packed call will do (no device needed): lut_bits_plan's dict with leveled_lut_packed_plan's dict for one chunk as `lut`.
     include/mosfhet_hip.h: mosfhet_hip_lut_bits_packed_plan."""
@@ -899,6 +908,33 @@ class Engine:
         _check(lib().mosfhet_hip_leveled_lut_packed_batch(self.h, _ptr(out), _ptr(sel_dft), _ptr(luts), int(size), int(N), int(l), int(Bg_bit), int(tables),
                                                           int(pack_log), int(count), self._stream()))
         return out
+
+    def trlwe_ram_read(self, sel_dft, mem, size, l, Bg_bit, out=None):
+        """Encrypted memory, read: every input b owns mem[b], 2^size TRLWE cells, and out[b] is the cell at the address its selectors encrypt (the CMUX tree over the
+        cells, top address bit first).  sel_dft: [count][size][2l][2][N] doubles as for leveled_lut (bit i of input b's address at [b][i]); mem:
+        [count][2^size][2][N] torus words, read only; returns [count][2][N]."""
+        count, N = mem.shape[0], mem.shape[-1]
+        assert tuple(sel_dft.shape) == (count, size, 2 * l, 2, N) and sel_dft.dtype == self.torch.float64, tuple(sel_dft.shape)
+        assert tuple(mem.shape) == (count, 1 << size, 2, N), tuple(mem.shape)
+        if out is None:
+            out = self.empty(count, 2, N)
+        assert tuple(out.shape) == (count, 2, N)
+        _check(lib().mosfhet_hip_trlwe_ram_read_batch(self.h, _ptr(out), _ptr(sel_dft), _ptr(mem), int(size), int(N), int(l), int(Bg_bit), int(count), self._stream()))
+        return out
+
+    def trlwe_ram_write(self, sel_dft, mem, val, size, l, Bg_bit):
+        """Encrypted memory, write, IN PLACE: cell i of mem[b] becomes the chain of `size` CMUXes between the cell and val[b] -- val[b] where i is the address the
+        selectors of input b encrypt, the old cell elsewhere.  sel_dft and mem as for trlwe_ram_read; val: [count][2][N].  Returns mem."""
+        count, N = mem.shape[0], mem.shape[-1]
+        assert tuple(sel_dft.shape) == (count, size, 2 * l, 2, N) and sel_dft.dtype == self.torch.float64, tuple(sel_dft.shape)
+        assert tuple(mem.shape) == (count, 1 << size, 2, N), tuple(mem.shape)
+        assert tuple(val.shape) == (count, 2, N), tuple(val.shape)
+        _check(lib().mosfhet_hip_trlwe_ram_write_batch(self.h, _ptr(mem), _ptr(sel_dft), _ptr(val), int(size), int(N), int(l), int(Bg_bit), int(count), self._stream()))
+        return mem
+
+    def trlwe_ram_plan(self, N, l, size, count, write=False):
+        """trlwe_ram_plan() at this device's CU count."""
+        return trlwe_ram_plan(N, l, size, count, write, self.torch.cuda.get_device_properties(self.device).multi_processor_count)
 
     def leveled_lut_packed_plan(self, N, l, size, tables, pack_log, count):
         """leveled_lut_packed_plan() at this device's CU count."""
