@@ -318,6 +318,15 @@ void mosfhet_eval_LUTs_packed_bits(TLWE **out /*[count][tables * m]*/, TLWE **in
 void mosfhet_trlwe_ram_read(TRLWE *out /*[count]*/, TRGSW_DFT **addr /*[count][size]*/, int size, TRLWE **mem /*[count][2^size]*/, int count);
 void mosfhet_trlwe_ram_write(TRLWE **mem /*[count][2^size]*/, TRGSW_DFT **addr /*[count][size]*/, int size, TRLWE *val /*[count]*/, int count);
 
+/* Encrypted automata (new; mosfhet_hip_trlwe_automaton_batch): a deterministic weighted automaton / layered branching program of `states` states over words of
+ * `steps` encrypted bits.  word[b] is an array of `steps` samples as trgsw_alloc_new_DFT_sample_array makes it (symbol t at word[b][t]); init[b] the `states` TRLWEs
+ * behind the last symbol (init_shared != 0: init[0] for every input); next0, next1 (in [0, states)) and rot0, rot1 (in [0, 2N)) are int [layers][states], position t
+ * using layer t mod layers.  Backwards from V_steps = init:  V_t[q] = R0 + word[b][t] (.) (R1 - R0),  R0 = X^rot0[q] V_{t+1}[next0[q]],  R1 = X^rot1[q] V_{t+1}[next1[q]].
+ * start < 0: out[b] is an array of `states` TRLWEs <- V_0; else out[b][0] <- V_0[start].  init is LEFT UNCHANGED.  1 <= steps, states, layers <= 4096.
+ * Synchronous; aborts on error; primary device; N = 1024 or 2048. */
+void mosfhet_trlwe_automaton(TRLWE **out /*[count][states or 1]*/, TRGSW_DFT **word /*[count][steps]*/, int steps, TRLWE **init /*[count or 1][states]*/, int init_shared,
+                             const int *next0, const int *next1, const int *rot0, const int *rot1, int states, int layers, int start, int count);
+
 /* A cleartext-weight layer on `count` independent inputs in one call (new; mosfhet_hip_tlwe_linear_batch): out[b][j] = (0, bias[j]) + sum_i W[j][i] in[b][i], the
  * loop of tlwe_scale_addto (src/tlwe.c:143-191) over the rows of W [rows_out][rows_in]; W[j][i] is the multiplier tlwe_scale takes, bias [rows_out] torus words or
  * NULL.  out[b][j] has the inputs' dimension.  Synchronous; aborts on error; primary device. */

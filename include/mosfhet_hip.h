@@ -886,6 +886,45 @@ int mosfhet_hip_trlwe_ram_write_batch(mosfhet_hip_ctx_t ctx, uint64_t *d_mem, co
                                       int Bg_bit, int count, void *stream);
 int mosfhet_hip_trlwe_ram_plan(int N, int l, int size, int count, int write, int cus, long long *plan /*[5]*/);
 
+/* Encrypted automata: a deterministic weighted finite automaton -- more generally a layered branching program -- run over a word whose symbols are ENCRYPTED bits
+ * (the third leveled primitive of the TFHE papers, next to the look-up table and the memory above).  Cost: `states` CMUXes per symbol.
+ * Ring and gadget: N in {1024, 2048}, k = 1; the gadget is a run-time argument: 1 <= l <= 6, Bg_bit <= 31, l * Bg_bit < 64.
+ * THE AUTOMATON is a handle made from host arrays and shared by the batch: states S in 1 .. MOSFHET_HIP_AUTOMATON_MAX_STATES, layers L in
+ * 1 .. MOSFHET_HIP_AUTOMATON_MAX_STEPS; per layer and state next0, next1 in [0, S) and rot0, rot1 in [0, 2N), each int32 [L][S].  Position t of the word uses
+ * layer t mod L: L = 1 is a time-invariant automaton, L = steps a branching program, anything between is periodic.  Creation checks and packs the tables on the host
+ * (no device is needed); the packed table is copied to a device the first time a call runs there (one allocation, one synchronous copy) and stays for the handle's life.
+ *   d_sel_dft  [count][steps][2l][2][N/2] complex in slot order: selector t of input b encrypts symbol t of b's word -- the layout of mosfhet_hip_leveled_lut_batch
+ *              with size = steps, hence what mosfhet_hip_circuit_bootstrap_3_dft_batch and mosfhet_hip_trgsw_from_gadget_batch leave on the device;
+ *              1 <= steps <= MOSFHET_HIP_AUTOMATON_MAX_STEPS
+ *   d_init     [count][S][2][N] torus words, the state vector behind the last symbol; with init_shared != 0 [S][2][N], one vector for the whole batch (for example
+ *              trivial samples of the final weights)
+ * THE EVALUATION runs backwards, as in the papers:  V_steps = init;  for t = steps-1 .. 0, with lambda = t mod L, for every state q
+ *     V_t[b][q] = R0 + sel[b][t] (.) (R1 - R0),   R0 = X^rot0[lambda][q] V_{t+1}[b][next0[lambda][q]],   R1 = X^rot1[lambda][q] V_{t+1}[b][next1[lambda][q]]
+ * X^a is the exact negacyclic rotation of both components (torus_polynomial_mul_by_xai, src/polynomial.c:184-199); (.) is the external product of the calls above:
+ * one chain over rows 0 .. 2l-1 from zero, rounded with the reduction mod 1.  V_0[b][q] is what the automaton started in q accumulates over b's word.
+ *   start < 0        d_out is [count][S][2][N] = V_0: a long word is streamed chunk by chunk, LAST CHUNK FIRST, by feeding the output back in as d_init
+ *   0 <= start < S   d_out is [count][2][N] = V_0[b][start], and step 0 computes that state only
+ * No word depends on count, on a sample's position in the batch, on the chunking or on the workspace bound.
+ * MOSFHET_HIP_EINVAL with a message naming the argument, before any HIP call: null pointers; N, gadget, states, layers, steps or start out of range; a table entry out
+ * of range (at creation); count < 0; d_out overlapping d_init as address ranges; a workspace bound (mosfhet_hip_set_leveled_lut_workspace) below one input's state
+ * vectors.  N is the handle's: the batch call takes no ring degree of its own, and the callers that know one from their arguments (Engine.trlwe_automaton,
+ * mosfhet_trlwe_automaton) refuse a handle made for another N.  count == 0 does nothing.
+ * One launch per step and chunk of inputs: the first reads d_init, the last writes d_out, those between alternate between two buffers [chunk][S][2][N] (steps = 1: none,
+ * steps = 2: one) in the CALLING THREAD's pool: no allocation and no synchronisation from the second call of a shape on (capturable from then on) -- and therefore ONE
+ * STREAM PER HOST THREAD at a time, as for mosfhet_hip_leveled_lut_batch.  A batch whose buffers exceed the bound runs in chunks of whole inputs.
+ * mosfhet_hip_trlwe_automaton_plan says what the launcher will do, as a pure function (no GPU; `cus` sizes grids only): plan = {launches, inputs per chunk, workspace
+ * bytes (buffers * chunk * S * 2N * 8), external products (count * (S * (steps - 1) + (start < 0 ? S : 1))), buffers}. */
+#define MOSFHET_HIP_AUTOMATON_MAX_STATES 4096
+#define MOSFHET_HIP_AUTOMATON_MAX_STEPS 4096
+typedef struct mosfhet_hip_automaton *mosfhet_hip_automaton_t;
+int mosfhet_hip_automaton_create(mosfhet_hip_automaton_t *out, const int *h_next0, const int *h_next1, const int *h_rot0, const int *h_rot1 /* each [layers][states] */,
+                                 int states, int layers, int N);
+int mosfhet_hip_automaton_destroy(mosfhet_hip_automaton_t automaton);
+int mosfhet_hip_automaton_info(mosfhet_hip_automaton_t automaton, long long info[3] /* N, states, layers */);
+int mosfhet_hip_trlwe_automaton_batch(mosfhet_hip_ctx_t ctx, uint64_t *d_out, mosfhet_hip_automaton_t automaton, const double *d_sel_dft, const uint64_t *d_init,
+                                      int init_shared, int steps, int start, int l, int Bg_bit, int count, void *stream);
+int mosfhet_hip_trlwe_automaton_plan(int N, int l, int states, int layers, int steps, int start, int count, int cus, long long *plan /*[5]*/);
+
 /* Key images for the on-disk formats (save_bootstrap_key / load_new_bootstrap_key src/bootstrap.c:63-104, trlwe_save_KS_key /
  * trlwe_load_new_KS_key src/keyswitch.c:122-160, tlwe_save_KS_key / tlwe_load_new_KS_key src/tlwe.c:247-287, trlwe_save_generic_ks_key /
  * trlwe_load_new_generic_ks_key src/keyswitch.c:409-455).  DFT-domain contents are backend-defined in the reference too (src/polynomial.c:336-357):

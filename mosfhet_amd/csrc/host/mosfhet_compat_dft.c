@@ -474,6 +474,34 @@ void mosfhet_trlwe_ram_write(TRLWE **mem, TRGSW_DFT **addr, int size, TRLWE *val
   trlwe_ram("mosfhet_trlwe_ram_write", val, addr, size, mem, 1, count);
 }
 
+/* Encrypted automata (mosfhet_hip_trlwe_automaton_batch): word[b] is input b's array of `steps` TRGSW_DFT selectors (symbol t at word[b][t]), init[b] its state
+ * vector of `states` host TRLWEs (init[0] for every input with init_shared), the tables int [layers][states].  out[b] receives V_0[b]: `states` samples with
+ * start < 0, the one sample V_0[b][start] else.  One upload, one call, one download; the handle lives for the call. */
+void mosfhet_trlwe_automaton(TRLWE **out, TRGSW_DFT **word, int steps, TRLWE **init, int init_shared, const int *next0, const int *next1, const int *rot0, const int *rot1,
+                             int states, int layers, int start, int count) {
+  const char *name = "mosfhet_trlwe_automaton";
+  need(out && word && init && next0 && next1 && rot0 && rot1 && steps >= 1 && states >= 1 && layers >= 1 && count >= 1, "mosfhet_trlwe_automaton: bad argument");
+  need_of(steps <= MOSFHET_HIP_AUTOMATON_MAX_STEPS && states <= MOSFHET_HIP_AUTOMATON_MAX_STATES && start < states, name, "steps, states or start out of range");
+  int l, Bg_bit, N, gathered;
+  double *sel = lut_selectors(word, steps, count, &l, &Bg_bit, &N, &gathered, name);
+  need_of(N == 1024 || N == 2048, name, "ring degree must be 1024 or 2048");
+  mosfhet_hip_automaton_t a = NULL;
+  check_rc(mosfhet_hip_automaton_create(&a, next0, next1, rot0, rot1, states, layers, N), name);
+  const size_t row = 2 * (size_t)N, vecs = init_shared ? 1 : (size_t)count, out_rows = start < 0 ? (size_t)states : 1;
+  const size_t init_w = vecs * (size_t)states * row, out_w = (size_t)count * out_rows * row;
+  Torus *h = (Torus *)mc_hstage_alloc(sizeof(Torus) * (init_w + out_w)), *d = (Torus *)mc_stage_alloc(sizeof(Torus) * (init_w + out_w));
+  for (size_t b = 0; b < vecs; b++)
+    for (int q = 0; q < states; q++) mc_trlwe_to_flat(h + (b * (size_t)states + (size_t)q) * row, init[b][q]);
+  mc_dev_copy(d, h, sizeof(Torus) * init_w, HIP_H2D);
+  check_rc(mosfhet_hip_trlwe_automaton_batch(ectx(), d + init_w, a, sel, d, init_shared, steps, start, l, Bg_bit, count, NULL), name);
+  mc_dev_copy(h, d + init_w, sizeof(Torus) * out_w, HIP_D2H);
+  for (size_t b = 0; b < (size_t)count; b++)
+    for (size_t q = 0; q < out_rows; q++) mc_trlwe_from_flat(out[b][q], h + (b * out_rows + q) * row);
+  mc_hstage_free(h);
+  mosfhet_hip_automaton_destroy(a);
+  if (gathered) hipFree(sel);
+}
+
 /* y = W x + bias with cleartext weights on `count` independent inputs (mosfhet_hip_tlwe_linear_batch; tlwe_scale_addto of src/tlwe.c:143-191 row by row):
  * in[b][i] input i of instance b, W [rows_out][rows_in], bias [rows_out] or NULL, out[b][j] of the inputs' dimension.  With a bootstrap key: the linear map, then
  * tlwe_keyswitch, then functional_bootstrap (mosfhet_hip_linear_keyswitch_functional_bootstrap_batch), out[b][j] of dimension N. */

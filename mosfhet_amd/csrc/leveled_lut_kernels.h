@@ -29,6 +29,10 @@
 // Memories that belong to the input (mosfhet_hip_trlwe_ram_read_batch / _write_batch, capi_ram.inc): 2^size TRLWE cells per input, the selectors its address bits.
 // Two further run-time modes of lut_cmux_kernel, no kernel of their own: mode 2 is mode 0's tree level from one place to another (memory -> workspace -> output),
 // mode 3 the chain of `size` CMUXes between a cell and the value to write, the difference in LDS across the products as mode 1 keeps its accumulator.
+//
+// Automata over encrypted words (mosfhet_hip_trlwe_automaton_batch, capi_automaton.inc): a vector of `states` TRLWE samples per input, one backward step per symbol.
+// One further run-time mode of lut_cmux_kernel, mode 4: mode 2's "from one place to another" with the two operands picked by the layer's transition entries and
+// rotated exactly (rot_coeff, as mode 1 rotates) on their way into the difference and, for the base, again at the store.
 #pragma once
 #include "bootstrap_kernels.h"
 
@@ -49,6 +53,11 @@ struct LutParams {
                                      //   mode 2 (a level of a read): lut = the level's source rows, lut_stride = words from one input's rows to the next;
                                      //          out = its destination rows, half0 = destination rows per input; half, sel_index as in mode 0
                                      //   mode 3 (a write): lut = the values [count][2][N]; out = the memories [count][2^size][2][N], updated in place
+                                     // mode 4, a step of an automaton (capi_automaton.inc): lut = the state vectors V_{t+1}, lut_stride = words from one input's vector
+                                     //          to the next (0: one vector shared by the batch); out = V_t, half0 = destination rows per input; half = states computed
+                                     //          per input, the first of them state `steps` (all: half = states, steps = 0; one: half = 1, steps = start);
+                                     //          size = the word's length, sel_index = t; dtab = the layer's transition entries, one 16-byte {next0, next1, rot0, rot1}
+                                     //          per state (read as LutStep through scalar loads: the state of a unit is uniform)
   int steps;                         // mode 1: min(size, log2 N) rotation steps
   // several tables over the same selectors (1 and unused strides for the one-table call)
   int tables;                        // tables of this pass: `lut` and `out` point at the first of them
@@ -58,6 +67,12 @@ struct LutParams {
   // several outputs packed into one table (0 everywhere but in mosfhet_hip_leveled_lut_packed_batch)
   int pack_log;                      // lut_tables_finish_kernel: an entry is m = 2^pack_log adjacent coefficients; step i rotates by m 2^i, m extractions; out is [count][out_tables][m][N + 1]
 };
+
+// mode 4's transition entry of one (layer, state): the sources V_{t+1}[next0], V_{t+1}[next1] and the exponents of their rotations, in [0, 2N)
+struct __attribute__((aligned(16))) LutStep {
+  int next0, next1, rot0, rot1;
+};
+static_assert(sizeof(LutStep) == sizeof(d2), "a transition entry travels in the place of one complex slot");
 
 // GADGET_OFFSET as a function: these kernels have always taken it through one, and the loop compiles differently as text in the kernel (cmux_steps.h)
 __device__ __forceinline__ uint64_t lut_gadget_offset(int l, int Bg_bit) { return GADGET_OFFSET(l, Bg_bit); }
@@ -206,6 +221,11 @@ __device__ __forceinline__ void lut_team_product(const uint64_t *home, bool rota
 //         words of the cell in front of the chain and again behind it, where it stores them: held in registers across the products they are 32 registers on top of
 //         the product's own, which at N = 2048 the 256 of a wavefront do not hold (28 bytes of scratch).  A unit reads and writes its own cell and reads val[b],
 //         which nobody writes.
+// The automata of capi_automaton.inc (a state vector is [states][2][N] words per input, selector t encrypts symbol t of the input's word):
+// mode 4: one backward step: persistent workgroups over the units (b, j), j < half, state q = steps + j with the layer's entry e = dtab[q]:
+//         dst[b][j] = R0 + sel[b][sel_index] (.) (R1 - R0), R0 = X^e.rot0 src[b][e.next0], R1 = X^e.rot1 src[b][e.next1].  R1 - R0 waits in LDS; R0 is rotated
+//         again out of the source row at the store (its pointer and rotation are uniform: scalar registers, nothing of it is held across the product).  src and dst
+//         are different buffers (any unit may read any source row): a unit writes one row of its own, no workgroup waits on or reads from another.
 template <class F>
 constexpr size_t lut_cmux_lds() { return sizeof(d2) * 2 * F::XCH_SLOTS + sizeof(uint64_t) * 2 * F::N; }
 
@@ -296,6 +316,36 @@ __global__ __launch_bounds__(2 * F::THREADS, 2) void lut_cmux_kernel(LutParams p
         cc[M + m * T + t] += ec[M + m * T + t];
       }
       // (the next unit's first stores to e are again this thread's own words, read last by this thread)
+    }
+    return;
+  }
+
+  if (p.mode == 4) {
+    const size_t units = (size_t)p.inputs * p.half;
+    // through the constant address space: the handle's table is not written while a kernel runs, so an entry is one scalar load (as list_word of trace_kernels.h)
+    typedef const LutStep __attribute__((address_space(4))) *const_steps_t;
+    const const_steps_t table = (const_steps_t) reinterpret_cast<const LutStep *>(p.dtab);
+    for (size_t u = blockIdx.x; u < units; u += gridDim.x) {
+      const size_t b = u / (size_t)p.half, j = u % (size_t)p.half;
+      const size_t q = (size_t)p.steps + j;
+      const LutStep e = {table[q].next0, table[q].next1, table[q].rot0, table[q].rot1};
+      const uint64_t *vec = p.lut + b * p.lut_stride;
+      const uint64_t *x = vec + (size_t)e.next0 * 2 * N, *y = vec + (size_t)e.next1 * 2 * N;
+      const Rotation r0 = split_rotation(e.rot0, N), r1 = split_rotation(e.rot1, N);
+      for (int w = tid; w < 2 * N; w += WG) {
+        const int c = w / N, i = w & (N - 1);
+        acc[w] = rot_coeff<N>(y + (size_t)c * N, i, r1.a_lo, r1.flip) - rot_coeff<N>(x + (size_t)c * N, i, r0.a_lo, r0.flip);
+      }
+      workgroup_sync();
+      lut_team_product(acc, false, false, 0, false, p.sel + (((size_t)p.first + b) * p.size + (size_t)p.sel_index) * sel_sz, l, Bg_bit, off, fft, xch_all, team, t, o_re, o_im);
+      const uint64_t *xc = x + (size_t)team * N;          // this team's output component
+      uint64_t *dc = p.out + (b * p.half0 + j) * 2 * N + (size_t)team * N;
+#pragma unroll
+      for (int m = 0; m < 8; m++) {
+        dc[m * T + t] = add_rounded<true>(rot_coeff<N>(xc, m * T + t, r0.a_lo, r0.flip), o_re[m], scale);
+        dc[M + m * T + t] = add_rounded<true>(rot_coeff<N>(xc, M + m * T + t, r0.a_lo, r0.flip), o_im[m], scale);
+      }
+      workgroup_sync();
     }
     return;
   }

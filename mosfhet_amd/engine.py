@@ -147,6 +147,52 @@ def trlwe_ram_plan(N, l, size, count, write=False, cus=256):
     return dict(cells=int(plan[0]), launches=int(plan[1]), chunk=int(plan[2]), workspace_bytes=int(plan[3]), products=int(plan[4]))
 
 
+AUTOMATON_MAX_STATES = 4096    # MOSFHET_HIP_AUTOMATON_MAX_STATES
+AUTOMATON_MAX_STEPS = 4096     # MOSFHET_HIP_AUTOMATON_MAX_STEPS
+
+
+def trlwe_automaton_plan(N, l, states, layers, steps, count, start=-1, cus=256):
+    """What a trlwe_automaton call will do (no device needed): dict(launches, chunk, workspace_bytes, products, buffers) -- kernel launches (one per step and chunk),
+    inputs per chunk, bytes of one chunk's state-vector buffers (buffers * chunk * states * 2N * 8), external products of the call
+    (count * (states * (steps - 1) + (states if start < 0 else 1))) and buffers (0 for one step, 1 for two, else 2).
+    include/mosfhet_hip.h: mosfhet_hip_trlwe_automaton_plan."""
+    plan = (C.c_longlong * 5)()
+    _check(lib().mosfhet_hip_trlwe_automaton_plan(int(N), int(l), int(states), int(layers), int(steps), int(start), int(count), int(cus), plan))
+    return dict(launches=int(plan[0]), chunk=int(plan[1]), workspace_bytes=int(plan[2]), products=int(plan[3]), buffers=int(plan[4]))
+
+
+class Automaton:
+    """The transition tables of a deterministic weighted automaton / layered branching program (mosfhet_hip_automaton_t): made by automaton_create or
+    Engine.automaton_create, shared by every call and batch that runs it."""
+
+    def __init__(self, handle):
+        self.h = handle
+        v = (C.c_longlong * 3)()
+        _check(lib().mosfhet_hip_automaton_info(self.h, v))
+        self.N, self.states, self.layers = int(v[0]), int(v[1]), int(v[2])
+
+    def info(self):
+        return dict(N=self.N, states=self.states, layers=self.layers)
+
+    def close(self):
+        if self.h:
+            lib().mosfhet_hip_automaton_destroy(self.h)
+            self.h = None
+
+    free = close
+
+
+def automaton_create(next0, next1, rot0, rot1, N):
+    """An Automaton from host tables (no device needed: the packed table is copied to a device by the first call that runs there).  next0, next1, rot0, rot1: integer
+    arrays [layers][states] ([states]: one layer, a time-invariant automaton); in state q of layer t mod layers a symbol 0 leads to next0[q] and multiplies by
+    X^rot0[q], a symbol 1 to next1[q] with X^rot1[q].  next in [0, states), rot in [0, 2N); N in {1024, 2048}."""
+    tabs = [np.atleast_2d(np.ascontiguousarray(a, dtype=np.int32)) for a in (next0, next1, rot0, rot1)]
+    assert all(a.ndim == 2 and a.shape == tabs[0].shape for a in tabs), [a.shape for a in tabs]
+    h = C.c_void_p()
+    _check(lib().mosfhet_hip_automaton_create(C.byref(h), *[a.ctypes.data_as(C.c_void_p) for a in tabs], int(tabs[0].shape[1]), int(tabs[0].shape[0]), int(N)))
+    return Automaton(h)
+
+
 def lut_bits_packed_plan(N, l, size, tables, pack_log, count, cus=256):
     """What a lut_bits_packed call will do (no device needed): lut_bits_plan's dict with leveled_lut_packed_plan's dict for one chunk as `lut`.
     include/mosfhet_hip.h: mosfhet_hip_lut_bits_packed_plan."""
@@ -935,6 +981,34 @@ class Engine:
     def trlwe_ram_plan(self, N, l, size, count, write=False):
         """trlwe_ram_plan() at this device's CU count."""
         return trlwe_ram_plan(N, l, size, count, write, self.torch.cuda.get_device_properties(self.device).multi_processor_count)
+
+    def automaton_create(self, next0, next1, rot0, rot1, N):
+        """automaton_create(): the handle is not tied to this engine's device."""
+        return automaton_create(next0, next1, rot0, rot1, N)
+
+    def trlwe_automaton(self, automaton, sel_dft, init, l, Bg_bit, start=-1, out=None):
+        """Encrypted automaton: runs `automaton` backwards over every input's word of encrypted bits.  V_steps = init; for t = steps-1 .. 0 and every state q:
+        V_t[b][q] = R0 + sel[b][t] (.) (R1 - R0) with R0 = X^rot0[q] V_{t+1}[b][next0[q]], R1 = X^rot1[q] V_{t+1}[b][next1[q]] of layer t mod layers.
+        sel_dft: [count][steps][2l][2][N] doubles as for leveled_lut (symbol t of input b's word at [b][t]); init: [count][states][2][N] torus words, or
+        [states][2][N], one vector shared by the batch; returns V_0 [count][states][2][N] with start < 0, else [count][2][N] = V_0[:, start] (the last launch then
+        computes that state only).  A long word is streamed last chunk first by passing the result as the next call's init."""
+        count, steps, N, S = sel_dft.shape[0], sel_dft.shape[1], init.shape[-1], automaton.states
+        if N != automaton.N:
+            raise MosfhetHipError("mosfhet_hip error -1: trlwe_automaton: the automaton was made for N = %d, the state vectors have N = %d" % (automaton.N, N))
+        assert tuple(sel_dft.shape) == (count, steps, 2 * l, 2, N) and sel_dft.dtype == self.torch.float64, tuple(sel_dft.shape)
+        shared = init.dim() == 3
+        assert tuple(init.shape) == ((S, 2, N) if shared else (count, S, 2, N)), tuple(init.shape)
+        shape = (count, S, 2, N) if start < 0 else (count, 2, N)
+        if out is None:
+            out = self.empty(*shape)
+        assert tuple(out.shape) == shape, tuple(out.shape)
+        _check(lib().mosfhet_hip_trlwe_automaton_batch(self.h, _ptr(out), automaton.h, _ptr(sel_dft), _ptr(init), int(shared), int(steps), int(start), int(l), int(Bg_bit),
+                                                       int(count), self._stream()))
+        return out
+
+    def trlwe_automaton_plan(self, N, l, states, layers, steps, count, start=-1):
+        """trlwe_automaton_plan() at this device's CU count."""
+        return trlwe_automaton_plan(N, l, states, layers, steps, count, start, self.torch.cuda.get_device_properties(self.device).multi_processor_count)
 
     def leveled_lut_packed_plan(self, N, l, size, tables, pack_log, count):
         """leveled_lut_packed_plan() at this device's CU count."""

@@ -81,8 +81,8 @@ FORMS = [("N = 2048, l = 1, pipelined loop (the build that failed)", ["-DAB_N=20
          ("Galois bootstrap by component on one CU, 4 x 2^9", ["-DAB_L=4", "-DAB_BG=9", "-DAB_GA"], "bycomp_ab.hip"),
          ("bootstrap by component, throughput form, 4 x 2^9", ["-DAB_L=4", "-DAB_BG=9", "-DAB_TP"], "bycomp_ab.hip"),
          # the leveled-LUT kernels (tools/ab/leveled_lut_ab.hip): table preparation, level 0, tree level / finish and, in the same kernel, the two modes of the
-         # per-input memories (a level of a read, the chain of a write); two-wavefront teams at N = 2048
-         ("leveled LUT: prepare, level 0, CMUX, finish and the memory modes, N = 2048", ["-DAB_N=2048"], "leveled_lut_ab.hip"),
+         # per-input memories (a level of a read, the chain of a write) and the step of an automaton; two-wavefront teams at N = 2048
+         ("leveled LUT: prepare, level 0, CMUX, finish, the memory modes and the automaton step, N = 2048", ["-DAB_N=2048"], "leveled_lut_ab.hip"),
          # the finish of the several-table call (tools/ab/leveled_lut_tables_ab.hip): grouped accumulators in LDS, the table loop inside the step loop
          ("leveled LUT, several tables: grouped finish, N = 2048", ["-DAB_N=2048"], "leveled_lut_tables_ab.hip")]
 
