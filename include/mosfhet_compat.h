@@ -327,6 +327,13 @@ void mosfhet_trlwe_ram_write(TRLWE **mem /*[count][2^size]*/, TRGSW_DFT **addr /
 void mosfhet_trlwe_automaton(TRLWE **out /*[count][states or 1]*/, TRGSW_DFT **word /*[count][steps]*/, int steps, TRLWE **init /*[count or 1][states]*/, int init_shared,
                              const int *next0, const int *next1, const int *rot0, const int *rot1, int states, int layers, int start, int count);
 
+/* Selector logic (new; mosfhet_hip_trgsw_logic_batch, where the gates are defined): a circuit of gates over TRGSW_DFT selectors, the AND gate being
+ * trgsw_mul_DFT2(out, x, y) (src/trgsw.c:433-447).  in[b] and out[b] are arrays as trgsw_alloc_new_DFT_sample_array makes them, of n_in and n_gates samples of one ring
+ * and gadget; gates is int [n_gates][4] = {op, x, y, z} (MOSFHET_HIP_SEL_*): wires 0 .. n_in - 1 are in[b], wire n_in + g is out[b][g], a gate reads inputs and EARLIER
+ * gates only and its unused fields are -1.  THE DEEPER WIRE GOES IN x, and a gate's output is usable only at a fine gadget with small noise such as (2048, 4, 9),
+ * sigma 2^-44 (include/mosfhet_hip.h).  One launch per level of the circuit.  Synchronous; aborts on error; primary device; N = 1024 or 2048. */
+void mosfhet_trgsw_logic(TRGSW_DFT **out /*[count][n_gates]*/, TRGSW_DFT **in /*[count][n_in]*/, const int *gates /*[n_gates][4]*/, int n_gates, int n_in, int count);
+
 /* A cleartext-weight layer on `count` independent inputs in one call (new; mosfhet_hip_tlwe_linear_batch): out[b][j] = (0, bias[j]) + sum_i W[j][i] in[b][i], the
  * loop of tlwe_scale_addto (src/tlwe.c:143-191) over the rows of W [rows_out][rows_in]; W[j][i] is the multiplier tlwe_scale takes, bias [rows_out] torus words or
  * NULL.  out[b][j] has the inputs' dimension.  Synchronous; aborts on error; primary device. */

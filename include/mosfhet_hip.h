@@ -925,6 +925,69 @@ int mosfhet_hip_trlwe_automaton_batch(mosfhet_hip_ctx_t ctx, uint64_t *d_out, mo
                                       int init_shared, int steps, int start, int l, int Bg_bit, int count, void *stream);
 int mosfhet_hip_trlwe_automaton_plan(int N, int l, int states, int layers, int steps, int start, int count, int cus, long long *plan /*[5]*/);
 
+/* Selector logic: circuits of gates over TRGSW-encrypted bits, computed on the device FROM selectors (the reference's trgsw_mul_DFT / trgsw_mul_DFT2,
+ * src/trgsw.c:425-442, are the AND gate).  The look-up tables, memories, automata and encrypted-weight layers above consume TRGSW_DFT selectors; this call makes new
+ * ones from them without a bootstrap: an address is incremented, two address bits become a one-hot line, an automaton's symbol is the XOR of two encrypted bits.
+ * Ring and gadget: N in {1024, 2048}, k = 1; the gadget is a run-time argument: 1 <= l <= 6, Bg_bit <= 31, l * Bg_bit < 64.
+ * WIRES 0 .. n_in - 1 are a batch element's input selectors; wire n_in + g is the output of gate g.
+ * THE CIRCUIT is a handle made from a host array int32 [n_gates][4] = {op, x, y, z} and shared by the batch.  Every operand a gate uses is a wire index below n_in + g
+ * (inputs or EARLIER gates only; x = y is allowed); every operand field a gate does not use must be -1; 1 <= n_in, n_gates <= MOSFHET_HIP_SELLOGIC_MAX_WIRES.
+ * X, Y, Z are the TRGSW_DFT samples on a gate's wires, r = c l + i a row (c = 0: component a, c = 1: component b):
+ *   T(S)_r   = (G(S[r].a), G(S[r].b)), G = polynomial_DFT_to_torus, nearest mod 2^64: the words mosfhet_hip_dft_to_torus_batch writes
+ *   E(L, W)  = the external product of the TRLWE sample L with W: one chain from +0.0 over W's rows 0 .. 2l-1 (the digits of L.a levels first, then L.b;
+ *              polynomial_decompose_i, polynomial_torus_to_DFT, the two-FMA mul_addto with the digit first and the row second), then G of both accumulators
+ *   H_r      = row r of the trivial sample of 1: 2^(64 - (i + 1) Bg_bit) at coefficient 0 of component c, zero elsewhere
+ *   F        = polynomial_torus_to_DFT exactly as mosfhet_hip_torus_to_dft_batch makes it;  P_r = E(T(X)_r, Y);  all integer arithmetic mod 2^64
+ *   op  name    operands   row r of the output, before F
+ *   0   NOT     x          H_r - T(X)_r
+ *   1   AND     x, y       P_r                                   trgsw_mul_DFT2(out, X, Y) row for row
+ *   2   NAND    x, y       H_r - P_r
+ *   3   OR      x, y       T(X)_r + T(Y)_r - P_r
+ *   4   NOR     x, y       H_r - T(X)_r - T(Y)_r + P_r
+ *   5   XOR     x, y       T(X)_r + T(Y)_r - 2 P_r
+ *   6   XNOR    x, y       H_r - T(X)_r - T(Y)_r + 2 P_r
+ *   7   ANDNOT  x, y       T(X)_r - P_r                          x and not y
+ *   8   MUX     x, y, z    T(Y)_r + E(T(X)_r - T(Y)_r, Z)        z ? x : y
+ * out[r] = (F(row.a), F(row.b)).  These are ring identities: the same gates multiply, add and select selectors of monomials or other small polynomials.
+ * No word depends on count, on a batch element's position, on the launch geometry or on how levels are grouped.  AND is NOT commutative, in its words or in its noise:
+ * THE DEEPER WIRE GOES IN x.  The left operand's noise is added; the right operand's row noise and the gadget's approximation error are multiplied by the digit norm
+ * once in the gate and once more when the result is used.  At (N, l, Bg_bit) = (2048, 4, 9) with sigma 2^-44 a gate output's external product with a sample of 4-bit
+ * messages in slots of 2^60 errs by about 2^50 - 2^52, and a chain with the accumulated wire in x grows by about 0.2 bit per gate; with the accumulated wire in y the
+ * result is lost at depth 2.  A GATE'S OUTPUT IS USABLE ONLY AT SUCH A FINE GADGET WITH SUCH NOISE: at (1024, 2, 8), (1024, 3, 10), (1024, 6, 7) with sigma 2.989e-8
+ * and at (2048, 1, 23) nothing survives one product (tests/test_trgsw_logic.py measures both), and selectors of mosfhet_hip_circuit_bootstrap_3_dft_batch are not
+ * expected to survive one either.  The words are defined and tested at every gadget all the same.
+ *   d_in_dft   [count][n_in][2l][2][N/2] complex in slot order: the layout of d_sel_dft of the leveled calls with size = n_in
+ *   d_out_dft  [count][n_gates][2l][2][N/2] complex: EVERY gate's output, row g of a batch element = wire n_in + g (a d_sel_dft with size = n_gates: the caller picks
+ *              its outputs by index); later levels read earlier rows of it
+ * Creation checks every entry, computes level(g) = 1 + the highest level of g's operands (inputs: 0) and packs the gates sorted by level -- on the host, no device is
+ * needed; the packed table is copied to a device the first time a call runs there (one allocation, one synchronous copy) and stays for the handle's life.  The call is
+ * one launch per level, teams = count x gates of the level x 2l (a batch whose widest level exceeds one grid runs in chunks of whole batch elements); no pool, no
+ * workspace; asynchronous on `stream`, never synchronises, capturable from the first call after the table is on the device.
+ * MOSFHET_HIP_EINVAL with a message naming the argument, before any HIP call: null pointers; N, gadget, n_in or n_gates out of range; a gate entry that is no op, uses
+ * a wire that is not earlier or sets an unused field (at creation); count < 0; d_out_dft overlapping d_in_dft as address ranges.  N is the handle's (Engine.trgsw_logic
+ * refuses tensors of another N).  count == 0 does nothing.
+ * mosfhet_hip_sellogic_info: info = {N, n_in, n_gates, levels, product gates (every op but NOT: 2l external products per batch element each)}.
+ * mosfhet_hip_trgsw_logic_plan says what the launcher will do, as a pure function (no GPU; `cus` is reserved): plan = {launches, teams of the widest launch, external
+ * products, inverse transforms, forward transforms}; the last three are those of n_gates AND gates (count x 2l x n_gates products; a handle's own count is
+ * count x 2l x info[4]). */
+#define MOSFHET_HIP_SELLOGIC_MAX_WIRES 4096
+#define MOSFHET_HIP_SEL_NOT 0
+#define MOSFHET_HIP_SEL_AND 1
+#define MOSFHET_HIP_SEL_NAND 2
+#define MOSFHET_HIP_SEL_OR 3
+#define MOSFHET_HIP_SEL_NOR 4
+#define MOSFHET_HIP_SEL_XOR 5
+#define MOSFHET_HIP_SEL_XNOR 6
+#define MOSFHET_HIP_SEL_ANDNOT 7
+#define MOSFHET_HIP_SEL_MUX 8
+typedef struct mosfhet_hip_sellogic *mosfhet_hip_sellogic_t;
+int mosfhet_hip_sellogic_create(mosfhet_hip_sellogic_t *out, const int *h_gates /*[n_gates][4]*/, int n_gates, int n_in, int N);
+int mosfhet_hip_sellogic_destroy(mosfhet_hip_sellogic_t c);
+int mosfhet_hip_sellogic_info(mosfhet_hip_sellogic_t c, long long info[5] /* N, n_in, n_gates, levels, product gates */);
+int mosfhet_hip_trgsw_logic_batch(mosfhet_hip_ctx_t ctx, double *d_out_dft /*[count][n_gates][2l][2][N/2] complex*/, mosfhet_hip_sellogic_t c,
+                                  const double *d_in_dft /*[count][n_in][2l][2][N/2] complex*/, int l, int Bg_bit, int count, void *stream);
+int mosfhet_hip_trgsw_logic_plan(int N, int l, int n_in, int n_gates, int levels, int widest_level, int count, int cus, long long *plan /*[5]*/);
+
 /* Key images for the on-disk formats (save_bootstrap_key / load_new_bootstrap_key src/bootstrap.c:63-104, trlwe_save_KS_key /
  * trlwe_load_new_KS_key src/keyswitch.c:122-160, tlwe_save_KS_key / tlwe_load_new_KS_key src/tlwe.c:247-287, trlwe_save_generic_ks_key /
  * trlwe_load_new_generic_ks_key src/keyswitch.c:409-455).  DFT-domain contents are backend-defined in the reference too (src/polynomial.c:336-357):

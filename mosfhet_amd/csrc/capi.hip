@@ -1819,3 +1819,4 @@ extern "C" int mosfhet_hip_time_programmable_bootstrap(mosfhet_hip_ctx_t ctx, mo
 #include "capi_gswlinear.inc"
 #include "capi_ram.inc"
 #include "capi_automaton.inc"
+#include "capi_sellogic.inc"

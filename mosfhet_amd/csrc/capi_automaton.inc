@@ -95,21 +95,25 @@ extern "C" int mosfhet_hip_automaton_info(mosfhet_hip_automaton_t automaton, lon
   return MOSFHET_HIP_OK;
 }
 
-// the table's copy on `device` (the current one): made by the first call there, synchronously, and kept for the handle's life
-static int automaton_image(mosfhet_hip_automaton_t a, int device, const LutStep **out) {
-  std::lock_guard<std::mutex> guard(a->lock);
-  auto it = a->images.find(device);
-  if (it == a->images.end()) {
+// a handle's packed table on `device` (the current one): the copy is made by the first call there, synchronously, under the handle's lock, and kept for the handle's
+// life (the automaton's transition entries here, the gate records of capi_sellogic.inc)
+template <class T>
+static int table_image(std::mutex &lock, std::map<int, T *> &images, const std::vector<T> &table, int device, const T **out) {
+  std::lock_guard<std::mutex> guard(lock);
+  auto it = images.find(device);
+  if (it == images.end()) {
     DevBuf image;
-    const size_t bytes = a->table.size() * sizeof(LutStep);
+    const size_t bytes = table.size() * sizeof(T);
     HIP_TRY(image.alloc(bytes));
-    HIP_TRY(hipMemcpy(image.p, a->table.data(), bytes, hipMemcpyHostToDevice));
-    it = a->images.emplace(device, image.as<LutStep>()).first;
+    HIP_TRY(hipMemcpy(image.p, table.data(), bytes, hipMemcpyHostToDevice));
+    it = images.emplace(device, image.as<T>()).first;
     image.p = nullptr;
   }
   *out = it->second;
   return MOSFHET_HIP_OK;
 }
+
+static int automaton_image(mosfhet_hip_automaton_t a, int device, const LutStep **out) { return table_image(a->lock, a->images, a->table, device, out); }
 
 template <class F>
 static int launch_automaton(const AutomatonPlan &plan, LutParams p, uint64_t *d_out, const LutStep *image, const uint64_t *d_init, int init_shared, uint64_t *ws, int states,

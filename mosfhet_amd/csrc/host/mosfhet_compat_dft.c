@@ -502,6 +502,33 @@ void mosfhet_trlwe_automaton(TRLWE **out, TRGSW_DFT **word, int steps, TRLWE **i
   if (gathered) hipFree(sel);
 }
 
+/* Selector logic (mosfhet_hip_trgsw_logic_batch): in[b] is batch element b's array of n_in TRGSW_DFT selectors, out[b] its array of n_gates selectors, gate g's
+ * output at out[b][g]; gates is int [n_gates][4] = {op, x, y, z}.  The samples live on the device: the call reads and writes their blocks where the arrays follow each
+ * other in memory, else through one gathered block each.  The handle is made from the samples' N and lives for the call. */
+void mosfhet_trgsw_logic(TRGSW_DFT **out, TRGSW_DFT **in, const int *gates, int n_gates, int n_in, int count) {
+  const char *name = "mosfhet_trgsw_logic";
+  need(out && in && gates && n_gates >= 1 && n_in >= 1 && count >= 1, "mosfhet_trgsw_logic: bad argument");
+  need_of(n_gates <= MOSFHET_HIP_SELLOGIC_MAX_WIRES && n_in <= MOSFHET_HIP_SELLOGIC_MAX_WIRES, name, "n_gates or n_in out of range");
+  int l, Bg_bit, N, gathered, lo, Bo, No, scattered;
+  double *src = lut_selectors(in, n_in, count, &l, &Bg_bit, &N, &gathered, name);
+  double *dst = lut_selectors(out, n_gates, count, &lo, &Bo, &No, &scattered, name);
+  need_of(lo == l && No == N, name, "the outputs' ring or gadget length differs from the inputs'");
+  need_of(N == 1024 || N == 2048, name, "ring degree must be 1024 or 2048");
+  mosfhet_hip_sellogic_t c = NULL;
+  check_rc(mosfhet_hip_sellogic_create(&c, gates, n_gates, n_in, N), name);
+  check_rc(mosfhet_hip_trgsw_logic_batch(ectx(), dst, c, src, l, Bg_bit, count, NULL), name);
+  need_of(hipStreamSynchronize(NULL) == 0, name, "the device reported an error");
+  const size_t esz = trgsw_dft_doubles(l, N);
+  for (int b = 0; b < count; b++)
+    for (int g = 0; g < n_gates; g++) {
+      if (scattered) mc_dev_copy(trgsw_dft_base(out[b][g], name), dst + ((size_t)b * n_gates + g) * esz, sizeof(double) * esz, HIP_D2D);
+      out[b][g]->Bg_bit = Bg_bit;
+    }
+  mosfhet_hip_sellogic_destroy(c);
+  if (gathered) hipFree(src);
+  if (scattered) hipFree(dst);
+}
+
 /* y = W x + bias with cleartext weights on `count` independent inputs (mosfhet_hip_tlwe_linear_batch; tlwe_scale_addto of src/tlwe.c:143-191 row by row):
  * in[b][i] input i of instance b, W [rows_out][rows_in], bias [rows_out] or NULL, out[b][j] of the inputs' dimension.  With a bootstrap key: the linear map, then
  * tlwe_keyswitch, then functional_bootstrap (mosfhet_hip_linear_keyswitch_functional_bootstrap_batch), out[b][j] of dimension N. */

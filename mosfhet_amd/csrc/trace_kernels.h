@@ -45,6 +45,9 @@
 //                                  per lane, two cmacs per point (digit first, row second) into the accumulator pair; then polylinear_finish, the tail kind 4 runs.
 //                                  Registers: kind 5 holds one component's digit words and one transform, kind 6 two accumulator pairs and three operand rows --
 //                                  what kind 4 holds.
+//   sel_gate_body<F>             kind 7 (mosfhet_hip_trgsw_logic_batch; trgsw_mul_DFT2, src/trgsw.c:425-442, and its ring combinations): one team per (batch element,
+//                                  gate of the level, row r) -- the row of X (and Y) back to torus words, the external product of that row with the right operand
+//                                  as ks_rows_rt forms it, the op's integer combination, and the forward tail of kind 2.  No torus-domain word is written.
 // Launch bound 1 like trlwe_fft_keyswitch_kernel: digit words, accumulator and the two product pairs are live together.
 #pragma once
 #include <stdint.h>
@@ -55,7 +58,7 @@
 namespace mosfhet {
 
 enum { TRACE_KIND_PACK = 0, TRACE_KIND_PRIV = 1, TRACE_KIND_GADGET = 2, TRACE_KIND_MANY = 3, TRACE_KIND_POLYLINEAR = 4, TRACE_KIND_GSW_DIGITS = 5,
-       TRACE_KIND_GSW_SUM = 6 };
+       TRACE_KIND_GSW_SUM = 6, TRACE_KIND_SEL_GATE = 7 };
 
 struct TraceParams {
   const d2 *__restrict__ key;   // the first entry the call uses: [log2 N or 2][t][2][M] complex
@@ -75,6 +78,8 @@ struct TraceParams {
   int rows_out, rows_in, idx;        // idx < 0: the TRLWE sample; else trlwe_extract_tlwe(., idx)
   // kind 5: in = the inputs of the round [count][rows_in][2][N], sel = the pool [count][rows_in][2l][M] complex, (l, base_bit) = the gadget
   // kind 6: key = the weights [entries][2l][2][M] complex, xin = the pool, l; row_ptr, col, bias, rows_out, rows_in, idx, out as kind 4
+  // kind 7: xin = the input selectors of the launch [count][rows_in][2l][2][M] complex, sel = every gate's output [count][rows_out][2l][2][M] complex, row_ptr = the
+  //         level's SelGate records, idx = gates of the level, (l, base_bit) = the gadget
 };
 
 // One step on the accumulator (a in al / ah, b in acc1):  acc += KeySwitch_entry(v(X^gen)).  The permutation of ga_eval_automorphism (scatter through LDS, signs by bit N
@@ -433,6 +438,119 @@ __device__ __forceinline__ void gsw_sum_body(d2 *xch, const F &fft, const TraceP
   polylinear_finish<F>(o_re, o_im, xch, fft, p, j, tid);
 }
 
+// kind 7's gate record, one per gate in the handle's level-sorted table: op_row = op | (gate index << 4); x, y, z = wire indices (-1: unused)
+struct __attribute__((aligned(16))) SelGate {
+  int op_row, x, y, z;
+};
+enum { SEL_NOT = 0, SEL_AND, SEL_NAND, SEL_OR, SEL_NOR, SEL_XOR, SEL_XNOR, SEL_ANDNOT, SEL_MUX, SEL_OPS };
+
+// T(S)_r.c: one polynomial of a selector row back in the torus domain, the words torus_to_dft_kernel's inverse direction writes
+template <class F>
+__device__ __forceinline__ void sel_row_words(uint64_t (&lo)[8], uint64_t (&hi)[8], const d2 *poly, d2 *xch, const F &fft, const RoundCtx &scale, int tid) {
+  constexpr int T = F::THREADS;
+  double re[8], im[8];
+#pragma unroll
+  for (int m = 0; m < 8; m++) { const d2 v = poly[m * T + tid]; re[m] = v.x; im[m] = v.y; }
+  fft.inverse(re, im, xch, tid);
+#pragma unroll
+  for (int m = 0; m < 8; m++) { lo[m] = round_mod_2_64(re[m], scale); hi[m] = round_mod_2_64(im[m], scale); }
+}
+
+// kind 7: row r of gate k of the level on batch element b, blockIdx.x = (b gates + k) 2l + r:
+//   out[r] = F(h H_r + cx T(X)_r + cy T(Y)_r + cp E(L, W)),   L = T(X)_r (MUX: T(X)_r - T(Y)_r),  W = Y (MUX: Z)
+//   op      NOT  AND  NAND  OR  NOR  XOR  XNOR  ANDNOT  MUX
+//   h        1    0    1    0    1    0    1      0      0
+//   cx      -1    0    0    1   -1    1   -1      1      0
+//   cy       0    0    0    1   -1    1   -1      0      1
+//   cp       0    1   -1   -1    1   -2    2     -1      1
+// E is the external product of the other calls: the digits of L.a against W's rows 0 .. l - 1, then those of L.b against rows l .. 2l - 1, into ONE accumulator pair from
+// +0.0 (ks_rows_rt twice), two inverse transforms, the general rounding.  Only the product's words stay in registers across the tail: the rows of X and Y are loaded
+// and inverted again behind it (lut_cmux_kernel mode 4 re-reads its base the same way), so the kind holds less than rlwe_priv_keyswitch_body does.  Wires below rows_in
+// are rows of xin, the others rows of sel written by EARLIER launches: a gate never reads the level it belongs to.
+template <class F>
+__device__ __forceinline__ void sel_gate_body(d2 *xch, const F &fft, const TraceParams &p, int tid) {
+  constexpr int M = F::M, T = F::THREADS;
+  const int l = p.l, base_bit = p.base_bit;
+  const unsigned rows = 2 * l, r = blockIdx.x % rows, u = blockIdx.x / rows, k = u % (unsigned)p.idx, b = u / (unsigned)p.idx;
+  // through the constant address space: the handle's table is not written while a kernel runs, so the record is one 16-byte scalar load (LutStep's idiom)
+  typedef const SelGate __attribute__((address_space(4))) *const_gates_t;
+  const const_gates_t table = (const_gates_t) reinterpret_cast<const SelGate *>(p.row_ptr);
+  const SelGate e = {table[k].op_row, table[k].x, table[k].y, table[k].z};
+  const int op = e.op_row & 15;
+  const size_t row = (size_t)2 * M, sample = rows * row;
+  const d2 *in = p.xin + (size_t)b * p.rows_in * sample;
+  d2 *mine = p.sel + (size_t)b * p.rows_out * sample;   // read (earlier gates) and written (this gate): no __restrict__
+  const d2 *X = (e.x < p.rows_in ? in + (size_t)e.x * sample : mine + (size_t)(e.x - p.rows_in) * sample) + r * row;
+  const int wy = op == SEL_NOT ? e.x : e.y, wz = op == SEL_MUX ? e.z : wy;
+  const d2 *Ys = wy < p.rows_in ? in + (size_t)wy * sample : mine + (size_t)(wy - p.rows_in) * sample;
+  const d2 *W = wz < p.rows_in ? in + (size_t)wz * sample : mine + (size_t)(wz - p.rows_in) * sample;
+  const d2 *Y = Ys + r * row;
+  const bool h = (0x055u >> op) & 1;
+  const uint64_t cx = (uint64_t)(int64_t)((int)(((0x07743u >> (2 * op)) & 3) ^ 2) - 2), cy = (uint64_t)(int64_t)((int)(((0x13740u >> (2 * op)) & 3) ^ 2) - 2);
+  const uint64_t cp = (uint64_t)(int64_t)((int)(((uint32_t)(0x1F2E1FF10ull >> (4 * op)) & 15) ^ 8) - 8);
+  const RoundCtx scale = round_scale<M>();
+  uint64_t pa_lo[8], pa_hi[8], pb_lo[8], pb_hi[8];
+#pragma unroll
+  for (int m = 0; m < 8; m++) { pa_lo[m] = 0; pa_hi[m] = 0; pb_lo[m] = 0; pb_hi[m] = 0; }
+  if (cp) {
+    const uint64_t off = GADGET_OFFSET(l, base_bit);
+    double o_re[2][8], o_im[2][8];
+#pragma unroll
+    for (int cc = 0; cc < 2; cc++)
+#pragma unroll
+      for (int m = 0; m < 8; m++) { o_re[cc][m] = 0.0; o_im[cc][m] = 0.0; }
+#pragma unroll 1
+    for (int cc = 0; cc < 2; cc++) {
+      uint64_t dd_lo[8], dd_hi[8];
+      sel_row_words<F>(dd_lo, dd_hi, X + cc * M, xch, fft, scale, tid);
+      if (op == SEL_MUX) {
+        uint64_t y_lo[8], y_hi[8];
+        sel_row_words<F>(y_lo, y_hi, Y + cc * M, xch, fft, scale, tid);
+#pragma unroll
+        for (int m = 0; m < 8; m++) { dd_lo[m] -= y_lo[m]; dd_hi[m] -= y_hi[m]; }
+      }
+#pragma unroll
+      for (int m = 0; m < 8; m++) { dd_lo[m] += off; dd_hi[m] += off; }
+      ks_rows_rt<F>(dd_lo, dd_hi, o_re, o_im, xch, fft, W + (size_t)cc * l * row, l, base_bit, tid);
+    }
+    fft.inverse(o_re[0], o_im[0], xch, tid);
+#pragma unroll
+    for (int m = 0; m < 8; m++) { pa_lo[m] = cp * round_mod_2_64(o_re[0][m], scale); pa_hi[m] = cp * round_mod_2_64(o_im[0][m], scale); }
+    fft.inverse(o_re[1], o_im[1], xch, tid);
+#pragma unroll
+    for (int m = 0; m < 8; m++) { pb_lo[m] = cp * round_mod_2_64(o_re[1][m], scale); pb_hi[m] = cp * round_mod_2_64(o_im[1][m], scale); }
+  }
+  // H_r: 2^(64 - (i + 1) Bg_bit) at coefficient 0 (thread 0, word 0) of component c, r = c l + i
+  const unsigned c = r >= (unsigned)l, i = r - c * l;
+  const uint64_t hw = h ? 1ull << (64 - (i + 1) * base_bit) : 0;
+  d2 *dst = mine + (size_t)(e.op_row >> 4) * sample + r * row;
+#pragma unroll 1
+  for (int q = 0; q < 2; q++) {   // one rolled body, as rlwe_priv_keyswitch_body's tail
+    uint64_t v_lo[8], v_hi[8];
+#pragma unroll
+    for (int m = 0; m < 8; m++) { v_lo[m] = q ? pb_lo[m] : pa_lo[m]; v_hi[m] = q ? pb_hi[m] : pa_hi[m]; }
+    if (cx) {
+      uint64_t t_lo[8], t_hi[8];
+      sel_row_words<F>(t_lo, t_hi, X + q * M, xch, fft, scale, tid);
+#pragma unroll
+      for (int m = 0; m < 8; m++) { v_lo[m] += cx * t_lo[m]; v_hi[m] += cx * t_hi[m]; }
+    }
+    if (cy) {
+      uint64_t t_lo[8], t_hi[8];
+      sel_row_words<F>(t_lo, t_hi, Y + q * M, xch, fft, scale, tid);
+#pragma unroll
+      for (int m = 0; m < 8; m++) { v_lo[m] += cy * t_lo[m]; v_hi[m] += cy * t_hi[m]; }
+    }
+    if ((unsigned)q == c && tid == 0) v_lo[0] += hw;
+    double re[8], im[8];
+#pragma unroll
+    for (int m = 0; m < 8; m++) { re[m] = torus_to_double(v_lo[m]); im[m] = torus_to_double(v_hi[m]); }
+    fft.forward(re, im, xch, tid);
+#pragma unroll
+    for (int m = 0; m < 8; m++) dst[q * M + m * T + tid] = d2{re[m], im[m]};
+  }
+}
+
 template <class F>
 __global__ __launch_bounds__(F::THREADS, 1) void trace_conversions_kernel(TraceParams p) {
   __shared__ __attribute__((aligned(16))) d2 xch[F::XCH_SLOTS];
@@ -444,6 +562,7 @@ __global__ __launch_bounds__(F::THREADS, 1) void trace_conversions_kernel(TraceP
   else if (p.kind == TRACE_KIND_POLYLINEAR) polylinear_body<F>(xch, fft, p, tid);
   else if (p.kind == TRACE_KIND_GSW_DIGITS) gsw_digits_body<F>(xch, fft, p, tid);
   else if (p.kind == TRACE_KIND_GSW_SUM) gsw_sum_body<F>(xch, fft, p, tid);
+  else if (p.kind == TRACE_KIND_SEL_GATE) sel_gate_body<F>(xch, fft, p, tid);
   else rlwe_priv_keyswitch_body<F>(xch, fft, p.key, p.key + (size_t)p.t * 2 * F::M, p.in, p.out, p.t, p.base_bit, p.kind == TRACE_KIND_GADGET ? p.sel : nullptr, p.l, tid);
 }
 

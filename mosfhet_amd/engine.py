@@ -193,6 +193,50 @@ def automaton_create(next0, next1, rot0, rot1, N):
     return Automaton(h)
 
 
+SELLOGIC_MAX_WIRES = 4096      # MOSFHET_HIP_SELLOGIC_MAX_WIRES
+SEL_NOT, SEL_AND, SEL_NAND, SEL_OR, SEL_NOR, SEL_XOR, SEL_XNOR, SEL_ANDNOT, SEL_MUX = range(9)   # MOSFHET_HIP_SEL_*
+
+
+def trgsw_logic_plan(N, l, n_in, n_gates, levels, widest_level, count, cus=256):
+    """What a trgsw_logic call will do (no device needed): dict(launches, teams, products, inverses, forwards) -- kernel launches (one per level and chunk of batch
+    elements), teams of the widest launch, and the external products, inverse and forward transforms of n_gates AND gates (count * 2l * n_gates products; a circuit's
+    own count is count * 2l * SelLogic.product_gates).  include/mosfhet_hip.h: mosfhet_hip_trgsw_logic_plan."""
+    plan = (C.c_longlong * 5)()
+    _check(lib().mosfhet_hip_trgsw_logic_plan(int(N), int(l), int(n_in), int(n_gates), int(levels), int(widest_level), int(count), int(cus), plan))
+    return dict(launches=int(plan[0]), teams=int(plan[1]), products=int(plan[2]), inverses=int(plan[3]), forwards=int(plan[4]))
+
+
+class SelLogic:
+    """A circuit of gates over TRGSW_DFT selectors (mosfhet_hip_sellogic_t): made by sellogic_create or Engine.sellogic_create, shared by every call and batch."""
+
+    def __init__(self, handle):
+        self.h = handle
+        v = (C.c_longlong * 5)()
+        _check(lib().mosfhet_hip_sellogic_info(self.h, v))
+        self.N, self.n_in, self.n_gates, self.levels, self.product_gates = (int(x) for x in v)
+
+    def info(self):
+        return dict(N=self.N, n_in=self.n_in, n_gates=self.n_gates, levels=self.levels, product_gates=self.product_gates)
+
+    def close(self):
+        if self.h:
+            lib().mosfhet_hip_sellogic_destroy(self.h)
+            self.h = None
+
+    free = close
+
+
+def sellogic_create(gates, n_in, N):
+    """A SelLogic from a host gate list (no device needed: the packed table is copied to a device by the first call that runs there).  gates: integers [n_gates][4] =
+    {op, x, y, z} with op one of SEL_NOT .. SEL_MUX; wires 0 .. n_in - 1 are the inputs, wire n_in + g the output of gate g; a gate reads inputs and EARLIER gates
+    only, and the fields it does not use are -1 (NOT: y, z; MUX uses all three, z ? x : y; the others: z).  N in {1024, 2048}."""
+    g = np.ascontiguousarray(gates, dtype=np.int32)
+    assert g.ndim == 2 and g.shape[1] == 4, g.shape
+    h = C.c_void_p()
+    _check(lib().mosfhet_hip_sellogic_create(C.byref(h), g.ctypes.data_as(C.c_void_p), int(g.shape[0]), int(n_in), int(N)))
+    return SelLogic(h)
+
+
 def lut_bits_packed_plan(N, l, size, tables, pack_log, count, cus=256):
     """What a lut_bits_packed call will do (no device needed): lut_bits_plan's dict with leveled_lut_packed_plan's dict for one chunk as `lut`.
     include/mosfhet_hip.h: mosfhet_hip_lut_bits_packed_plan."""
@@ -1009,6 +1053,31 @@ class Engine:
     def trlwe_automaton_plan(self, N, l, states, layers, steps, count, start=-1):
         """trlwe_automaton_plan() at this device's CU count."""
         return trlwe_automaton_plan(N, l, states, layers, steps, count, start, self.torch.cuda.get_device_properties(self.device).multi_processor_count)
+
+    def sellogic_create(self, gates, n_in, N):
+        """sellogic_create(): the handle is not tied to this engine's device."""
+        return sellogic_create(gates, n_in, N)
+
+    def trgsw_logic(self, circuit, in_dft, l, Bg_bit, out=None):
+        """Selector logic: evaluates `circuit` on every batch element's input selectors and returns EVERY gate's output selector, [count][n_gates][2l][2][N] float64
+        (row g = wire n_in + g: a sel_dft of the leveled calls with size = n_gates; pick outputs by index).  in_dft: [count][n_in][2l][2][N] float64 as for leveled_lut.
+        One launch per level.  AND-like gates are not commutative in their noise: THE DEEPER WIRE GOES IN x (the left operand's noise is added, the right operand's
+        is amplified), and a gate's output is usable only at a fine gadget with lvl2-sized noise such as (2048, 4, 9), sigma 2^-44 -- include/mosfhet_hip.h."""
+        count, N = in_dft.shape[0], in_dft.shape[-1]
+        if N != circuit.N:
+            raise MosfhetHipError("mosfhet_hip error -1: trgsw_logic: the circuit was made for N = %d, the selectors have N = %d" % (circuit.N, N))
+        assert tuple(in_dft.shape) == (count, circuit.n_in, 2 * l, 2, N) and in_dft.dtype == self.torch.float64, tuple(in_dft.shape)
+        shape = (count, circuit.n_gates, 2 * l, 2, N)
+        if out is None:
+            out = self.torch.empty(shape, dtype=self.torch.float64, device=self.device)
+        assert tuple(out.shape) == shape and out.dtype == self.torch.float64, tuple(out.shape)
+        _check(lib().mosfhet_hip_trgsw_logic_batch(self.h, _ptr(out) if count else None, circuit.h, _ptr(in_dft) if count else None, int(l), int(Bg_bit), int(count),
+                                                   self._stream()))
+        return out
+
+    def trgsw_logic_plan(self, N, l, n_in, n_gates, levels, widest_level, count):
+        """trgsw_logic_plan() at this device's CU count."""
+        return trgsw_logic_plan(N, l, n_in, n_gates, levels, widest_level, count, self.torch.cuda.get_device_properties(self.device).multi_processor_count)
 
     def leveled_lut_packed_plan(self, N, l, size, tables, pack_log, count):
         """leveled_lut_packed_plan() at this device's CU count."""
