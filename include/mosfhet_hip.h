@@ -988,6 +988,65 @@ int mosfhet_hip_trgsw_logic_batch(mosfhet_hip_ctx_t ctx, double *d_out_dft /*[co
                                   const double *d_in_dft /*[count][n_in][2l][2][N/2] complex*/, int l, int Bg_bit, int count, void *stream);
 int mosfhet_hip_trgsw_logic_plan(int N, int l, int n_in, int n_gates, int levels, int widest_level, int count, int cus, long long *plan /*[5]*/);
 
+/* ---- The client half on the device: encrypting and opening batches of samples under a secret key (csrc/capi_client.inc, csrc/client_kernels.h; the reference's
+ * tlwe_new_sample / tlwe_phase, src/tlwe.c, trlwe_new_sample / trlwe_phase, src/trlwe.c:296-331, trgsw_new_monomial_sample + trgsw_to_DFT, src/trgsw.c:152-168).
+ * For a user who keeps key and data on one trusted box: selectors for the leveled calls are made, and their results opened, without a host round trip.  k = 1.
+ *
+ * mosfhet_hip_client_key_create makes the key handle ON THE HOST (no device needed): h_s_rlwe [N] with N a power of two in 256 .. 4096, h_s_lwe [n] with
+ * 1 <= n <= 65536, either may be NULL (not both); every coefficient must fit int16 as a signed word (binary keys and the bounded keys of tlwe / trlwe_new_bounded_key).
+ * Creation packs the TRLWE key's nonzero coefficients as a list of (position, value) and the LWE key as one int per coefficient; the image is copied to a device the
+ * first time a call runs there (one allocation, one synchronous copy, under the handle's lock) and stays for the handle's life.  Any number of host threads and
+ * contexts may share a handle.  A call that needs the key the handle lacks returns MOSFHET_HIP_EINVAL.
+ * mosfhet_hip_client_key_info: info = {N, n, nonzero coefficients of s_rlwe, s_rlwe binary (every coefficient 0 or 1)?, nonzero coefficients of s_lwe, s_lwe binary?}
+ * (N = 0 / n = 0: that key is missing).
+ *
+ * Samples, word for word (all arithmetic mod 2^64):
+ *   TLWE    out[i] = a_i for i < n, out[n] = sum_i a_i s_i + e + msg
+ *   TRLWE   out[0] = a uniform, out[1] = b = a * s + e + msg; the product is exact and negacyclic (X^N = -1); d_msg NULL = the zero polynomial
+ *   TRGSW   row q = c l + j (c < 2, j < l) of sample u is a fresh TRLWE(0); then m[u] 2^(64 - (j+1) Bg_bit) is added to coefficient e of component c -- AFTER b was formed
+ *           from the plain mask -- where X^exp[u] = +-X^e: exponent taken mod 2N (two's complement: -3 is 2N - 3), sign flipped for N <= exp mod 2N
+ *           (trgsw_new_monomial_sample; tests/client_reference.py).  d_exp NULL = all 0.  Gadget: 1 <= l <= 6, 1 <= Bg_bit <= 31, l * Bg_bit < 64, the rule of the
+ *           RAM and automaton calls.  d_out_torus [count][2l][2][N] words and / or d_out_dft [count][2l][2][N/2] complex in slot order: the selector layout of the
+ *           leveled calls, so `count` here is their count x size.  At least one output; with both, the doubles are the engine's forward transform
+ *           (mosfhet_hip_torus_to_dft_batch) of exactly the words in d_out_torus.  d_out_dft needs N in {1024, 2048, 4096}.
+ *
+ * Randomness: MASKS AND NOISE both come from ChaCha20 under the secret of mosfhet_hip_set_keygen_secret (below) -- unlike the key generators, whose masks come from a
+ * public seed: two encrypt calls that shared masks would publish the difference of their MESSAGES.  One block per (row, coefficient x), parameterised as the
+ * generators' noise: counter = (row << 16) | x, nonce = (call index << 8) | kind with kind 6: TLWE, 7: TRLWE, 8: TRGSW; the call index is the generators' counter, so
+ * no two calls of any kind share a nonce.  Output words 0 - 3 give the noise term exactly as the generators compute theirs; words 4 - 5 of the SAME block are the mask
+ * word (low word first).  TLWE: row = the sample's index, mask word i from block x = i, the one noise term from block x = 0.  TRLWE: row = the sample's index.  TRGSW: row =
+ * u 2l + q.  Launches are chunks of at most 2^20 rows; no word depends on the chunking, on the launch geometry, on count or on which outputs were asked for.  Like the
+ * generators' noise this is reproducible under an installed secret WITHIN a release (known answers: tests/test_client_samples.py).
+ * NO ENCRYPTION UNDER STREAM CAPTURE: the nonce is drawn when the call is made, so a replayed graph would encrypt again with the same masks and noise -- two samples
+ * whose difference is the bare difference of their messages.  The three encrypt calls query hipStreamIsCapturing and return MOSFHET_HIP_EINVAL ("capture") before
+ * anything is launched.
+ *
+ * Phases are exact, no transform: phase = b - sum_i a_i s_i, respectively b - a * s (tlwe_phase, trlwe_phase).  msg_bits = 0 returns the phases, msg_bits in 1 .. 63
+ * returns (phase + 2^(63 - msg_bits)) >> (64 - msg_bits), the message of msg_bits bits nearest to the phase; anything else is refused.  One launch, no pool, never
+ * synchronises: capturable from the first call after the key image is on the device.
+ *
+ * Every call: asynchronous on `stream` (the encrypt calls of a DFT-only TRGSW batch keep torus rows in the calling thread's pool, at most 1 GiB, chunk by chunk);
+ * count == 0 does nothing.  MOSFHET_HIP_EINVAL with a message naming the argument, before any launch: null ctx, key or buffer; the handle lacks the key; count < 0;
+ * gadget or msg_bits out of range; both TRGSW outputs NULL; an output overlapping an input (or the other output) as address ranges; a stream in capture (encryption).
+ * mosfhet_hip_trgsw_encrypt_plan says what the launcher will do, as a pure function (no GPU): with_torus_out 0 = d_out_dft only, 1 = both outputs, 2 = d_out_torus
+ * only; info = {launches, workgroups of the widest launch, workspace bytes (pool), chunks}. */
+typedef struct mosfhet_hip_client_key *mosfhet_hip_client_key_t;
+int mosfhet_hip_client_key_create(mosfhet_hip_client_key_t *out, const uint64_t *h_s_rlwe /*[N] or NULL*/, int N, const uint64_t *h_s_lwe /*[n] or NULL*/, int n);
+int mosfhet_hip_client_key_destroy(mosfhet_hip_client_key_t key);
+int mosfhet_hip_client_key_info(mosfhet_hip_client_key_t key, int64_t info[6]);
+int mosfhet_hip_tlwe_encrypt_batch(mosfhet_hip_ctx_t ctx, mosfhet_hip_client_key_t key, uint64_t *d_out /*[count][n+1]*/, const uint64_t *d_msg /*[count]*/, double sigma,
+                                   int count, void *stream);
+int mosfhet_hip_trlwe_encrypt_batch(mosfhet_hip_ctx_t ctx, mosfhet_hip_client_key_t key, uint64_t *d_out /*[count][2][N]*/, const uint64_t *d_msg /*[count][N] or NULL*/,
+                                    double sigma, int count, void *stream);
+int mosfhet_hip_trgsw_encrypt_batch(mosfhet_hip_ctx_t ctx, mosfhet_hip_client_key_t key, double *d_out_dft /*[count][2l][2][N/2] complex or NULL*/,
+                                    uint64_t *d_out_torus /*[count][2l][2][N] or NULL*/, const int32_t *d_m /*[count]*/, const int32_t *d_exp /*[count] or NULL*/, int l,
+                                    int Bg_bit, double sigma, int count, void *stream);
+int mosfhet_hip_trgsw_encrypt_plan(int N, int l, int count, int with_torus_out, int64_t info[4]);
+int mosfhet_hip_tlwe_phase_batch(mosfhet_hip_ctx_t ctx, mosfhet_hip_client_key_t key, uint64_t *d_out /*[count]*/, const uint64_t *d_in /*[count][n+1]*/, int msg_bits,
+                                 int count, void *stream);
+int mosfhet_hip_trlwe_phase_batch(mosfhet_hip_ctx_t ctx, mosfhet_hip_client_key_t key, uint64_t *d_out /*[count][N]*/, const uint64_t *d_in /*[count][2][N]*/, int msg_bits,
+                                  int count, void *stream);
+
 /* Key images for the on-disk formats (save_bootstrap_key / load_new_bootstrap_key src/bootstrap.c:63-104, trlwe_save_KS_key /
  * trlwe_load_new_KS_key src/keyswitch.c:122-160, tlwe_save_KS_key / tlwe_load_new_KS_key src/tlwe.c:247-287, trlwe_save_generic_ks_key /
  * trlwe_load_new_generic_ks_key src/keyswitch.c:409-455).  DFT-domain contents are backend-defined in the reference too (src/polynomial.c:336-357):
@@ -1045,7 +1104,11 @@ int mosfhet_hip_time_programmable_bootstrap(mosfhet_hip_ctx_t ctx, mosfhet_hip_b
  *     counter = (row << 16) | coefficient, nonce = (call index << 8) | kind -- the call index counts generate calls from 1 after the secret was installed;
  *     kind 1: table keys (packing, private, LUT packing), 2: bootstrap keys, 3: unfolded bootstrap keys, 4: FFT key-switch key sets, 5: LWE tables.
  *     Output words 0 - 3 are two 64-bit uniforms (low word first), u = ((w >> 11) + 0.5) 2^-53, the term is cos(2 pi u1) sqrt(-2 ln u2) sigma 2^64
- *     truncated towards zero (evaluated in double: within 2^-48 sigma of the exact value). */
+ *     truncated towards zero (evaluated in double: within 2^-48 sigma of the exact value).
+ *   - The ENCRYPT calls of the client half (mosfhet_hip_tlwe_encrypt_batch, _trlwe_, _trgsw_, above) draw on the same secret and the same call counter with kinds 6
+ *     (TLWE), 7 (TRLWE) and 8 (TRGSW): noise from words 0 - 3 as here, and -- unlike the generators -- their MASKS from words 4 - 5 of the same block (low word
+ *     first), so their masks are secret-derived and never repeat between calls.  TLWE: row = sample, mask word i from coefficient i, the noise term from coefficient 0;
+ *     TRLWE: row = sample; TRGSW: row = sample * 2l + c * l + j.  Reproducible within a release, like the noise. */
 int mosfhet_hip_set_keygen_secret(const void *key32);
 
 /* ---- DFT-level entry points behind the reference's legacy signatures (mosfhet.h:179-182,263-264,342-344,454,296 of the reference; csrc/capi_dft.inc).

@@ -29,6 +29,7 @@
 #include "linear_kernels.h"
 #include "pack_kernels.h"
 #include "trace_kernels.h"
+#include "client_kernels.h"
 
 using namespace mosfhet;
 
@@ -80,7 +81,7 @@ struct DevBuf {
 // handle: handles are read-only after creation, so any number of host threads may share them, as the reference's callers share its keys
 // (re-entrant through thread-local scratch, src/polynomial.c:269-352).  A thread's launches are ordered by the stream it passes; buffers are
 // released at thread exit (hipFree waits for work in flight).
-enum { POOL_BSK = 0, POOL_EXT0 = 1, POOL_EXT1 = 2, POOL_CTX0 = 3, POOL_UNFOLD = 6, POOL_PACK = 7, POOL_VEC = 8, POOL_VEC2 = 9, POOL_VEC3 = 10, POOL_VEC4 = 11, POOL_LUT = 12, POOL_BITS = 13, POOL_LINEAR = 14, POOL_LINEAR_OUT = 15, POOL_PACK_COLS = 16, POOL_PACK_PARTS = 17, POOL_UNPACK = 18, POOL_TRACE_MANY = 19, POOL_POLYLINEAR = 20, POOL_POLYLINEAR_OUT = 21, POOL_GSWLINEAR = 22, POOL_RAM = 23, POOL_AUTOMATON = 24, POOL_SLOTS = 25 };
+enum { POOL_BSK = 0, POOL_EXT0 = 1, POOL_EXT1 = 2, POOL_CTX0 = 3, POOL_UNFOLD = 6, POOL_PACK = 7, POOL_VEC = 8, POOL_VEC2 = 9, POOL_VEC3 = 10, POOL_VEC4 = 11, POOL_LUT = 12, POOL_BITS = 13, POOL_LINEAR = 14, POOL_LINEAR_OUT = 15, POOL_PACK_COLS = 16, POOL_PACK_PARTS = 17, POOL_UNPACK = 18, POOL_TRACE_MANY = 19, POOL_POLYLINEAR = 20, POOL_POLYLINEAR_OUT = 21, POOL_GSWLINEAR = 22, POOL_RAM = 23, POOL_AUTOMATON = 24, POOL_CLIENT = 25, POOL_SLOTS = 26 };
 struct ThreadPool {
   struct Dev {
     int device = -1;
@@ -1820,3 +1821,4 @@ extern "C" int mosfhet_hip_time_programmable_bootstrap(mosfhet_hip_ctx_t ctx, mo
 #include "capi_ram.inc"
 #include "capi_automaton.inc"
 #include "capi_sellogic.inc"
+#include "capi_client.inc"

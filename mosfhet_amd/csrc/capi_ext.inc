@@ -978,7 +978,7 @@ extern "C" int mosfhet_hip_trlwe_ksk_generate(mosfhet_hip_ctx_t ctx, mosfhet_hip
   HIP_TRY(hipMemcpy(d_keys, h_s_out, (size_t)N * sizeof(uint64_t), hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(d_keys + N, h_msgs, (size_t)entries * N * sizeof(uint64_t), hipMemcpyHostToDevice));
   hipLaunchKernelGGL(trlwe_poly_keygen_kernel, dim3((unsigned)n_rows), dim3(256), (size_t)N * sizeof(uint64_t) + (size_t)N * 2 * sizeof(uint16_t), nullptr,
-                     rows.as<uint64_t>(), d_keys, d_keys + N, N, t, base_bit, sigma, seed, noise_key_for_call(NOISE_TRLWE_KSK));
+                     rows.as<uint64_t>(), d_keys, d_keys + N, N, t, base_bit, sigma, seed, noise_key_for_call(NOISE_TRLWE_KSK), ClientParams{});
   RING_DISPATCH(ctx, N, hipLaunchKernelGGL(torus_to_dft_kernel<F>, dim3((unsigned)polys), dim3(F::THREADS), 0, nullptr, rows.as<uint64_t>(), g->d_ak, TW));
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(nullptr));
@@ -1010,7 +1010,7 @@ extern "C" int mosfhet_hip_tlwe_ksk_generate(mosfhet_hip_ctx_t ctx, mosfhet_hip_
   for (size_t first = 0; first < n_rows; first += 1u << 20) {
     const size_t chunk = n_rows - first < (1u << 20) ? n_rows - first : (1u << 20);
     hipLaunchKernelGGL(tlwe_ksk_keygen_kernel, dim3((unsigned)chunk), dim3(64), 0, nullptr, k->d_ksk, d_keys, d_keys + n_out, n_out, t, base_bit, sigma, seed, first,
-                       compressed, nkey);
+                       compressed, nkey, ClientParams{});
   }
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(nullptr));

@@ -59,6 +59,23 @@ __device__ __forceinline__ uint64_t keygen_noise(const NoiseKey &key, uint64_t r
   return (uint64_t)(int64_t)(18446744073709551616.0 * z);
 }
 
+// The client half (client_kernels.h: samples encrypted and opened under a secret-key handle) runs as RUN-TIME KINDS of two kernels of this file, no kernel of its own:
+// kinds 1 (TRLWE / TRGSW rows) and 2 (TRLWE phases) in trlwe_poly_keygen_kernel -- one workgroup of 256 threads per row over dynamic LDS, as its own rows -- and kinds
+// 3 (TLWE samples) and 4 (TLWE phases) in tlwe_ksk_keygen_kernel, one wavefront per sample.  kind 0: the generator itself, every word as before.
+struct ClientParams {
+  int kind;
+  uint64_t *out;           // 1: [rows][2][N] (rows_first = the row stored at out[0]); 2: [count][N]; 3: [count][n + 1]; 4: [count]
+  const uint64_t *in;      // 1: [rows][N] message polynomials or null (TRLWE); 2, 4: the samples; 3: [count] message words
+  const int32_t *m, *exp;  // 1, TRGSW (l > 0): [samples] messages, [samples] exponents or null
+  const int *key;          // 1, 2: the TRLWE key's nonzero coefficients, (value << 16) | position; 3, 4: the LWE key, one int per coefficient
+  int cnt, binary, N, l, Bg_bit, msg_bits;   // N: the ring degree (1, 2) or the LWE length (3, 4)
+  double sigma;
+  size_t first_row;        // row number of blockIdx.x = 0 (the ChaCha20 counter's row)
+  size_t rows_first;       // 1: row number stored at out[0]
+};
+__device__ __forceinline__ void client_ring_body(const ClientParams &p, const NoiseKey &nkey, uint64_t *ext /*dynamic LDS, [2N]*/);
+__device__ __forceinline__ void client_lwe_body(const ClientParams &p, const NoiseKey &nkey);
+
 // kind 0 (packing): rows (i < n, j < t, v in 1..2^bb-1), message = s_in[i] v 2^(64-(j+1)bb) on X^0
 // kind 1 (private): rows (i <= n, ...), message polynomial = -s_out * (s_i v 2^(64-(j+1)bb)), s_n = -1
 // kind 2 (LUT packing, trlwe_new_packing_KS_key, src/keyswitch.c:214-241): rows ((i, e) with i < n, e < slots; j; v), message = s_in[i] v 2^(64-(j+1)bb) on
@@ -216,8 +233,9 @@ __global__ __launch_bounds__(256) void trgsw_bk_keygen_k_kernel(uint64_t *__rest
 // pair, :39-50; the relinearisation key, :3-10 -- they differ only in the polynomial being switched from): entry e, row r < t is
 // TRLWE_{s_out}(msg_e(X) * 2^(64 - (r+1) bb)).  One workgroup per row; the caller transforms the rows afterwards.
 __global__ __launch_bounds__(256) void trlwe_poly_keygen_kernel(uint64_t *__restrict__ rows, const uint64_t *__restrict__ s_out, const uint64_t *__restrict__ msgs,
-                                                              int N, int t, int base_bit, double sigma, uint64_t seed, NoiseKey nkey) {
+                                                              int N, int t, int base_bit, double sigma, uint64_t seed, NoiseKey nkey, ClientParams client) {
   extern __shared__ uint64_t sh[];
+  if (client.kind) { client_ring_body(client, nkey, sh); return; }   // (launch-uniform: the client half's rows and phases, client_kernels.h)
   uint64_t *a = sh;
   uint16_t *ones = reinterpret_cast<uint16_t *>(sh + N);
   int16_t *vals = reinterpret_cast<int16_t *>(ones + N);   // the key's nonzero coefficients (binary keys: all 1; bounded keys: small integers)
@@ -274,7 +292,9 @@ __global__ __launch_bounds__(256) void table_expand_kernel(uint64_t *__restrict_
 // LWE -> LWE key-switch table (tlwe_new_KS_key, src/tlwe.c:193-212): row (i, j, v) = TLWE_{s_out}(s_in[i] v 2^(64 - (j+1) bb)), a uniform from the
 // counter-based generator, b = <a, s_out> + e + message.  One wavefront per row.  compressed: only b is stored ([rows] words).
 __global__ __launch_bounds__(64) void tlwe_ksk_keygen_kernel(uint64_t *__restrict__ rows, const uint64_t *__restrict__ s_out, const uint64_t *__restrict__ s_in,
-                                                            int n_out, int t, int base_bit, double sigma, uint64_t seed, size_t first_row, int compressed, NoiseKey nkey) {
+                                                            int n_out, int t, int base_bit, double sigma, uint64_t seed, size_t first_row, int compressed, NoiseKey nkey,
+                                                            ClientParams client) {
+  if (client.kind) { client_lwe_body(client, nkey); return; }   // (launch-uniform: the client half's TLWE samples and phases, client_kernels.h)
   const size_t r = first_row + blockIdx.x;
   const int cands = (1 << base_bit) - 1, lane = threadIdx.x;
   const int v = (int)(r % cands) + 1, j = (int)((r / cands) % t);

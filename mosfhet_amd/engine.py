@@ -237,6 +237,49 @@ def sellogic_create(gates, n_in, N):
     return SelLogic(h)
 
 
+TRGSW_ENCRYPT_OUTPUTS = ("dft", "both", "torus")    # with_torus_out of mosfhet_hip_trgsw_encrypt_plan
+
+
+def trgsw_encrypt_plan(N, l, count, outputs="dft"):
+    """What a trgsw_encrypt call will do (no device needed): dict(launches, workgroups, workspace_bytes, chunks) -- kernel launches (a row launch and, with a DFT
+    output, a transform per chunk of at most 2^20 rows), workgroups of the widest launch, bytes of pooled torus rows (DFT-only calls) and chunks.  outputs: "dft",
+    "both" or "torus".  include/mosfhet_hip.h: mosfhet_hip_trgsw_encrypt_plan."""
+    info = (C.c_int64 * 4)()
+    _check(lib().mosfhet_hip_trgsw_encrypt_plan(int(N), int(l), int(count), TRGSW_ENCRYPT_OUTPUTS.index(outputs), info))
+    return dict(launches=int(info[0]), workgroups=int(info[1]), workspace_bytes=int(info[2]), chunks=int(info[3]))
+
+
+class ClientKey:
+    """Secret keys for the encrypt and phase calls (mosfhet_hip_client_key_t): made by client_key_create, shared by every engine, call and host thread."""
+
+    def __init__(self, handle):
+        self.h = handle
+        v = (C.c_int64 * 6)()
+        _check(lib().mosfhet_hip_client_key_info(self.h, v))
+        self.N, self.n, self.rlwe_weight, self.lwe_weight = int(v[0]), int(v[1]), int(v[2]), int(v[4])
+        self.rlwe_binary, self.lwe_binary = bool(v[3]), bool(v[5])
+
+    def info(self):
+        return dict(N=self.N, n=self.n, rlwe_weight=self.rlwe_weight, rlwe_binary=self.rlwe_binary, lwe_weight=self.lwe_weight, lwe_binary=self.lwe_binary)
+
+    def close(self):
+        if self.h:
+            lib().mosfhet_hip_client_key_destroy(self.h)
+            self.h = None
+
+    free = close
+
+
+def client_key_create(s_rlwe=None, s_lwe=None):
+    """A ClientKey from host keys (no device needed: the packed key is copied to a device by the first call that runs there).  s_rlwe: [N] words, N a power of two in
+    256 .. 4096; s_lwe: [n] words; either may be None; coefficients are binary or small signed integers (they must fit 16 bits)."""
+    keys = [None if s is None else np.ascontiguousarray(s, dtype=np.uint64).reshape(-1) for s in (s_rlwe, s_lwe)]
+    ptr = [None if s is None else s.ctypes.data_as(C.c_void_p) for s in keys]
+    h = C.c_void_p()
+    _check(lib().mosfhet_hip_client_key_create(C.byref(h), ptr[0], 0 if keys[0] is None else int(keys[0].size), ptr[1], 0 if keys[1] is None else int(keys[1].size)))
+    return ClientKey(h)
+
+
 def lut_bits_packed_plan(N, l, size, tables, pack_log, count, cus=256):
     """What a lut_bits_packed call will do (no device needed): lut_bits_plan's dict with leveled_lut_packed_plan's dict for one chunk as `lut`.
     include/mosfhet_hip.h: mosfhet_hip_lut_bits_packed_plan."""
@@ -1078,6 +1121,66 @@ class Engine:
     def trgsw_logic_plan(self, N, l, n_in, n_gates, levels, widest_level, count):
         """trgsw_logic_plan() at this device's CU count."""
         return trgsw_logic_plan(N, l, n_in, n_gates, levels, widest_level, count, self.torch.cuda.get_device_properties(self.device).multi_processor_count)
+
+    # ---- the client half: encrypt and open samples under a ClientKey (include/mosfhet_hip.h "The client half on the device") ----
+    def tlwe_encrypt(self, key, msg, sigma, out=None):
+        """TLWE samples of the torus words msg [count] under key's LWE key: [count][n + 1], out[i] = a_i, out[n] = sum a_i s_i + e + msg.  Masks and noise from
+        ChaCha20 under the keygen secret, one nonce per call; refused on a capturing stream."""
+        count = msg.shape[0]
+        assert tuple(msg.shape) == (count,) and msg.dtype == self.torch.int64, tuple(msg.shape)
+        if out is None:
+            out = self.empty(count, key.n + 1)
+        assert tuple(out.shape) == (count, key.n + 1), tuple(out.shape)
+        _check(lib().mosfhet_hip_tlwe_encrypt_batch(self.h, key.h, _ptr(out) if count else None, _ptr(msg) if count else None, C.c_double(sigma), int(count), self._stream()))
+        return out
+
+    def trlwe_encrypt(self, key, msg, sigma, count=None, out=None):
+        """TRLWE samples of the polynomials msg [count][N] (None: `count` samples of zero) under key's TRLWE key: [count][2][N], b = a * s + e + msg, the product
+        exact.  Randomness and capture rule as for tlwe_encrypt."""
+        if msg is not None:
+            count = msg.shape[0]
+            assert tuple(msg.shape) == (count, key.N) and msg.dtype == self.torch.int64, tuple(msg.shape)
+        if out is None:
+            out = self.empty(count, 2, key.N)
+        assert tuple(out.shape) == (count, 2, key.N), tuple(out.shape)
+        _check(lib().mosfhet_hip_trlwe_encrypt_batch(self.h, key.h, _ptr(out) if count else None, _ptr(msg) if msg is not None and count else None, C.c_double(sigma),
+                                                     int(count), self._stream()))
+        return out
+
+    def trgsw_encrypt(self, key, m, l, Bg_bit, sigma, exp=None, torus=False, dft=True):
+        """TRGSW samples of m[u] X^exp[u] (trgsw_monomial_sample; exp None: X^0) under key's TRLWE key.  m, exp: int32 tensors of one shape, e.g. [count][size] for
+        the leveled calls' selectors.  Returns the TRGSW_DFT samples, shape + [2l][2][N] float64 (the sel_dft layout); torus=True: (dft, torus rows shape + [2l][2][N]
+        int64), the doubles being torus_to_dft of exactly those rows; dft=False (with torus=True): the torus rows only.  Randomness and capture rule as for
+        tlwe_encrypt."""
+        assert dft or torus
+        assert m.dtype == self.torch.int32 and (exp is None or (exp.dtype == self.torch.int32 and exp.shape == m.shape)), (m.dtype, m.shape)
+        shape, count, N = tuple(m.shape), m.numel(), key.N
+        d = self.torch.empty(shape + (2 * l, 2, N), dtype=self.torch.float64, device=self.device) if dft else None
+        t = self.empty(*(shape + (2 * l, 2, N))) if torus else None
+        _check(lib().mosfhet_hip_trgsw_encrypt_batch(self.h, key.h, _ptr(d) if dft and count else None, _ptr(t) if torus and count else None, _ptr(m) if count else None,
+                                                     _ptr(exp) if exp is not None and count else None, int(l), int(Bg_bit), C.c_double(sigma), int(count), self._stream()))
+        return (d, t) if dft and torus else (d if dft else t)
+
+    def tlwe_phase(self, key, ct, msg_bits=0, out=None):
+        """Phases b - sum a_i s_i of the TLWE samples ct [count][n + 1], exact: [count] words; msg_bits in 1 .. 63: the messages of that many bits nearest to them,
+        (phase + 2^(63 - msg_bits)) >> (64 - msg_bits)."""
+        count = ct.shape[0]
+        assert tuple(ct.shape) == (count, key.n + 1), tuple(ct.shape)
+        if out is None:
+            out = self.empty(count)
+        assert tuple(out.shape) == (count,), tuple(out.shape)
+        _check(lib().mosfhet_hip_tlwe_phase_batch(self.h, key.h, _ptr(out) if count else None, _ptr(ct) if count else None, int(msg_bits), int(count), self._stream()))
+        return out
+
+    def trlwe_phase(self, key, ct, msg_bits=0, out=None):
+        """Phases b - a * s of the TRLWE samples ct [count][2][N], exact (no transform): [count][N] words; msg_bits as for tlwe_phase."""
+        count = ct.shape[0]
+        assert tuple(ct.shape) == (count, 2, key.N), tuple(ct.shape)
+        if out is None:
+            out = self.empty(count, key.N)
+        assert tuple(out.shape) == (count, key.N), tuple(out.shape)
+        _check(lib().mosfhet_hip_trlwe_phase_batch(self.h, key.h, _ptr(out) if count else None, _ptr(ct) if count else None, int(msg_bits), int(count), self._stream()))
+        return out
 
     def leveled_lut_packed_plan(self, N, l, size, tables, pack_log, count):
         """leveled_lut_packed_plan() at this device's CU count."""
