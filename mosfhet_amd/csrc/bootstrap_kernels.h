@@ -421,6 +421,127 @@ __global__ __launch_bounds__(F::THREADS * G, 2) void pbs_group_kernel(PbsParams 
 }
 
 // ------------------------------------------------------------------------------------------------------------
+// Steps of the kernels that keep the WHOLE accumulator in LDS as acc[2][N] -- the latency family (pbs_team / pbs_wide_team / pbs_wide_pair_kernel), the two-CU
+// family (pbs_ga_split_kernel; pbs_split_kernel states the same steps in its own text, see there) and the Galois pair (pbs_ga_wide_kernel, and pbs_ga_kernel
+// for the generator schedule) -- each defined ONCE, by the rule of cmux_steps.h: these kernels are bit-identical to each other and to the oracle because they
+// run the same steps.
+// WG: threads of the workgroup, tid: the thread's index in it; T = F::THREADS: threads of a transform team, t: the thread's index in its team.
+// ------------------------------------------------------------------------------------------------------------
+// accumulator fill of a blind rotation on a caller-supplied accumulator (p.skip_init): the TRLWE sample at `src`, as it is
+template <int N, int WG>
+__device__ __forceinline__ void acc_copy_in(uint64_t *acc, const uint64_t *src, int tid) {
+  for (int x = tid; x < 2 * N; x += WG) acc[x] = src[x];
+}
+// the test vector of workgroup b: its own or the one shared by the batch; with TRGSW accumulators (p.rows > 1, see PbsParams) row b % rows of the shared set
+template <int N>
+__device__ __forceinline__ const uint64_t *test_vector(const PbsParams &p, size_t b) {
+  return p.rows > 1 ? p.tv + (b % (size_t)p.rows) * (size_t)(2 * N) : p.tv + b * (size_t)p.tv_stride;
+}
+// accumulator fill of a bootstrap: acc = tv * X^(2N - bbar), bbar the switched body word (src/bootstrap.c:192-195, src/bootstrap_ga.c:64-65)
+template <int N, int WG>
+__device__ __forceinline__ void acc_rotate_in(uint64_t *acc, const uint64_t *__restrict__ tv, uint32_t bbar, int tid) {
+  const auto [a_lo, flip] = first_rotation(bbar, N);
+  for (int x = tid; x < 2 * N; x += WG) acc[x] = rot_coeff<N>(tv + (x / N) * N, x & (N - 1), a_lo, flip);
+}
+// accumulator write-out: the TLWE sample extracted at 0 (p.extract; src/trlwe.c:540-552 at idx = 0: the mask comes from component 0, the body from component 1)
+// or the rotated TRLWE sample.  A workgroup of a two-CU pair writes the components it holds (mine0, mine1).
+template <int N, int WG>
+__device__ __forceinline__ void acc_write_out(const PbsParams &p, size_t b, const uint64_t *acc, int tid, bool mine0 = true, bool mine1 = true) {
+  if (p.extract) {
+    uint64_t *dst = p.out + b * (size_t)(N + 1);
+    if (mine0) for (int j = tid; j < N; j += WG) dst[j] = extract0_coeff(acc, j, N);
+    if (mine1 && tid == 0) dst[N] = acc[N];
+  } else {
+    uint64_t *dst = p.out + b * (size_t)(2 * N);
+    for (int x = tid; x < 2 * N; x += WG)
+      if (x < N ? mine0 : mine1) dst[x] = acc[x];
+  }
+}
+// The word the digits of coefficient j are cut from in a CMUX step: ((X^a - 1) acc)[j] + off (src/polynomial.c:220-235, 74-89) ...
+template <int N>
+__device__ __forceinline__ uint64_t rotated_difference(const uint64_t *acc, int j, Rotation rot, uint64_t off) {
+  return rot_coeff<N>(acc, j, rot.a_lo, rot.flip) - acc[j] + off;
+}
+// ... and the digit of one level as a double (exact): the field at `shift` = 64 - (level + 1) Bg_bit, masked, re-centred by half = 2^(Bg_bit - 1).  Digits of
+// a product that does not rotate (the Galois kernels) are cut from acc[j] + off.
+__device__ __forceinline__ double digit_field(uint64_t word, int shift, uint32_t mask, int half) {
+  return (double)((int)((uint32_t)(word >> shift) & mask) - half);
+}
+// o += chain over four consecutive key rows of a product: the double phase of pbs_wide_pair_kernel (which see).  `rows`: this team's output component of the
+// first row, lane offset included, all four requested before the transforms; `digits(xr, xi, yr, yi)` fills this team's two digit polynomials -- rows `team` (x)
+// and 2 + team (y) of the four; hand[4][M]: hand-over buffer r holds row r.  The fma chain runs in row order: the x rows (0, 1) while the y rows land, then,
+// behind a barrier, rows 2 and 3.  The barrier that frees the hand-over buffers again is the caller's.
+template <class F, class D>
+__device__ __forceinline__ void double_phase(double (&o_re)[8], double (&o_im)[8], const d2 *rows, d2 *hand, d2 *xch, const F &fft, int team, int t,
+                                             D digits) {
+  constexpr int M = F::M, T = F::THREADS;
+  d2 kk[4][8];
+#pragma unroll
+  for (int r = 0; r < 4; r++)
+#pragma unroll
+    for (int m = 0; m < 8; m++) kk[r][m] = rows[(size_t)r * (2 * M) + m * T];
+  double xr[8], xi[8], yr[8], yi[8];
+  digits(xr, xi, yr, yi);
+  fft.forward2_head(xr, xi, yr, yi, xch, t);
+  fft.pass_d_fwd(xr, xi);
+  d2 *hx = hand + (size_t)team * M, *hy = hand + (size_t)(2 + team) * M;
+#pragma unroll
+  for (int m = 0; m < 8; m++) hx[m * T + t] = d2{xr[m], xi[m]};
+  fft.forward2_fetch(yr, yi, xch, t);
+  fft.pass_d_fwd(yr, yi);
+  F::forward2_done();   // (a workgroup barrier: both teams' x rows are handed over)
+#pragma unroll
+  for (int m = 0; m < 8; m++) hy[m * T + t] = d2{yr[m], yi[m]};
+#pragma unroll
+  for (int r = 0; r < 4; r++) {
+    if (r == 2) workgroup_sync();   // (both teams' y rows are handed over)
+    const d2 *__restrict__ dr = hand + (size_t)r * M;
+#pragma unroll
+    for (int m = 0; m < 8; m++) {
+      const d2 d = dr[m * T + t], k = kk[r][m];
+      cmac(o_re[m], o_im[m], d.x, d.y, k);
+    }
+  }
+}
+// The three ways a product reaches the accumulator component `accw` of the team that holds it in o_re / o_im: the inverse transform (workgroup barriers inside
+// F's: a team that sits it out walks F::transform_barriers_only()), the rounding to Torus64, and
+//   PRODUCT_ADD        accw += result: a CMUX step (src/trlwe.c:629-634, 437-439);
+//   PRODUCT_REPLACE    accw = result: the external product of a Galois step (src/bootstrap_ga.c:50);
+//   PRODUCT_KEYSWITCH  the key switch of an automorphism, as(a) = the product of the permuted a's digits with the key entry: a = -as(a) (team 0),
+//                      b = b - as(a) (team 1) [src/trlwe.c:775-781, src/keyswitch.c:162-193].
+// Macros for GADGET_OFFSET's reason (cmux_steps.h): as functions they are optimised on their own first and their callers compile to other, if equivalent, code
+// (the operands of add_rounded's sum change places, and with them the register allocation of the whole kernel).  M, T: F::M, F::THREADS; `accw` and `m` live in
+// the macros' own block.  Undefined again at the end of this header.
+#define PRODUCT_WORDS_(RE_, IM_)                  \
+  _Pragma("unroll") for (int m = 0; m < 8; m++) { \
+    RE_;                                          \
+    IM_;                                          \
+  }
+#define PRODUCT_ADD(REDUCE, M, T, accw_, o_re, o_im, xch_, fft, scale, t)                                  \
+  do {                                                                                                     \
+    (fft).inverse(o_re, o_im, xch_, t);                                                                    \
+    uint64_t *accw = (accw_);                                                                              \
+    PRODUCT_WORDS_(accw[m * (T) + (t)] = add_rounded<REDUCE>(accw[m * (T) + (t)], (o_re)[m], scale),       \
+                   accw[(M) + m * (T) + (t)] = add_rounded<REDUCE>(accw[(M) + m * (T) + (t)], (o_im)[m], scale)) \
+  } while (0)
+#define PRODUCT_REPLACE(M, T, accw_, o_re, o_im, xch_, fft, scale, t)                                                                        \
+  do {                                                                                                                                       \
+    (fft).inverse(o_re, o_im, xch_, t);                                                                                                      \
+    uint64_t *accw = (accw_);                                                                                                                \
+    PRODUCT_WORDS_(accw[m * (T) + (t)] = round_mod_2_64((o_re)[m], scale), accw[(M) + m * (T) + (t)] = round_mod_2_64((o_im)[m], scale))     \
+  } while (0)
+#define PRODUCT_KEYSWITCH(M, T, accw_, team, o_re, o_im, xch_, fft, scale, t)                                                                        \
+  do {                                                                                                                                               \
+    (fft).inverse(o_re, o_im, xch_, t);                                                                                                              \
+    uint64_t *accw = (accw_);                                                                                                                        \
+    if ((team) == 0) {                                                                                                                               \
+      PRODUCT_WORDS_(accw[m * (T) + (t)] = 0 - round_mod_2_64((o_re)[m], scale), accw[(M) + m * (T) + (t)] = 0 - round_mod_2_64((o_im)[m], scale))   \
+    } else {                                                                                                                                         \
+      PRODUCT_WORDS_(accw[m * (T) + (t)] -= round_mod_2_64((o_re)[m], scale), accw[(M) + m * (T) + (t)] -= round_mod_2_64((o_im)[m], scale))         \
+    }                                                                                                                                                \
+  } while (0)
+
+// ------------------------------------------------------------------------------------------------------------
 // Latency-oriented variant for SMALL batches (fewer ciphertexts than the chip has CUs x 8): one workgroup of 2L wavefronts per
 // ciphertext, wavefront w owns TRGSW row w of every CMUX (its digits, its forward transform), then wavefronts 0 and 1 run the
 // multiply-accumulate over all rows -- in row order, the same fma chain as pbs_kernel and the oracle, so results are bit-identical --
@@ -443,15 +564,8 @@ __global__ __launch_bounds__(64 * 2 * L) void pbs_team_kernel(PbsParams p) {
   const int Bg_bit = BG > 0 ? BG : p.Bg_bit;
   F fft;
   fft.init(p.tw, t);
-  if (p.skip_init) {
-    const uint64_t *src = p.out + b * (size_t)(2 * N);
-    for (int x = tid; x < 2 * N; x += TEAM) acc[x >> 10][x & (N - 1)] = src[x];
-  } else {
-    const uint64_t *__restrict__ tv = p.tv + b * (size_t)p.tv_stride;
-    const uint32_t bbar = modswitch<LOG2N2>(pbs_pre(ct[p.n], p, LOG2N2) + p.prec_offset);
-    const auto [a_lo, flip] = first_rotation(bbar, N);
-    for (int x = tid; x < 2 * N; x += TEAM) acc[x >> 10][x & (N - 1)] = rot_coeff<N>(tv + (x >> 10) * N, x & (N - 1), a_lo, flip);
-  }
+  if (p.skip_init) acc_copy_in<N, TEAM>(&acc[0][0], p.out + b * (size_t)(2 * N), tid);
+  else acc_rotate_in<N, TEAM>(&acc[0][0], p.tv + b * (size_t)p.tv_stride, modswitch<LOG2N2>(pbs_pre(ct[p.n], p, LOG2N2) + p.prec_offset), tid);
   workgroup_sync();
   const uint64_t off = GADGET_OFFSET(L, Bg_bit);
   const RoundCtx scale = round_scale<M>();
@@ -463,7 +577,7 @@ __global__ __launch_bounds__(64 * 2 * L) void pbs_team_kernel(PbsParams p) {
     const int abar = (int)modswitch<LOG2N2>(pbs_pre(ct[i], p, LOG2N2));
     if (!abar) continue;   // src/bootstrap.c:114 (uniform over the workgroup)
     const d2 *__restrict__ bkrow = p.bk + (size_t)i * row_sz;
-    const auto [a_lo, flip] = split_rotation(abar, N);
+    const Rotation rot = split_rotation(abar, N);
     // wavefronts 0 and 1 fetch their component of all R key rows now, under the digit extraction and the forward transform
     d2 kk[R][8];
     if (w < 2) {
@@ -476,10 +590,9 @@ __global__ __launch_bounds__(64 * 2 * L) void pbs_team_kernel(PbsParams p) {
 #pragma unroll
     for (int m = 0; m < 8; m++) {
       const int j = m * T + t;
-      const uint64_t d_lo = rot_coeff<N>(acc[q], j, a_lo, flip) - acc[q][j] + off;
-      const uint64_t d_hi = rot_coeff<N>(acc[q], j + M, a_lo, flip) - acc[q][j + M] + off;
-      re[m] = (double)((int)((uint32_t)(d_lo >> shift) & mask) - half);
-      im[m] = (double)((int)((uint32_t)(d_hi >> shift) & mask) - half);
+      const uint64_t d_lo = rotated_difference<N>(acc[q], j, rot, off), d_hi = rotated_difference<N>(acc[q], j + M, rot, off);
+      re[m] = digit_field(d_lo, shift, mask, half);
+      im[m] = digit_field(d_hi, shift, mask, half);
     }
     fft.forward(re, im, xch[w], t);
 #pragma unroll
@@ -497,24 +610,11 @@ __global__ __launch_bounds__(64 * 2 * L) void pbs_team_kernel(PbsParams p) {
           cmac(o_re[m], o_im[m], d.x, d.y, k);
         }
       }
-      fft.inverse(o_re, o_im, xinv[w], t);
-#pragma unroll
-      for (int m = 0; m < 8; m++) {
-        acc[w][m * T + t] = add_rounded<kReduce>(acc[w][m * T + t], o_re[m], scale);
-        acc[w][M + m * T + t] = add_rounded<kReduce>(acc[w][M + m * T + t], o_im[m], scale);
-      }
+      PRODUCT_ADD(kReduce, M, T, acc[w], o_re, o_im, xinv[w], fft, scale, t);
     }
     workgroup_sync();
   }
-  if (p.extract) {
-    // src/trlwe.c:540-552 at idx = 0
-    uint64_t *dst = p.out + b * (size_t)(N + 1);
-    for (int j = tid; j < N; j += TEAM) dst[j] = extract0_coeff(acc[0], j, N);
-    if (tid == 0) dst[N] = acc[1][0];
-  } else {
-    uint64_t *dst = p.out + b * (size_t)(2 * N);
-    for (int x = tid; x < 2 * N; x += TEAM) dst[x] = acc[x >> 10][x & (N - 1)];
-  }
+  acc_write_out<N, TEAM>(p, b, &acc[0][0], tid);
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -548,15 +648,8 @@ __global__ __launch_bounds__(F::THREADS * WideTeams<L>::value) void pbs_wide_tea
   const int Bg_bit = BG > 0 ? BG : p.Bg_bit;
   F fft;
   fft.init(p.tw, t);
-  if (p.skip_init) {
-    const uint64_t *src = p.out + b * (size_t)(2 * N);
-    for (int x = tid; x < 2 * N; x += WG) acc[x] = src[x];
-  } else {
-    const uint64_t *__restrict__ tv = p.rows > 1 ? p.tv + (b % (size_t)p.rows) * (size_t)(2 * N) : p.tv + b * (size_t)p.tv_stride;
-    const uint32_t bbar = modswitch<LOG2N2>(pbs_pre(ct[p.n], p, LOG2N2) + p.prec_offset);
-    const auto [a_lo, flip] = first_rotation(bbar, N);
-    for (int x = tid; x < 2 * N; x += WG) acc[x] = rot_coeff<N>(tv + (x / N) * N, x & (N - 1), a_lo, flip);
-  }
+  if (p.skip_init) acc_copy_in<N, WG>(acc, p.out + b * (size_t)(2 * N), tid);
+  else acc_rotate_in<N, WG>(acc, test_vector<N>(p, b), modswitch<LOG2N2>(pbs_pre(ct[p.n], p, LOG2N2) + p.prec_offset), tid);
   workgroup_sync();
   const uint64_t off = GADGET_OFFSET(L, Bg_bit);
   const RoundCtx scale = round_scale<M>();
@@ -568,7 +661,7 @@ __global__ __launch_bounds__(F::THREADS * WideTeams<L>::value) void pbs_wide_tea
     const int abar = (int)modswitch<LOG2N2>(pbs_pre(ct[i], p, LOG2N2));
     if (!abar) continue;   // src/bootstrap.c:114 (uniform over the workgroup)
     const d2 *__restrict__ bkrow = p.bk + (size_t)i * row_sz;
-    const auto [a_lo, flip] = split_rotation(abar, N);
+    const Rotation rot = split_rotation(abar, N);
     double o_re[8], o_im[8];
 #pragma unroll
     for (int m = 0; m < 8; m++) { o_re[m] = 0.0; o_im[m] = 0.0; }
@@ -597,10 +690,9 @@ __global__ __launch_bounds__(F::THREADS * WideTeams<L>::value) void pbs_wide_tea
 #pragma unroll
         for (int m = 0; m < 8; m++) {
           const int j = m * T + t;
-          const uint64_t d_lo = rot_coeff<N>(accq, j, a_lo, flip) - accq[j] + off;
-          const uint64_t d_hi = rot_coeff<N>(accq, j + M, a_lo, flip) - accq[j + M] + off;
-          re[m] = (double)((int)((uint32_t)(d_lo >> shift) & mask) - half);
-          im[m] = (double)((int)((uint32_t)(d_hi >> shift) & mask) - half);
+          const uint64_t d_lo = rotated_difference<N>(accq, j, rot, off), d_hi = rotated_difference<N>(accq, j + M, rot, off);
+          re[m] = digit_field(d_lo, shift, mask, half);
+          im[m] = digit_field(d_hi, shift, mask, half);
         }
       }
       fft.forward(re, im, xch, t);
@@ -625,27 +717,13 @@ __global__ __launch_bounds__(F::THREADS * WideTeams<L>::value) void pbs_wide_tea
       workgroup_sync();   // the transformed digits are consumed: the buffers are free for the next phase's exchanges / the inverse
     }
     if (mac) {   // (workgroup barriers inside: the other teams walk the same barriers)
-      fft.inverse(o_re, o_im, xch, t);
-      uint64_t *accw = acc + (size_t)team * N;
-#pragma unroll
-      for (int m = 0; m < 8; m++) {
-        accw[m * T + t] = add_rounded<kReduce>(accw[m * T + t], o_re[m], scale);
-        accw[M + m * T + t] = add_rounded<kReduce>(accw[M + m * T + t], o_im[m], scale);
-      }
+      PRODUCT_ADD(kReduce, M, T, acc + (size_t)team * N, o_re, o_im, xch, fft, scale, t);
     } else {
       F::transform_barriers_only();
     }
     workgroup_sync();
   }
-  if (p.extract) {
-    // src/trlwe.c:540-552 at idx = 0
-    uint64_t *dst = p.out + b * (size_t)(N + 1);
-    for (int j = tid; j < N; j += WG) dst[j] = extract0_coeff(acc, j, N);
-    if (tid == 0) dst[N] = acc[N];
-  } else {
-    uint64_t *dst = p.out + b * (size_t)(2 * N);
-    for (int x = tid; x < 2 * N; x += WG) dst[x] = acc[x];
-  }
+  acc_write_out<N, WG>(p, b, acc, tid);
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -674,15 +752,8 @@ __global__ __launch_bounds__(2 * F::THREADS) void pbs_wide_pair_kernel(PbsParams
   const int Bg_bit = BG > 0 ? BG : p.Bg_bit;
   F fft;
   fft_setup(fft, p.tw, t);
-  if (p.skip_init) {
-    const uint64_t *src = p.out + b * (size_t)(2 * N);
-    for (int x = tid; x < 2 * N; x += WG) acc[x] = src[x];
-  } else {
-    const uint64_t *__restrict__ tv = p.rows > 1 ? p.tv + (b % (size_t)p.rows) * (size_t)(2 * N) : p.tv + b * (size_t)p.tv_stride;
-    const uint32_t bbar = modswitch<LOG2N2>(pbs_pre(ct[p.n], p, LOG2N2) + p.prec_offset);
-    const auto [a_lo, flip] = first_rotation(bbar, N);
-    for (int x = tid; x < 2 * N; x += WG) acc[x] = rot_coeff<N>(tv + (x / N) * N, x & (N - 1), a_lo, flip);
-  }
+  if (p.skip_init) acc_copy_in<N, WG>(acc, p.out + b * (size_t)(2 * N), tid);
+  else acc_rotate_in<N, WG>(acc, test_vector<N>(p, b), modswitch<LOG2N2>(pbs_pre(ct[p.n], p, LOG2N2) + p.prec_offset), tid);
   workgroup_sync();
   const uint64_t off = GADGET_OFFSET(L, Bg_bit);
   const RoundCtx scale = round_scale<M>();
@@ -693,83 +764,35 @@ __global__ __launch_bounds__(2 * F::THREADS) void pbs_wide_pair_kernel(PbsParams
     const int abar = (int)modswitch<LOG2N2>(pbs_pre(ct[i], p, LOG2N2));
     if (!abar) continue;   // src/bootstrap.c:114 (uniform over the workgroup)
     const d2 *__restrict__ bkrow = p.bk + (size_t)i * row_sz;
-    const auto [a_lo, flip] = split_rotation(abar, N);
+    const Rotation rot = split_rotation(abar, N);
     double o_re[8], o_im[8];
 #pragma unroll
     for (int m = 0; m < 8; m++) { o_re[m] = 0.0; o_im[m] = 0.0; }
 #pragma unroll
     for (int dp = 0; dp < DPH; dp++) {
-      d2 kk[4][8];   // this team's output component of the double phase's four key rows
-#pragma unroll
-      for (int r = 0; r < 4; r++)
-#pragma unroll
-        for (int m = 0; m < 8; m++) kk[r][m] = bkrow[(size_t)(4 * dp + r) * (2 * M) + (size_t)team * M + m * T + t];
       // rows rx (x) and rx + 2 (y): L is even, so both teams' x rows lie in one accumulator component and both y rows in one (the same one unless L % 4 != 0)
       const int rx = 4 * dp + team, ry = rx + 2, qx = (4 * dp) / L, qy = (4 * dp + 2) / L, sx = 64 - (rx % L + 1) * Bg_bit, sy = 64 - (ry % L + 1) * Bg_bit;
-      double xr[8], xi[8], yr[8], yi[8];
-      {
-        const uint64_t *accx = acc + (size_t)qx * N, *accy = acc + (size_t)qy * N;
+      const uint64_t *accx = acc + (size_t)qx * N, *accy = acc + (size_t)qy * N;
+      double_phase(o_re, o_im, bkrow + (size_t)(4 * dp) * (2 * M) + (size_t)team * M + t, hand, xch, fft, team, t,
+                   [&](double (&xr)[8], double (&xi)[8], double (&yr)[8], double (&yi)[8]) {
 #pragma unroll
-        for (int m = 0; m < 8; m++) {
+        for (int m = 0; m < 8; m++) {   // (the rotated accumulator words are read once for both levels)
           const int j = m * T + t;
-          const uint64_t d_lo = rot_coeff<N>(accx, j, a_lo, flip) - accx[j] + off;
-          const uint64_t d_hi = rot_coeff<N>(accx, j + M, a_lo, flip) - accx[j + M] + off;
-          xr[m] = (double)((int)((uint32_t)(d_lo >> sx) & mask) - half);
-          xi[m] = (double)((int)((uint32_t)(d_hi >> sx) & mask) - half);
-          const uint64_t e_lo = qy == qx ? d_lo : rot_coeff<N>(accy, j, a_lo, flip) - accy[j] + off;
-          const uint64_t e_hi = qy == qx ? d_hi : rot_coeff<N>(accy, j + M, a_lo, flip) - accy[j + M] + off;
-          yr[m] = (double)((int)((uint32_t)(e_lo >> sy) & mask) - half);
-          yi[m] = (double)((int)((uint32_t)(e_hi >> sy) & mask) - half);
+          const uint64_t d_lo = rotated_difference<N>(accx, j, rot, off), d_hi = rotated_difference<N>(accx, j + M, rot, off);
+          xr[m] = digit_field(d_lo, sx, mask, half);
+          xi[m] = digit_field(d_hi, sx, mask, half);
+          const uint64_t e_lo = qy == qx ? d_lo : rotated_difference<N>(accy, j, rot, off);
+          const uint64_t e_hi = qy == qx ? d_hi : rotated_difference<N>(accy, j + M, rot, off);
+          yr[m] = digit_field(e_lo, sy, mask, half);
+          yi[m] = digit_field(e_hi, sy, mask, half);
         }
-      }
-      fft.forward2_head(xr, xi, yr, yi, xch, t);
-      fft.pass_d_fwd(xr, xi);
-      d2 *hx = hand + (size_t)team * M, *hy = hand + (size_t)(2 + team) * M;   // hand-over buffer r holds row 4 dp + r
-#pragma unroll
-      for (int m = 0; m < 8; m++) hx[m * T + t] = d2{xr[m], xi[m]};
-      fft.forward2_fetch(yr, yi, xch, t);
-      fft.pass_d_fwd(yr, yi);
-      F::forward2_done();   // (a workgroup barrier: both teams' x rows are handed over)
-#pragma unroll
-      for (int m = 0; m < 8; m++) hy[m * T + t] = d2{yr[m], yi[m]};
-#pragma unroll
-      for (int r = 0; r < 2; r++) {   // fma chain over the double phase's rows in order: the x rows (0, 1) while the y rows land
-        const d2 *__restrict__ dr = hand + (size_t)r * M;
-#pragma unroll
-        for (int m = 0; m < 8; m++) {
-          const d2 d = dr[m * T + t], k = kk[r][m];
-          cmac(o_re[m], o_im[m], d.x, d.y, k);
-        }
-      }
-      workgroup_sync();
-#pragma unroll
-      for (int r = 2; r < 4; r++) {
-        const d2 *__restrict__ dr = hand + (size_t)r * M;
-#pragma unroll
-        for (int m = 0; m < 8; m++) {
-          const d2 d = dr[m * T + t], k = kk[r][m];
-          cmac(o_re[m], o_im[m], d.x, d.y, k);
-        }
-      }
+      });
       workgroup_sync();   // the hand-over buffers are consumed
     }
-    fft.inverse(o_re, o_im, xch, t);
-    uint64_t *accw = acc + (size_t)team * N;
-#pragma unroll
-    for (int m = 0; m < 8; m++) {
-      accw[m * T + t] = add_rounded<kReduce>(accw[m * T + t], o_re[m], scale);
-      accw[M + m * T + t] = add_rounded<kReduce>(accw[M + m * T + t], o_im[m], scale);
-    }
+    PRODUCT_ADD(kReduce, M, T, acc + (size_t)team * N, o_re, o_im, xch, fft, scale, t);
     workgroup_sync();
   }
-  if (p.extract) {
-    uint64_t *dst = p.out + b * (size_t)(N + 1);
-    for (int j = tid; j < N; j += WG) dst[j] = extract0_coeff(acc, j, N);
-    if (tid == 0) dst[N] = acc[N];
-  } else {
-    uint64_t *dst = p.out + b * (size_t)(2 * N);
-    for (int x = tid; x < 2 * N; x += WG) dst[x] = acc[x];
-  }
+  acc_write_out<N, WG>(p, b, acc, tid);
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -784,13 +807,13 @@ __global__ __launch_bounds__(2 * F::THREADS) void pbs_wide_pair_kernel(PbsParams
 // Summation order: out[c] = (chain over rows 0 .. l-1 from zero) + (chain over rows l .. 2l-1 from zero) -- NOT the reference's one chain over all 2 l rows
 // (an fma chain cannot be cut without changing roundings).  The difference is FFT-level rounding; the oracle restates this order
 // (oracle_tfhe.c: orc_set_product_order(1), held to the reference within the tolerance of the plain order) and the kernel is bit-identical to THAT.
-// Exchange (tools/ubench/xchg.hip: 1.5 us per step against 3.75 us for data + flag): no flag.  Receive slots hold a sentinel -- a NaN pattern that fma
-// arithmetic on finite numbers never produces; the sender's lanes store their 16-byte items with device-scope stores, the receiver's lanes poll THEIR OWN
-// items with device-scope loads until both halves of every item differ from the sentinel, then put the sentinel back (complete before the workgroup's next send
-// can be observed: s_waitcnt + the step's barrier).  Two slot sets alternate by step, so a sender never meets a slot its partner has not reset.
-// Pairing: blocks B and B + 8 (the same XCD when workgroups are dealt round-robin; nothing depends on it) claim their ciphertext through one state word:
-// the first to arrive waits a bounded time for the second; if that runs out (the partner is not resident: the chip is shared) it takes the whole
-// bootstrap ALONE -- both components, the same summation order, the same bits -- and the late partner leaves.  Nothing can hang and no result depends on timing.
+// The pairing of the two workgroups and their exchange are described at split_claim and split_receive8 in front of the kernel, which pbs_ga_split_kernel calls.
+// Two slot sets alternate by step, so a sender never meets a slot its partner has not reset; the slots a step put back are at their coherence point
+// (s_waitcnt + the step's barrier) before the workgroup's next send can be observed.
+// THIS kernel keeps its own text of every step, the claim and the receive included: it is the one whose timing followed the text.  With the shared steps
+// (double_phase, split_receive8, split_claim, the fill and the write-out) a single paired bootstrap took 2 % longer; with the double phase and the receive put
+// back and the other helpers kept, 128 paired bootstraps did (profiles/latency_steps_2026-10-21.txt).  A change to the claim or the receive is made here AND in
+// the helper.
 // ------------------------------------------------------------------------------------------------------------
 constexpr uint64_t kSplitSentinel = 0xFFF7A5C3DEADBEEFull;
 struct SplitParams {
@@ -804,6 +827,9 @@ __global__ void split_prepare_kernel(uint64_t *xbuf_words, size_t n_words, unsig
   if (i < n_words) xbuf_words[i] = kSplitSentinel;
   if (i < (size_t)count) state[i] = 0u;
 }
+// Exchange between the workgroups of a pair (tools/ubench/xchg.hip: 1.5 us per step against 3.75 us for data + flag): no flag.  Receive slots hold a sentinel --
+// a NaN pattern that fma arithmetic on finite numbers never produces; the sender's lanes store their 16-byte items with device-scope stores, the receiver's
+// lanes poll THEIR OWN items with device-scope loads until both halves of every item differ from the sentinel, then put the sentinel back.
 // the lane's eight 16-byte items of a 16 KiB set (item m at [m * 128 + t]), device scope
 __device__ __forceinline__ void split_store8(d2 *p, const double (&re)[8], const double (&im)[8]) {
 #pragma unroll
@@ -828,6 +854,48 @@ __device__ __forceinline__ void split_load8(d2 (&v)[8], const d2 *p) {
       : "=&v"(v[0]), "=&v"(v[1]), "=&v"(v[2]), "=&v"(v[3]), "=&v"(v[4]), "=&v"(v[5]), "=&v"(v[6]), "=&v"(v[7])
       : "v"(p), "v"(p + 256), "v"(p + 512), "v"(p + 768)
       : "memory");
+}
+// Receive the lane's eight items of a slot set: wait until none holds the sentinel, then hand item m to `use(m, item)` and put the sentinel back, item by item.
+template <class U>
+__device__ __forceinline__ void split_receive8(d2 *slot, U use) {
+  d2 v[8];
+  bool all;
+  do {
+    split_load8(v, slot);
+    all = true;
+#pragma unroll
+    for (int m = 0; m < 8; m++) {   // (element copies first: __builtin_bit_cast of a vector ELEMENT reads element 0 whichever is named -- clang 22)
+      const double vx = v[m].x, vy = v[m].y;
+      all = all && __builtin_bit_cast(uint64_t, vx) != kSplitSentinel && __builtin_bit_cast(uint64_t, vy) != kSplitSentinel;
+    }
+  } while (!all);
+  const double sent = __builtin_bit_cast(double, kSplitSentinel);
+#pragma unroll
+  for (int m = 0; m < 8; m++) {
+    use(m, v[m]);
+    const d2 sv = d2{sent, sent};
+    asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(slot + m * 128), "v"(sv) : "memory");   // (s_nop 1: see split_store8)
+  }
+}
+// Pairing: blocks B and B + 8 (the same XCD when workgroups are dealt round-robin; nothing depends on it) claim their ciphertext b through one state word:
+// the first to arrive waits a bounded time for the second; if that runs out (the partner is not resident: the chip is shared) it takes the whole
+// bootstrap ALONE -- both components, the same summation order, the same bits -- and the late partner leaves.  Nothing can hang and no result depends on timing.
+// Called by one thread of workgroup h of the pair; returns 0: paired, 1: alone, 2: leave.
+__device__ __forceinline__ int split_claim(const SplitParams &sp, size_t b, int h) {
+  unsigned int *st = sp.state + b;
+  if (sp.limit <= 0) return h == 0 ? 1 : 2;
+  unsigned int seen = 0u, one = 1u;
+  if (__hip_atomic_compare_exchange_strong(st, &seen, 1u, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
+    const long long t0 = wall_clock64();   // first here: wait for the partner, but not for ever
+    for (;;) {
+      if (__hip_atomic_load(st, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 2u) return 0;
+      if (wall_clock64() - t0 > sp.limit)   // (a partner that arrives now finds 3 and leaves; one that got its 2 in first is a partner)
+        return __hip_atomic_compare_exchange_strong(st, &one, 3u, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) ? 1 : 0;
+      __builtin_amdgcn_s_sleep(8);
+    }
+  }
+  if (seen != 1u) return 2;   // the ciphertext is paired or taken already
+  return __hip_atomic_compare_exchange_strong(st, &one, 2u, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) ? 0 : 2;
 }
 
 template <class F, int L, int BG, bool SOLO = false>
@@ -1171,6 +1239,23 @@ __device__ __forceinline__ uint32_t inverse_mod_2n(uint32_t x, uint32_t mask) {
   for (int i = 0; i < 4; i++) inv = (inv * (2u - x * inv)) & mask;
   return inv;
 }
+// The generator schedule of the Galois blind rotation (src/bootstrap_ga.c:44-58) over the switched mask words a_i | 1 of `ct`, a_cur the one at hand:
+// before the first step acc <- Auto_{w0'}(acc), w0' = (a_0 | 1)^-1 ...
+template <int LOG2N2>
+__device__ __forceinline__ int ga_first_gen(uint32_t &a_cur, const uint64_t *__restrict__ ct) {
+  a_cur = modswitch<LOG2N2>(ct[0]) | 1u;
+  return (int)inverse_mod_2n(a_cur, (1u << LOG2N2) - 1);
+}
+// ... and step i ends with Auto_gen, gen = a_i * (a_{i+1})^-1 (the last step: a_{n-1})
+template <int LOG2N2>
+__device__ __forceinline__ int ga_step_gen(uint32_t &a_cur, const uint64_t *__restrict__ ct, int i, int n) {
+  constexpr uint32_t mask = (1u << LOG2N2) - 1;
+  if (i + 1 >= n) return (int)a_cur;
+  const uint32_t a_next = modswitch<LOG2N2>(ct[i + 1]) | 1u;
+  const int gen = (int)((a_cur * inverse_mod_2n(a_next, mask)) & mask);
+  a_cur = a_next;
+  return gen;
+}
 
 struct GaParams {
   PbsParams p;
@@ -1235,24 +1320,15 @@ __global__ __launch_bounds__(F::THREADS, 2) void pbs_ga_kernel(GaParams g) {
       }
     }
     F::sync();
-    const uint32_t mask = 2 * N - 1;
-    // src/bootstrap_ga.c:44-45: w0' = (a_0 | 1)^-1 ; acc = Auto_{w0'}(acc)
-    uint32_t a_cur = modswitch<LOG2N2>(ct[0]) | 1u;
+    uint32_t a_cur;
     {
-      const int gen = (int)inverse_mod_2n(a_cur, mask);
+      const int gen = ga_first_gen<LOG2N2>(a_cur, ct);
       ga_eval_automorphism<F, L, BG>(al, ah, acc1, xch, fft, g.ak + (size_t)((gen - 1) >> 1) * ak_sz, gen, off, Bg_bit, scale, t);
     }
     for (int i = 0; i < p.n; i++) {
       if (T > 64 && p.pace && i > 0 && i % p.pace_every == 0) pace_teams(p.pace, (unsigned)(i / p.pace_every), t, p.pace_limit);
-      // :46-58: acc = BK_i (.) acc ; gen = a_i * (a_{i+1})^-1 (last step: a_{n-1}) ; acc = Auto_gen(acc)
-      int gen;
-      if (i + 1 < p.n) {
-        const uint32_t a_next = modswitch<LOG2N2>(ct[i + 1]) | 1u;
-        gen = (int)((a_cur * inverse_mod_2n(a_next, mask)) & mask);
-        a_cur = a_next;
-      } else {
-        gen = (int)a_cur;
-      }
+      // :46-58: acc = BK_i (.) acc ; acc = Auto_gen(acc)
+      const int gen = ga_step_gen<LOG2N2>(a_cur, ct, i, p.n);
       ga_external_product<F, L, BG>(al, ah, acc1, xch, fft, p.bk + (size_t)i * row_sz, off, Bg_bit, scale, t);
       ga_eval_automorphism<F, L, BG>(al, ah, acc1, xch, fft, g.ak + (size_t)((gen - 1) >> 1) * ak_sz, gen, off, Bg_bit, scale, t);
     }
@@ -1318,8 +1394,8 @@ struct GaWide {
         double re[8], im[8];
 #pragma unroll
         for (int m = 0; m < 8; m++) {
-          re[m] = (double)((int)((uint32_t)((accq[m * T + t] + off) >> shift) & mask) - half);
-          im[m] = (double)((int)((uint32_t)((accq[M + m * T + t] + off) >> shift) & mask) - half);
+          re[m] = digit_field(accq[m * T + t] + off, shift, mask, half);
+          im[m] = digit_field(accq[M + m * T + t] + off, shift, mask, half);
         }
         fft.forward(re, im, xch, t);
 #pragma unroll
@@ -1340,19 +1416,13 @@ struct GaWide {
       }
       workgroup_sync();
     }
-    fft.inverse(o_re, o_im, xch, t);
   }
 
-  // acc <- BK (.) acc   (src/bootstrap_ga.c:50: the product replaces the accumulator)
+  // acc <- BK (.) acc
   __device__ __forceinline__ void external_product(const d2 *__restrict__ bkrow, const RoundCtx &scale) const {
     double o_re[8], o_im[8];
     product(o_re, o_im, bkrow, 2 * l);
-    uint64_t *accw = acc + (size_t)team * N;
-#pragma unroll
-    for (int m = 0; m < 8; m++) {
-      accw[m * T + t] = round_mod_2_64(o_re[m], scale);
-      accw[M + m * T + t] = round_mod_2_64(o_im[m], scale);
-    }
+    PRODUCT_REPLACE(M, T, acc + (size_t)team * N, o_re, o_im, xch, fft, scale, t);
     workgroup_sync();
   }
 
@@ -1372,20 +1442,7 @@ struct GaWide {
     workgroup_sync();
     double o_re[8], o_im[8];
     product(o_re, o_im, entry, l);
-    uint64_t *accw = acc + (size_t)team * N;
-    if (team == 0) {
-#pragma unroll
-      for (int m = 0; m < 8; m++) {
-        accw[m * T + t] = 0 - round_mod_2_64(o_re[m], scale);
-        accw[M + m * T + t] = 0 - round_mod_2_64(o_im[m], scale);
-      }
-    } else {
-#pragma unroll
-      for (int m = 0; m < 8; m++) {
-        accw[m * T + t] -= round_mod_2_64(o_re[m], scale);
-        accw[M + m * T + t] -= round_mod_2_64(o_im[m], scale);
-      }
-    }
+    PRODUCT_KEYSWITCH(M, T, acc + (size_t)team * N, team, o_re, o_im, xch, fft, scale, t);
     workgroup_sync();
   }
 };
@@ -1406,47 +1463,25 @@ __global__ __launch_bounds__(2 * F::THREADS) void pbs_ga_wide_kernel(GaParams g,
   const RoundCtx scale = round_scale<M>();
   const size_t row_sz = (size_t)2 * l * 2 * M, ak_sz = (size_t)l * 2 * M;
   const uint64_t *__restrict__ ct = p.in + b * (size_t)(p.n + 1);
-  if (p.skip_init) {
-    const uint64_t *src = p.out + b * (size_t)(2 * N);
-    for (int x = tid; x < 2 * N; x += WG) acc[x] = src[x];
-  } else {
-    const uint64_t *__restrict__ tv = p.tv + b * (size_t)p.tv_stride;
-    const uint32_t bbar = modswitch<LOG2N2>(ct[p.n] + p.prec_offset);
-    const auto [a_lo, flip] = first_rotation(bbar, N);
-    for (int x = tid; x < 2 * N; x += WG) acc[x] = rot_coeff<N>(tv + (x / N) * N, x & (N - 1), a_lo, flip);
-  }
+  if (p.skip_init) acc_copy_in<N, WG>(acc, p.out + b * (size_t)(2 * N), tid);
+  else acc_rotate_in<N, WG>(acc, p.tv + b * (size_t)p.tv_stride, modswitch<LOG2N2>(ct[p.n] + p.prec_offset), tid);
   workgroup_sync();
   const GaWide<F> w{fft, xch_all, xch_all + (size_t)team * F::XCH_SLOTS, acc, team, t, tid, l, Bg_bit, off, (1u << Bg_bit) - 1, 1 << (Bg_bit - 1)};
-  const uint32_t mask = 2 * N - 1;
-  uint32_t a_cur = modswitch<LOG2N2>(ct[0]) | 1u;
+  uint32_t a_cur;
   {
-    const int gen = (int)inverse_mod_2n(a_cur, mask);
+    const int gen = ga_first_gen<LOG2N2>(a_cur, ct);
     w.eval_automorphism(g.ak + (size_t)((gen - 1) >> 1) * ak_sz, gen, scale);
   }
   for (int i = 0; i < p.n; i++) {
-    int gen;
-    if (i + 1 < p.n) {
-      const uint32_t a_next = modswitch<LOG2N2>(ct[i + 1]) | 1u;
-      gen = (int)((a_cur * inverse_mod_2n(a_next, mask)) & mask);
-      a_cur = a_next;
-    } else {
-      gen = (int)a_cur;
-    }
+    const int gen = ga_step_gen<LOG2N2>(a_cur, ct, i, p.n);
     w.external_product(p.bk + (size_t)i * row_sz, scale);
     w.eval_automorphism(g.ak + (size_t)((gen - 1) >> 1) * ak_sz, gen, scale);
   }
-  if (p.extract) {
-    uint64_t *dst = p.out + b * (size_t)(N + 1);
-    for (int j = tid; j < N; j += WG) dst[j] = extract0_coeff(acc, j, N);
-    if (tid == 0) dst[N] = acc[N];
-  } else {
-    uint64_t *dst = p.out + b * (size_t)(2 * N);
-    for (int x = tid; x < 2 * N; x += WG) dst[x] = acc[x];
-  }
+  acc_write_out<N, WG>(p, b, acc, tid);
 }
 
 // ------------------------------------------------------------------------------------------------------------
-// pbs_ga_split_kernel: the Galois-automorphism bootstrap on TWO workgroups, like pbs_split_kernel (which see: pairing, sentinel slots, the take-it-alone fall-back).
+// pbs_ga_split_kernel: the Galois-automorphism bootstrap on TWO workgroups, like pbs_split_kernel (the same pairing with its take-it-alone fall-back, split_claim, and the same sentinel slots, split_store8 / split_receive8).
 // Workgroup 0 keeps accumulator component a, workgroup 1 component b.  Per step (src/bootstrap_ga.c:48-52):
 //   * acc <- BK_i (.) acc: each workgroup decomposes ITS component (l = 4 rows, the double phase of pbs_wide_pair_kernel), multiplies into both output components,
 //     sends the partial sum it does not keep, adds its partner's, inverse-transforms and REPLACES its component -- the per-component summation order of
@@ -1471,34 +1506,9 @@ __global__ __launch_bounds__(2 * F::THREADS) void pbs_ga_split_kernel(GaParams g
   const int h = SOLO ? 0 : (int)((blockIdx.x >> 3) & 1u);
   const size_t b = SOLO ? (size_t)blockIdx.x : (size_t)(blockIdx.x >> 4) * 8 + (blockIdx.x & 7u);
   if (b >= (size_t)sp.count) return;
-  if (!SOLO && tid == 0) {   // pairing: see pbs_split_kernel
-    unsigned int *st = sp.state + b;
-    int mode;
-    if (sp.limit <= 0) {
-      mode = h == 0 ? 1 : 2;
-    } else {
-      unsigned int seen = 0u;
-      if (__hip_atomic_compare_exchange_strong(st, &seen, 1u, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
-        const long long t0 = wall_clock64();
-        mode = -1;
-        while (mode < 0) {
-          if (__hip_atomic_load(st, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 2u) mode = 0;
-          else if (wall_clock64() - t0 > sp.limit) {
-            unsigned int one = 1u;
-            mode = __hip_atomic_compare_exchange_strong(st, &one, 3u, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) ? 1 : 0;
-          } else __builtin_amdgcn_s_sleep(8);
-        }
-      } else if (seen == 1u) {
-        unsigned int one = 1u;
-        mode = __hip_atomic_compare_exchange_strong(st, &one, 2u, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) ? 0 : 2;
-      } else {
-        mode = 2;
-      }
-    }
-    mode_s = mode;
-  }
+  if (!SOLO && tid == 0) mode_s = split_claim(sp, b, h);
   if (!SOLO) workgroup_sync();
-  const int mode = SOLO ? 1 : mode_s;
+  const int mode = SOLO ? 1 : mode_s;   // 0 paired, 1 alone, 2 leave
   if (mode == 2) return;
   const bool alone = SOLO || mode == 1;
   const int dp_lo = alone ? 0 : h, dp_hi = alone ? 2 : h + 1;
@@ -1509,15 +1519,8 @@ __global__ __launch_bounds__(2 * F::THREADS) void pbs_ga_split_kernel(GaParams g
   F fft;
   fft_setup(fft, p.tw, t);
   const uint64_t *__restrict__ ct = p.in + b * (size_t)(p.n + 1);
-  if (p.skip_init) {
-    const uint64_t *src = p.out + b * (size_t)(2 * N);
-    for (int x = tid; x < 2 * N; x += WG) acc[x] = src[x];
-  } else {
-    const uint64_t *__restrict__ tv = p.tv + b * (size_t)p.tv_stride;
-    const uint32_t bbar = modswitch<LOG2N2>(ct[p.n] + p.prec_offset);
-    const auto [a_lo, flip] = first_rotation(bbar, N);
-    for (int x = tid; x < 2 * N; x += WG) acc[x] = rot_coeff<N>(tv + (x / N) * N, x & (N - 1), a_lo, flip);
-  }
+  if (p.skip_init) acc_copy_in<N, WG>(acc, p.out + b * (size_t)(2 * N), tid);
+  else acc_rotate_in<N, WG>(acc, p.tv + b * (size_t)p.tv_stride, modswitch<LOG2N2>(ct[p.n] + p.prec_offset), tid);
   workgroup_sync();
   const uint64_t off = GADGET_OFFSET(L, Bg_bit);
   const RoundCtx scale = round_scale<M>();
@@ -1525,74 +1528,22 @@ __global__ __launch_bounds__(2 * F::THREADS) void pbs_ga_split_kernel(GaParams g
   const uint32_t dmask = (1u << Bg_bit) - 1;
   const int half = 1 << (Bg_bit - 1);
   const int sx = 64 - (team + 1) * Bg_bit, sy = 64 - (team + 3) * Bg_bit;   // this team's levels: team (x) and team + 2 (y)
-  const double sent = __builtin_bit_cast(double, kSplitSentinel);
 
-  // o = the chain over the four rows `rows` (this team's output component, lane offset included) of DFT(digit_level(accx)): the double phase of pbs_wide_pair_kernel
+  // o = the chain over the four rows `rows` (this team's output component, lane offset included) of DFT(digit_level(accx)): one double phase
   auto quad = [&](const uint64_t *accx, const d2 *__restrict__ rows, double (&o_re)[8], double (&o_im)[8]) {
-    d2 kk[4][8];
-#pragma unroll
-    for (int r = 0; r < 4; r++)
-#pragma unroll
-      for (int m = 0; m < 8; m++) kk[r][m] = rows[(size_t)r * (2 * M) + m * T];
 #pragma unroll
     for (int m = 0; m < 8; m++) { o_re[m] = 0.0; o_im[m] = 0.0; }
-    double xr[8], xi[8], yr[8], yi[8];
-#pragma unroll
-    for (int m = 0; m < 8; m++) {
-      const uint64_t d_lo = accx[m * T + t] + off, d_hi = accx[M + m * T + t] + off;
-      xr[m] = (double)((int)((uint32_t)(d_lo >> sx) & dmask) - half);
-      xi[m] = (double)((int)((uint32_t)(d_hi >> sx) & dmask) - half);
-      yr[m] = (double)((int)((uint32_t)(d_lo >> sy) & dmask) - half);
-      yi[m] = (double)((int)((uint32_t)(d_hi >> sy) & dmask) - half);
-    }
-    fft.forward2_head(xr, xi, yr, yi, xch, t);
-    fft.pass_d_fwd(xr, xi);
-    d2 *hx = hand + (size_t)team * M, *hy = hand + (size_t)(2 + team) * M;
-#pragma unroll
-    for (int m = 0; m < 8; m++) hx[m * T + t] = d2{xr[m], xi[m]};
-    fft.forward2_fetch(yr, yi, xch, t);
-    fft.pass_d_fwd(yr, yi);
-    F::forward2_done();
-#pragma unroll
-    for (int m = 0; m < 8; m++) hy[m * T + t] = d2{yr[m], yi[m]};
-#pragma unroll
-    for (int r = 0; r < 2; r++) {
-      const d2 *__restrict__ dr = hand + (size_t)r * M;
+    double_phase(o_re, o_im, rows, hand, xch, fft, team, t, [&](double (&xr)[8], double (&xi)[8], double (&yr)[8], double (&yi)[8]) {
 #pragma unroll
       for (int m = 0; m < 8; m++) {
-        const d2 d = dr[m * T + t], k = kk[r][m];
-        cmac(o_re[m], o_im[m], d.x, d.y, k);
+        const uint64_t d_lo = accx[m * T + t] + off, d_hi = accx[M + m * T + t] + off;
+        xr[m] = digit_field(d_lo, sx, dmask, half);
+        xi[m] = digit_field(d_hi, sx, dmask, half);
+        yr[m] = digit_field(d_lo, sy, dmask, half);
+        yi[m] = digit_field(d_hi, sy, dmask, half);
       }
-    }
-    workgroup_sync();
-#pragma unroll
-    for (int r = 2; r < 4; r++) {
-      const d2 *__restrict__ dr = hand + (size_t)r * M;
-#pragma unroll
-      for (int m = 0; m < 8; m++) {
-        const d2 d = dr[m * T + t], k = kk[r][m];
-        cmac(o_re[m], o_im[m], d.x, d.y, k);
-      }
-    }
+    });
     workgroup_sync();   // the hand-over buffers are consumed
-  };
-  // the lane's eight items of a slot set: wait for them, put the sentinel back
-  auto receive = [&](d2 *slot, d2 (&v)[8]) {
-    bool all;
-    do {
-      split_load8(v, slot);
-      all = true;
-#pragma unroll
-      for (int m = 0; m < 8; m++) {
-        const double vx = v[m].x, vy = v[m].y;
-        all = all && __builtin_bit_cast(uint64_t, vx) != kSplitSentinel && __builtin_bit_cast(uint64_t, vy) != kSplitSentinel;
-      }
-    } while (!all);
-#pragma unroll
-    for (int m = 0; m < 8; m++) {
-      const d2 sv = d2{sent, sent};
-      asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(slot + m * 128), "v"(sv) : "memory");
-    }
   };
   int par_ep = 0, par_ks = 0;
 
@@ -1617,21 +1568,15 @@ __global__ __launch_bounds__(2 * F::THREADS) void pbs_ga_split_kernel(GaParams g
         split_store8(send_ep + (size_t)par_ep * M + t, s_re, s_im);
         inv = false;
       } else {
-        d2 v[8];
-        receive(recv_ep + (size_t)par_ep * M + t, v);
-#pragma unroll
-        for (int m = 0; m < 8; m++) { s_re[m] = s_re[m] + v[m].x; s_im[m] = s_im[m] + v[m].y; }
+        split_receive8(recv_ep + (size_t)par_ep * M + t, [&](int m, const d2 &v) {
+          s_re[m] = s_re[m] + v.x;
+          s_im[m] = s_im[m] + v.y;
+        });
       }
       par_ep ^= 1;
     }
     if (inv) {
-      fft.inverse(s_re, s_im, xch, t);
-      uint64_t *accw = acc + (size_t)team * N;
-#pragma unroll
-      for (int m = 0; m < 8; m++) {
-        accw[m * T + t] = round_mod_2_64(s_re[m], scale);
-        accw[M + m * T + t] = round_mod_2_64(s_im[m], scale);
-      }
+      PRODUCT_REPLACE(M, T, acc + (size_t)team * N, s_re, s_im, xch, fft, scale, t);
     } else {
       F::transform_barriers_only();
     }
@@ -1661,29 +1606,15 @@ __global__ __launch_bounds__(2 * F::THREADS) void pbs_ga_split_kernel(GaParams g
     if (!alone) {
       if (h == 0 && team == 1) split_store8(slot_ks + (size_t)par_ks * M + t, o_re, o_im);
       if (h == 1 && team == 1) {
-        d2 v[8];
-        receive(slot_ks + (size_t)par_ks * M + t, v);
-#pragma unroll
-        for (int m = 0; m < 8; m++) { o_re[m] = v[m].x; o_im[m] = v[m].y; }
+        split_receive8(slot_ks + (size_t)par_ks * M + t, [&](int m, const d2 &v) {
+          o_re[m] = v.x;
+          o_im[m] = v.y;
+        });
       }
       par_ks ^= 1;
     }
     if (inv) {
-      fft.inverse(o_re, o_im, xch, t);
-      uint64_t *accw = acc + (size_t)team * N;
-      if (team == 0) {
-#pragma unroll
-        for (int m = 0; m < 8; m++) {
-          accw[m * T + t] = 0 - round_mod_2_64(o_re[m], scale);
-          accw[M + m * T + t] = 0 - round_mod_2_64(o_im[m], scale);
-        }
-      } else {
-#pragma unroll
-        for (int m = 0; m < 8; m++) {
-          accw[m * T + t] -= round_mod_2_64(o_re[m], scale);
-          accw[M + m * T + t] -= round_mod_2_64(o_im[m], scale);
-        }
-      }
+      PRODUCT_KEYSWITCH(M, T, acc + (size_t)team * N, team, o_re, o_im, xch, fft, scale, t);
     } else {
       F::transform_barriers_only();
     }
@@ -1691,34 +1622,17 @@ __global__ __launch_bounds__(2 * F::THREADS) void pbs_ga_split_kernel(GaParams g
     workgroup_sync();
   };
 
-  const uint32_t mask2n = 2 * N - 1;
-  uint32_t a_cur = modswitch<LOG2N2>(ct[0]) | 1u;
+  uint32_t a_cur;
   {
-    const int gen = (int)inverse_mod_2n(a_cur, mask2n);
+    const int gen = ga_first_gen<LOG2N2>(a_cur, ct);
     eval_automorphism(g.ak + (size_t)((gen - 1) >> 1) * ak_sz, gen);
   }
   for (int i = 0; i < p.n; i++) {
-    int gen;
-    if (i + 1 < p.n) {
-      const uint32_t a_next = modswitch<LOG2N2>(ct[i + 1]) | 1u;
-      gen = (int)((a_cur * inverse_mod_2n(a_next, mask2n)) & mask2n);
-      a_cur = a_next;
-    } else {
-      gen = (int)a_cur;
-    }
+    const int gen = ga_step_gen<LOG2N2>(a_cur, ct, i, p.n);
     external_product(p.bk + (size_t)i * row_sz);
     eval_automorphism(g.ak + (size_t)((gen - 1) >> 1) * ak_sz, gen);
   }
-  const bool mine0 = alone || h == 0, mine1 = alone || h == 1;
-  if (p.extract) {
-    uint64_t *dst = p.out + b * (size_t)(N + 1);
-    if (mine0) for (int j = tid; j < N; j += WG) dst[j] = extract0_coeff(acc, j, N);
-    if (mine1 && tid == 0) dst[N] = acc[N];
-  } else {
-    uint64_t *dst = p.out + b * (size_t)(2 * N);
-    for (int x = tid; x < 2 * N; x += WG)
-      if (x < N ? mine0 : mine1) dst[x] = acc[x];
-  }
+  acc_write_out<N, WG>(p, b, acc, tid, alone || h == 0, alone || h == 1);   // the components this workgroup holds
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -2212,3 +2126,8 @@ __global__ void dft_mul_kernel(d2 *out, const d2 *a, const d2 *b, size_t count, 
 }
 
 }  // namespace mosfhet
+
+#undef PRODUCT_WORDS_
+#undef PRODUCT_ADD
+#undef PRODUCT_REPLACE
+#undef PRODUCT_KEYSWITCH

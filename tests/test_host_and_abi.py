@@ -237,6 +237,60 @@ def test_kernel_listing_diff_tool():
         assert [subprocess.run(tool + [paths[k]], capture_output=True).returncode for k in ("parent", "ignored", "changed", "missing")] == [0, 0, 1, 1]
 
 
+def test_kernel_listing_diff_where(monkeypatch):
+    """tools/kernel_listing_diff.py --where on two synthetic two-kernel listings: one kernel differs in its prologue only, the other inside its loop (a backward
+    branch; the test lowers the loop length from the 500 lines of a step loop to 3).  The differing line ranges count the parent's normalised lines from the label."""
+    import sys
+    monkeypatch.syspath_prepend(os.path.join(ROOT, "tools"))   # (undone when the test ends)
+    import kernel_listing_diff as kld
+
+    def kernel(name, index, prologue, loop):
+        return "\n".join(["%s:   ; @%s" % (name, name)] + prologue + [".LBB%d_1:   ; the step loop" % index] + loop +
+                         ["\ts_cbranch_scc1 .LBB%d_1" % index, "\tglobal_store_dword v0, v1, s[0:1]", "\ts_endpgm", "\t.amdhsa_kernel %s" % name, "\t\t.amdhsa_next_free_vgpr 8",
+                          "\t.end_amdhsa_kernel"])
+
+    pro, loop = ["\ts_load_dwordx2 s[0:1], s[4:5], 0x0", "\tv_mov_b32_e32 v1, 0"], ["\tv_add_u32_e32 v1, v1, v0", "\tv_mul_lo_u32 v1, v1, v0", "\ts_add_i32 s2, s2, -1", "\ts_cmp_lg_u32 s2, 0"]
+    names = ["_Z8prologuePm", "_Z6inloopPm"]
+    parent = "\n".join(kernel(n, i, pro, loop) for i, n in enumerate(names))
+    new = "\n".join([kernel(names[0], 0, [pro[0], "\tv_mov_b32_e32 v1, 1"], loop), kernel(names[1], 1, pro, [loop[0], "\tv_mul_lo_u32 v1, v0, v1", "\ts_nop 0"] + loop[2:])])
+
+    a, b = kld.kernels(parent), kld.kernels(new)
+    assert kld.loops(a[names[0]], 3) == [(3, 8)] and kld.loops(a[names[0]]) == []          # the label is line 3, the branch line 8; no loop of 500 lines
+    assert kld.where(a[names[0]], b[names[0]], 3) == ([(2, 2)], [(3, 8)], [])               # the second line of the prologue
+    assert kld.where(a[names[1]], b[names[1]], 3) == ([(5, 5)], [(3, 8)], [(5, 5)])         # the loop's second instruction (replaced by two)
+    # an insertion is the empty range in front of its line: inside the loop behind the label, outside in front of it
+    grown = a[names[1]][:3] + ["s_nop 0"] + a[names[1]][3:]
+    assert kld.where(a[names[1]], grown, 3)[0::2] == ([(4, 3)], [(4, 3)])
+    grown = a[names[1]][:2] + ["s_nop 0"] + a[names[1]][2:]
+    assert kld.where(a[names[1]], grown, 3)[0::2] == ([(3, 2)], [])
+
+    report, same = kld.compare(parent, new, show_where=True, loop_min=3)
+    text = "\n".join(report)
+    assert not same and "kernels that differ: 2" in report
+    pro_at, loop_at = text.index("prologue(unsigned long*)"), text.index("inloop(unsigned long*)")
+    assert "differing parent lines: 2-2" in text[pro_at:loop_at] and "loops (a backward branch over 3 lines or more): 3-8" in text[pro_at:loop_at]
+    assert "differences inside a loop: none" in text[pro_at:loop_at] and "differences inside a loop: 5-5" in text[loop_at:]
+    assert not any("differing parent lines" in line for line in kld.compare(parent, new)[0])   # only when asked for
+    # ... and the resource lines that changed
+    assert text.count("resource lines: same") == 2
+    more = new.replace(".amdhsa_next_free_vgpr 8", ".amdhsa_next_free_vgpr 12", 1)
+    assert "resource lines: .amdhsa_next_free_vgpr 8 -> 12" in "\n".join(kld.compare(parent, more, "prologue", show_where=True, loop_min=3)[0])
+
+    # the command line: --where anywhere behind the two listings, with or without a name filter
+    import subprocess
+    import tempfile
+    with tempfile.TemporaryDirectory() as tmp:
+        pa, pb = os.path.join(tmp, "parent.s"), os.path.join(tmp, "new.s")
+        for path, listing in ((pa, parent), (pb, new)):
+            with open(path, "w") as fh:
+                fh.write(listing)
+        tool = [sys.executable, os.path.join(ROOT, "tools", "kernel_listing_diff.py"), pa, pb]
+        res = subprocess.run(tool + ["--where", "inloop"], capture_output=True, text=True)
+        assert res.returncode == 1 and "kernels that differ: 1" in res.stdout and "differing parent lines: 5-5" in res.stdout
+        assert "loops (a backward branch over 500 lines or more): none" in res.stdout and "differences inside a loop: none" in res.stdout
+        assert "differing parent lines" not in subprocess.run(tool, capture_output=True, text=True).stdout
+
+
 def test_no_lds_reads_emitted_behind_a_workgroup_barrier():
     """The root cause of the "wrong units" of rounds 3 - 5 (experiments/README.md, Round 5) was the COMPILER moving LDS reads that the source places in front of a
     workgroup barrier behind it (machine sinking into the block after a conditional branch; S_BARRIER is no store to that pass).  Every barrier of the library now goes
