@@ -523,7 +523,8 @@ int mosfhet_hip_polylinear_clone(mosfhet_hip_ctx_t ctx_other, mosfhet_hip_polyli
 int mosfhet_hip_trlwe_linear_batch(mosfhet_hip_ctx_t ctx, mosfhet_hip_polylinear_t lin, uint64_t *d_out /*[count][rows_out][2][N]*/,
                                    const uint64_t *d_in /*[count][rows_in][2][N]*/, int count, void *stream);
 /* The same words followed by trlwe_extract_tlwe(., idx) (src/trlwe.c:540-552), 0 <= idx < N (else MOSFHET_HIP_EINVAL): a[i] = out.a[idx - i] for i <= idx,
- * -out.a[N + idx - i] above, b = out.b[idx].  The TRLWE result is never written; d_out is the [..][N+1] layout the key switch takes next. */
+ * -out.a[N + idx - i] above, b = out.b[idx].  The TRLWE result is never written; d_out is the [..][N+1] layout the key switch takes next.  count == 0 returns before
+ * the handle is read: idx < 0 is refused at every count, idx >= N where there is something to do. */
 int mosfhet_hip_trlwe_linear_extract_batch(mosfhet_hip_ctx_t ctx, mosfhet_hip_polylinear_t lin, uint64_t *d_out /*[count][rows_out][N+1]*/, const uint64_t *d_in, int idx,
                                            int count, void *stream);
 /* src/trlwe.c:491-505 and :540-552 into the calling thread's pool, then the body of mosfhet_hip_keyswitch_functional_bootstrap_batch on the count * rows_out samples:

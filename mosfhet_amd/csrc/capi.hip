@@ -277,6 +277,33 @@ static bool ring_ok(int N) { return N == 1024 || N == 2048 || N == 4096; }
     else { using F = Fft4096; const d2 *TW = (ctx_)->tw4096; (void)TW; __VA_ARGS__; }                  \
   } while (0)
 
+// do the byte ranges [a, a + a_bytes) and [b, b + b_bytes) meet?
+static bool ranges_overlap(const void *a, size_t a_bytes, const void *b, size_t b_bytes) {
+  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+  return a0 < b0 + b_bytes && b0 < a0 + a_bytes;
+}
+
+// The checks in front of key switch + bootstrap, for every call that ends in one.  The key switch must lead from the bootstrap's output key back to its input key;
+// lwe_rows = false leaves the key's row layout (LWE -> LWE, not a packing key) to the key switch itself.
+static int ks_bootstrap_keys_match(const char *who, const mosfhet_hip_ksk *ksk, const mosfhet_hip_bsk *bsk, bool lwe_rows = true) {
+  if (ksk->n_in != bsk->k * bsk->N || ksk->n_out != bsk->n || (lwe_rows && ksk->b_word != ksk->n_out))
+    return fail(MOSFHET_HIP_EINVAL, "%s: key-switch key is %d -> %d, expected %d -> %d", who, ksk->n_in, ksk->n_out, bsk->k * bsk->N, bsk->n);
+  return MOSFHET_HIP_OK;
+}
+
+// ... and on the samples that reach it: *samples = count * rows_out (* per, where per > 0 samples are opened from each result) fits an int, and there is one test
+// vector or one per sample.
+static int ks_bootstrap_samples(const char *who, int count, int rows_out, int per, int tv_count, long long *samples) {
+  char x_per[32] = "";
+  if (per) snprintf(x_per, sizeof(x_per), " x per = %d", per);
+  const long long results = (long long)count * rows_out;
+  *samples = results > 0x7fffffffLL ? results : results * (per ? per : 1);
+  if (*samples > 0x7fffffffLL) return fail(MOSFHET_HIP_EINVAL, "%s: count = %d x rows_out = %d%s samples do not fit an int", who, count, rows_out, x_per);
+  if (tv_count != 1 && tv_count != *samples)
+    return fail(MOSFHET_HIP_EINVAL, "%s: tv_count = %d (1 or count * rows_out%s = %lld)", who, tv_count, per ? " * per" : "", *samples);
+  return MOSFHET_HIP_OK;
+}
+
 extern "C" int mosfhet_hip_ctx_sync(mosfhet_hip_ctx_t ctx, void *stream) {
   if (!ctx) return fail(MOSFHET_HIP_EINVAL, "ctx_sync: null ctx");
   HIP_TRY(hipSetDevice(ctx->device));
@@ -1430,8 +1457,7 @@ extern "C" int mosfhet_hip_full_domain_functional_bootstrap_batch(mosfhet_hip_ct
                                                                   const uint64_t *d_in, int count, int precision, void *stream) {
   if (!ctx || !bsk || !ksk || (count > 0 && !d_out) || (count > 0 && !d_tv) || (count > 0 && !d_in) || count < 0) return fail(MOSFHET_HIP_EINVAL, "fdfb: bad argument");
   if (precision < 1 || precision > 30) return fail(MOSFHET_HIP_EINVAL, "fdfb: precision %d", precision);
-  if (ksk->n_in != bsk->k * bsk->N || ksk->n_out != bsk->n)
-    return fail(MOSFHET_HIP_EINVAL, "fdfb: key-switch key is %d -> %d, expected %d -> %d", ksk->n_in, ksk->n_out, bsk->k * bsk->N, bsk->n);
+  if (int rk = ks_bootstrap_keys_match("fdfb", ksk, bsk, false)) return rk;
   if (count == 0) return MOSFHET_HIP_OK;
   HIP_TRY(hipSetDevice(ctx->device));
   const int N = bsk->N, n = bsk->n, k = bsk->k;
@@ -1812,8 +1838,9 @@ extern "C" int mosfhet_hip_time_programmable_bootstrap(mosfhet_hip_ctx_t ctx, mo
 #include "capi_vec.inc"
 #include "capi_lut.inc"
 #include "capi_bits.inc"
-#include "capi_linear.inc"
 #include "capi_pack.inc"
+#include "capi_linear_common.inc"
+#include "capi_linear.inc"
 #include "capi_unpack.inc"
 #include "capi_trace.inc"
 #include "capi_polylinear.inc"

@@ -157,7 +157,7 @@ extern "C" int mosfhet_hip_trlwe_automaton_batch(mosfhet_hip_ctx_t ctx, uint64_t
   if (!d_sel_dft) return fail(MOSFHET_HIP_EINVAL, "%s: null d_sel_dft", who);
   if (!d_init) return fail(MOSFHET_HIP_EINVAL, "%s: null d_init", who);
   const size_t sample = (size_t)2 * N * sizeof(uint64_t);
-  if (ram_ranges_meet(d_out, (size_t)count * (start < 0 ? states : 1) * sample, d_init, (size_t)(init_shared ? 1 : count) * states * sample))
+  if (ranges_overlap(d_out, (size_t)count * (start < 0 ? states : 1) * sample, d_init, (size_t)(init_shared ? 1 : count) * states * sample))
     return fail(MOSFHET_HIP_EINVAL, "%s: d_out overlaps d_init", who);
   HIP_TRY(hipSetDevice(ctx->device));
   const int cus = device_cus() > 0 ? device_cus() : 256;

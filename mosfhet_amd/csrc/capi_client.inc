@@ -152,7 +152,7 @@ extern "C" int mosfhet_hip_tlwe_encrypt_batch(mosfhet_hip_ctx_t ctx, mosfhet_hip
   if (!d_out) return fail(MOSFHET_HIP_EINVAL, "%s: null d_out", who);
   if (!d_msg) return fail(MOSFHET_HIP_EINVAL, "%s: null d_msg", who);
   const int n = key->n;
-  if (ram_ranges_meet(d_out, (size_t)count * ((size_t)n + 1) * sizeof(uint64_t), d_msg, (size_t)count * sizeof(uint64_t)))
+  if (ranges_overlap(d_out, (size_t)count * ((size_t)n + 1) * sizeof(uint64_t), d_msg, (size_t)count * sizeof(uint64_t)))
     return fail(MOSFHET_HIP_EINVAL, "%s: d_out overlaps d_msg", who);
   HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t s = pick(ctx, stream);
@@ -182,7 +182,7 @@ extern "C" int mosfhet_hip_trlwe_encrypt_batch(mosfhet_hip_ctx_t ctx, mosfhet_hi
   if (count == 0) return MOSFHET_HIP_OK;
   if (!d_out) return fail(MOSFHET_HIP_EINVAL, "%s: null d_out", who);
   const int N = key->N;
-  if (d_msg && ram_ranges_meet(d_out, (size_t)count * 2 * N * sizeof(uint64_t), d_msg, (size_t)count * N * sizeof(uint64_t)))
+  if (d_msg && ranges_overlap(d_out, (size_t)count * 2 * N * sizeof(uint64_t), d_msg, (size_t)count * N * sizeof(uint64_t)))
     return fail(MOSFHET_HIP_EINVAL, "%s: d_out overlaps d_msg", who);
   HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t s = pick(ctx, stream);
@@ -211,12 +211,12 @@ extern "C" int mosfhet_hip_trgsw_encrypt_batch(mosfhet_hip_ctx_t ctx, mosfhet_hi
   if (rc || count == 0) return rc;
   if (!d_m) return fail(MOSFHET_HIP_EINVAL, "%s: null d_m", who);
   const size_t n_rows = (size_t)count * 2 * l, out_bytes = n_rows * 2 * N * sizeof(uint64_t), list_bytes = (size_t)count * sizeof(int32_t);
-  if (d_out_dft && d_out_torus && ram_ranges_meet(d_out_dft, out_bytes, d_out_torus, out_bytes)) return fail(MOSFHET_HIP_EINVAL, "%s: d_out_dft overlaps d_out_torus", who);
+  if (d_out_dft && d_out_torus && ranges_overlap(d_out_dft, out_bytes, d_out_torus, out_bytes)) return fail(MOSFHET_HIP_EINVAL, "%s: d_out_dft overlaps d_out_torus", who);
   for (const void *o : {(const void *)d_out_dft, (const void *)d_out_torus}) {
     if (!o) continue;
     const char *name = o == (const void *)d_out_dft ? "d_out_dft" : "d_out_torus";
-    if (ram_ranges_meet(o, out_bytes, d_m, list_bytes)) return fail(MOSFHET_HIP_EINVAL, "%s: %s overlaps d_m", who, name);
-    if (d_exp && ram_ranges_meet(o, out_bytes, d_exp, list_bytes)) return fail(MOSFHET_HIP_EINVAL, "%s: %s overlaps d_exp", who, name);
+    if (ranges_overlap(o, out_bytes, d_m, list_bytes)) return fail(MOSFHET_HIP_EINVAL, "%s: %s overlaps d_m", who, name);
+    if (d_exp && ranges_overlap(o, out_bytes, d_exp, list_bytes)) return fail(MOSFHET_HIP_EINVAL, "%s: %s overlaps d_exp", who, name);
   }
   HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t s = pick(ctx, stream);
@@ -253,7 +253,7 @@ static int client_phase_check(const char *who, mosfhet_hip_ctx_t ctx, mosfhet_hi
   if (count == 0) return MOSFHET_HIP_OK;
   if (!d_out) return fail(MOSFHET_HIP_EINVAL, "%s: null d_out", who);
   if (!d_in) return fail(MOSFHET_HIP_EINVAL, "%s: null d_in", who);
-  if (ram_ranges_meet(d_out, (size_t)count * out_words * sizeof(uint64_t), d_in, (size_t)count * in_words * sizeof(uint64_t)))
+  if (ranges_overlap(d_out, (size_t)count * out_words * sizeof(uint64_t), d_in, (size_t)count * in_words * sizeof(uint64_t)))
     return fail(MOSFHET_HIP_EINVAL, "%s: d_out overlaps d_in", who);
   return MOSFHET_HIP_OK;
 }

@@ -1047,8 +1047,7 @@ extern "C" int mosfhet_hip_keyswitch_functional_bootstrap_batch(mosfhet_hip_ctx_
                                                                 const uint64_t *d_tv, int tv_count, const uint64_t *d_in, int count, int torus_base, int extract,
                                                                 void *stream) {
   if (!ctx || !ksk || !bsk || count < 0) return fail(MOSFHET_HIP_EINVAL, "keyswitch_bootstrap: bad argument");
-  if (ksk->n_in != bsk->k * bsk->N || ksk->n_out != bsk->n || ksk->b_word != ksk->n_out)
-    return fail(MOSFHET_HIP_EINVAL, "keyswitch_bootstrap: key-switch key is %d -> %d, expected %d -> %d", ksk->n_in, ksk->n_out, bsk->k * bsk->N, bsk->n);
+  if (int rk = ks_bootstrap_keys_match("keyswitch_bootstrap", ksk, bsk)) return rk;
   if (count == 0) return MOSFHET_HIP_OK;
   HIP_TRY(hipSetDevice(ctx->device));
   uint64_t *tmp = nullptr;

@@ -12,21 +12,13 @@
 // second-level list of ceil(entries / LINEAR_CHUNK) > LINEAR_CHUNK staging rows, walked by one wavefront (1 / LINEAR_CHUNK of the row's work).  The staging rows [count][parts][n + 1] live in the calling thread's pool (slot POOL_LINEAR), as
 // every temporary of this library: a call neither allocates per call nor synchronises, and is capturable on its one stream once a call of the same size has
 // grown the pool.
-struct mosfhet_hip_linear {
-  mosfhet_hip_ctx_t ctx = nullptr;   // compared, never read: the context may already be destroyed when the handle is freed or cloned
-  int device = 0;
+struct LinearShape {
   int rows_out = 0, rows_in = 0, narrow = 0, sparse = 0, has_bias = 0;
   long long nnz = -1;
   int lists = 0, entries = 0;        // sparse, first level: lists (rows and chunks of cut rows) and their entries
   int parts = 0, lists2 = 0, entries2 = 0;   // second level: staging rows, cut rows, entries (= parts)
-  size_t off[10] = {}, bytes = 0;    // offsets of the arrays in the one device image
-  char *d = nullptr;
-  ~mosfhet_hip_linear() {
-    if (ctx) (void)hipSetDevice(device);
-    if (d) (void)hipFree(d);
-  }
-  template <class T> const T *at(int k) const { return reinterpret_cast<const T *>(d + off[k]); }
 };
+struct mosfhet_hip_linear : LinearImage, LinearShape { using Shape = LinearShape; };   // the image and its clone: capi_linear_common.inc
 enum { LIN_W = 0, LIN_BIAS, LIN_PTR, LIN_COL, LIN_VAL, LIN_DST, LIN_PTR2, LIN_COL2, LIN_VAL2, LIN_DST2 };
 
 struct LinearPlan { int sparse, wide; unsigned strips, tiles, units, workgroups, gx, gy; long long passes, bytes; };
@@ -81,16 +73,13 @@ static bool linear_is_narrow(const int64_t *v, size_t count) {
   return true;
 }
 
-// lays the arrays out in one image (16-byte aligned each), uploads it
-static int linear_upload(mosfhet_hip_linear *h, const void *const *src, const size_t *len) {
-  size_t total = 0;
-  for (int k = 0; k < 10; k++) { h->off[k] = total; total += (len[k] + 15) & ~(size_t)15; }
-  std::vector<char> image(total ? total : 16, 0);
+// the image, put together on the host (the padding zero) and uploaded in one copy
+static int linear_upload(mosfhet_hip_linear *h, mosfhet_hip_ctx_t ctx, const void *const *src, const size_t *len) {
+  const int rc = image_alloc(h, ctx, len, 10);
+  if (rc) return rc;
+  std::vector<char> image(h->bytes, 0);
   for (int k = 0; k < 10; k++)
     if (len[k]) memcpy(image.data() + h->off[k], src[k], len[k]);
-  h->bytes = image.size();
-  HIP_TRY(hipSetDevice(h->device));
-  HIP_TRY(hipMalloc((void **)&h->d, h->bytes));
   HIP_TRY(hipMemcpy(h->d, image.data(), h->bytes, hipMemcpyHostToDevice));
   return MOSFHET_HIP_OK;
 }
@@ -102,7 +91,7 @@ extern "C" int mosfhet_hip_linear_create_dense(mosfhet_hip_ctx_t ctx, mosfhet_hi
   const size_t tiles = ((size_t)rows_out + LINEAR_TJ - 1) / LINEAR_TJ;
   if (tiles * (size_t)rows_in > (size_t)0x7fffffff / LINEAR_TJ) return fail(MOSFHET_HIP_EINVAL, "linear_create_dense: rows_out = %d x rows_in = %d weights do not fit 2^31", rows_out, rows_in);
   std::unique_ptr<mosfhet_hip_linear> h(new mosfhet_hip_linear());
-  h->ctx = ctx; h->device = ctx->device; h->rows_out = rows_out; h->rows_in = rows_in; h->has_bias = h_bias != nullptr;
+  h->rows_out = rows_out; h->rows_in = rows_in; h->has_bias = h_bias != nullptr;
   h->narrow = linear_is_narrow(h_W, (size_t)rows_out * rows_in);
   h->lists = rows_out;
   std::vector<int64_t> wt(tiles * rows_in * LINEAR_TJ, 0);                    // tile-major: [tile][i][TJ], rows past rows_out stay zero
@@ -110,7 +99,7 @@ extern "C" int mosfhet_hip_linear_create_dense(mosfhet_hip_ctx_t ctx, mosfhet_hi
     for (int i = 0; i < rows_in; i++) wt[((size_t)(j / LINEAR_TJ) * rows_in + i) * LINEAR_TJ + j % LINEAR_TJ] = h_W[(size_t)j * rows_in + i];
   const void *src[10] = {wt.data(), h_bias};
   size_t len[10] = {wt.size() * sizeof(int64_t), h_bias ? (size_t)rows_out * sizeof(uint64_t) : 0};
-  if ((rc = linear_upload(h.get(), src, len))) return rc;
+  if ((rc = linear_upload(h.get(), ctx, src, len))) return rc;
   *out = h.release();
   return MOSFHET_HIP_OK;
 }
@@ -119,16 +108,11 @@ extern "C" int mosfhet_hip_linear_create_sparse(mosfhet_hip_ctx_t ctx, mosfhet_h
                                                 const uint64_t *h_bias, int rows_out, int rows_in) {
   int rc = linear_shape_checks("linear_create_sparse", ctx, out, rows_out, rows_in);
   if (rc) return rc;
-  if (!h_row_ptr) return fail(MOSFHET_HIP_EINVAL, "linear_create_sparse: null h_row_ptr");
-  if (h_row_ptr[0] != 0) return fail(MOSFHET_HIP_EINVAL, "linear_create_sparse: row_ptr[0] = %d (must be 0)", h_row_ptr[0]);
-  for (int j = 0; j < rows_out; j++)
-    if (h_row_ptr[j + 1] < h_row_ptr[j]) return fail(MOSFHET_HIP_EINVAL, "linear_create_sparse: row_ptr[%d] = %d is below row_ptr[%d] = %d", j + 1, h_row_ptr[j + 1], j, h_row_ptr[j]);
-  const int nnz = h_row_ptr[rows_out];
-  if (nnz && (!h_col || !h_val)) return fail(MOSFHET_HIP_EINVAL, "linear_create_sparse: null h_col or h_val");
-  for (int q = 0; q < nnz; q++)
-    if (h_col[q] < 0 || h_col[q] >= rows_in) return fail(MOSFHET_HIP_EINVAL, "linear_create_sparse: col[%d] = %d (rows_in = %d)", q, h_col[q], rows_in);
+  long long entries;
+  if ((rc = csr_check("linear_create_sparse", h_row_ptr, h_col, rows_out, rows_in, !h_col || !h_val ? "h_col or h_val" : nullptr, &entries))) return rc;
+  const int nnz = (int)entries;
   std::unique_ptr<mosfhet_hip_linear> h(new mosfhet_hip_linear());
-  h->ctx = ctx; h->device = ctx->device; h->rows_out = rows_out; h->rows_in = rows_in; h->has_bias = h_bias != nullptr; h->sparse = 1; h->nnz = nnz;
+  h->rows_out = rows_out; h->rows_in = rows_in; h->has_bias = h_bias != nullptr; h->sparse = 1; h->nnz = nnz;
   h->narrow = linear_is_narrow(h_val, (size_t)nnz);
   // first level: a row of at most LINEAR_CHUNK entries is one list written to its output row; a longer one is cut into chunks, one staging row each.  The
   // entries keep their order, so col / val are the caller's arrays as they are.
@@ -149,7 +133,7 @@ extern "C" int mosfhet_hip_linear_create_sparse(mosfhet_hip_ctx_t ctx, mosfhet_h
   const void *src[10] = {nullptr, h_bias, ptr.data(), h_col, h_val, dst.data(), ptr2.data(), col2.data(), val2.data(), dst2.data()};
   size_t len[10] = {0, h_bias ? (size_t)rows_out * sizeof(uint64_t) : 0, ptr.size() * sizeof(int), (size_t)nnz * sizeof(int), (size_t)nnz * sizeof(int64_t), dst.size() * sizeof(int),
                     h->lists2 ? ptr2.size() * sizeof(int) : 0, col2.size() * sizeof(int), val2.size() * sizeof(int64_t), dst2.size() * sizeof(int)};
-  if ((rc = linear_upload(h.get(), src, len))) return rc;
+  if ((rc = linear_upload(h.get(), ctx, src, len))) return rc;
   *out = h.release();
   return MOSFHET_HIP_OK;
 }
@@ -165,24 +149,8 @@ extern "C" int mosfhet_hip_linear_info(mosfhet_hip_linear_t lin, long long info[
   return MOSFHET_HIP_OK;
 }
 
-// after the pattern of mosfhet_hip_ksk_clone: a copy of the handle on the device of ctx_other, device to device
 extern "C" int mosfhet_hip_linear_clone(mosfhet_hip_ctx_t ctx_other, mosfhet_hip_linear_t lin, mosfhet_hip_linear_t *out) {
-  if (!ctx_other) return fail(MOSFHET_HIP_EINVAL, "linear_clone: null ctx_other");
-  if (!lin) return fail(MOSFHET_HIP_EINVAL, "linear_clone: null lin");
-  if (!out) return fail(MOSFHET_HIP_EINVAL, "linear_clone: null out");
-  HIP_TRY(hipSetDevice(lin->device));
-  HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipSetDevice(ctx_other->device));
-  std::unique_ptr<mosfhet_hip_linear> h(new mosfhet_hip_linear());
-  h->ctx = ctx_other; h->device = ctx_other->device;
-  h->rows_out = lin->rows_out; h->rows_in = lin->rows_in; h->narrow = lin->narrow; h->sparse = lin->sparse; h->has_bias = lin->has_bias; h->nnz = lin->nnz;
-  h->lists = lin->lists; h->entries = lin->entries; h->parts = lin->parts; h->lists2 = lin->lists2; h->entries2 = lin->entries2; h->bytes = lin->bytes;
-  memcpy(h->off, lin->off, sizeof(h->off));
-  HIP_TRY(hipMalloc((void **)&h->d, h->bytes));
-  const int rc = copy_across(h->d, ctx_other->device, lin->d, lin->device, h->bytes);
-  if (rc) return rc;
-  *out = h.release();
-  return MOSFHET_HIP_OK;
+  return clone_image("linear_clone", ctx_other, lin, out);
 }
 
 static int linear_launch(const char *who, const LinearParams &p, int n, int count, hipStream_t s) {
@@ -219,11 +187,6 @@ static int linear_run(const char *who, mosfhet_hip_ctx_t ctx, mosfhet_hip_linear
   return linear_launch(who, p, n, count, s);
 }
 
-static bool linear_overlap(const void *a, size_t a_bytes, const void *b, size_t b_bytes) {
-  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-  return a0 < b0 + b_bytes && b0 < a0 + a_bytes;
-}
-
 // Null handles and scalar ranges come before any handle is read and before any HIP call.
 extern "C" int mosfhet_hip_tlwe_linear_batch(mosfhet_hip_ctx_t ctx, mosfhet_hip_linear_t lin, uint64_t *d_out, const uint64_t *d_in, int n, int count, void *stream) {
   const char *who = "tlwe_linear";
@@ -238,7 +201,7 @@ extern "C" int mosfhet_hip_tlwe_linear_batch(mosfhet_hip_ctx_t ctx, mosfhet_hip_
   int rc = linear_plan(who, lin->rows_out, lin->rows_in, lin->nnz, lin->narrow, n, count, 256, &plan);   // the size limits, on the whole call
   if (rc) return rc;
   const size_t row = ((size_t)n + 1) * sizeof(uint64_t);
-  if (linear_overlap(d_out, (size_t)count * lin->rows_out * row, d_in, (size_t)count * lin->rows_in * row))
+  if (ranges_overlap(d_out, (size_t)count * lin->rows_out * row, d_in, (size_t)count * lin->rows_in * row))
     return fail(MOSFHET_HIP_EINVAL, "%s: d_out overlaps d_in", who);
   HIP_TRY(hipSetDevice(ctx->device));
   return linear_run(who, ctx, lin, d_out, d_in, n, count, pick(ctx, stream));
@@ -261,14 +224,13 @@ extern "C" int mosfhet_hip_linear_keyswitch_functional_bootstrap_batch(mosfhet_h
   if (!d_out || !d_tv || !d_in) return fail(MOSFHET_HIP_EINVAL, "%s: null buffer", who);
   if (lin->ctx != ctx) return fail(MOSFHET_HIP_EINVAL, "%s: lin belongs to another context (device %d): mosfhet_hip_linear_clone makes a copy for this one", who, lin->device);
   // the checks of the body below on the two keys, BEFORE the linear kernel is queued: it reads ksk->n_in + 1 words per input sample
-  if (ksk->n_in != bsk->k * bsk->N || ksk->n_out != bsk->n || ksk->b_word != ksk->n_out)
-    return fail(MOSFHET_HIP_EINVAL, "%s: key-switch key is %d -> %d, expected %d -> %d", who, ksk->n_in, ksk->n_out, bsk->k * bsk->N, bsk->n);
+  int rc = ks_bootstrap_keys_match(who, ksk, bsk);
+  if (rc) return rc;
   const int n = ksk->n_in;
-  const long long samples = (long long)count * lin->rows_out;
-  if (samples > 0x7fffffffLL) return fail(MOSFHET_HIP_EINVAL, "%s: count = %d x rows_out = %d samples do not fit an int", who, count, lin->rows_out);
-  if (tv_count != 1 && tv_count != samples) return fail(MOSFHET_HIP_EINVAL, "%s: tv_count = %d (1 or count * rows_out = %lld)", who, tv_count, samples);
+  long long samples;
+  if ((rc = ks_bootstrap_samples(who, count, lin->rows_out, 0, tv_count, &samples))) return rc;
   LinearPlan plan;
-  int rc = linear_plan(who, lin->rows_out, lin->rows_in, lin->nnz, lin->narrow, n, count, 256, &plan);
+  rc = linear_plan(who, lin->rows_out, lin->rows_in, lin->nnz, lin->narrow, n, count, 256, &plan);
   if (rc) return rc;
   HIP_TRY(hipSetDevice(ctx->device));
   uint64_t *y = nullptr;

@@ -117,7 +117,7 @@ extern "C" int mosfhet_hip_tlwe_pack_batch(mosfhet_hip_ctx_t ctx, mosfhet_hip_ga
   PackPlan plan;
   int rc = pack_plan(who, pk->N, pk->entries, pk->t, total, per, split, 256, 0, &plan);   // the ring, per <= N, split <= n_in, the size limits
   if (rc) return rc;
-  if (linear_overlap(d_out, (size_t)plan.outputs * 2 * pk->N * sizeof(uint64_t), d_in, (size_t)total * ((size_t)pk->entries + 1) * sizeof(uint64_t)))
+  if (ranges_overlap(d_out, (size_t)plan.outputs * 2 * pk->N * sizeof(uint64_t), d_in, (size_t)total * ((size_t)pk->entries + 1) * sizeof(uint64_t)))
     return fail(MOSFHET_HIP_EINVAL, "%s: d_out overlaps d_in", who);
   HIP_TRY(hipSetDevice(ctx->device));
   PackParams p = {};

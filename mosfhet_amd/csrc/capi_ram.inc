@@ -49,12 +49,6 @@ extern "C" int mosfhet_hip_trlwe_ram_plan(int N, int l, int size, int count, int
   return MOSFHET_HIP_OK;
 }
 
-// do the address ranges [a, a + a_bytes) and [b, b + b_bytes) meet?
-static bool ram_ranges_meet(const void *a, size_t a_bytes, const void *b, size_t b_bytes) {
-  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-  return a0 < b0 + b_bytes && b0 < a0 + a_bytes;
-}
-
 // Argument checks of both calls, before any HIP call.  `other` is d_out (read) or d_val (write): [count][2][N] words.
 static int ram_check(const char *who, const char *other_name, mosfhet_hip_ctx_t ctx, const void *other, const double *d_sel_dft, const uint64_t *d_mem, int size, int N,
                      int l, int Bg_bit, int count, int write, RamPlan *plan) {
@@ -68,7 +62,7 @@ static int ram_check(const char *who, const char *other_name, mosfhet_hip_ctx_t 
   if (!d_sel_dft) return fail(MOSFHET_HIP_EINVAL, "%s: null d_sel_dft", who);
   if (!d_mem) return fail(MOSFHET_HIP_EINVAL, "%s: null d_mem", who);
   const size_t sample = (size_t)2 * N * sizeof(uint64_t);
-  if (ram_ranges_meet(other, (size_t)count * sample, d_mem, ((size_t)count << size) * sample))
+  if (ranges_overlap(other, (size_t)count * sample, d_mem, ((size_t)count << size) * sample))
     return fail(MOSFHET_HIP_EINVAL, "%s: %s overlaps d_mem", who, other_name);
   return MOSFHET_HIP_OK;
 }

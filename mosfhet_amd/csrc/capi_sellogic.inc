@@ -133,7 +133,7 @@ extern "C" int mosfhet_hip_trgsw_logic_batch(mosfhet_hip_ctx_t ctx, double *d_ou
   if (!d_out_dft) return fail(MOSFHET_HIP_EINVAL, "%s: null d_out_dft", who);
   if (!d_in_dft) return fail(MOSFHET_HIP_EINVAL, "%s: null d_in_dft", who);
   const size_t sample = (size_t)2 * l * 2 * N * sizeof(double);   // bytes of one TRGSW_DFT sample
-  if (ram_ranges_meet(d_out_dft, (size_t)count * c->n_gates * sample, d_in_dft, (size_t)count * c->n_in * sample))
+  if (ranges_overlap(d_out_dft, (size_t)count * c->n_gates * sample, d_in_dft, (size_t)count * c->n_in * sample))
     return fail(MOSFHET_HIP_EINVAL, "%s: d_out_dft overlaps d_in_dft", who);
   HIP_TRY(hipSetDevice(ctx->device));
   const SelGate *image = nullptr;

@@ -79,7 +79,7 @@ extern "C" int mosfhet_hip_tlwe_trace_pack_batch(mosfhet_hip_ctx_t ctx, mosfhet_
   const int rc = trace_check(who, TRACE_KIND_PACK, ctx, tks, entry0, d_out, d_in, 0, count, &run);
   if (rc || !run) return rc;
   const int N = tks->N;
-  if (linear_overlap(d_out, (size_t)count * 2 * N * sizeof(uint64_t), d_in, (size_t)count * ((size_t)N + 1) * sizeof(uint64_t)))
+  if (ranges_overlap(d_out, (size_t)count * 2 * N * sizeof(uint64_t), d_in, (size_t)count * ((size_t)N + 1) * sizeof(uint64_t)))
     return fail(MOSFHET_HIP_EINVAL, "%s: d_out overlaps d_in", who);
   HIP_TRY(hipSetDevice(ctx->device));
   return launch_trace(ctx, tks, TRACE_KIND_PACK, entry0, d_in, d_out, nullptr, 1, (unsigned)count, pick(ctx, stream));
@@ -150,7 +150,7 @@ extern "C" int mosfhet_hip_tlwe_trace_pack_many_batch(mosfhet_hip_ctx_t ctx, mos
   int rc = trace_many_plan(who, tks->N, tks->t, tks->base_bit, tks->entries, entry0, total, log_per, 0, &plan);
   if (rc) return rc;
   const int N = tks->N;
-  if (linear_overlap(d_out, (size_t)plan.outputs * 2 * N * sizeof(uint64_t), d_in, (size_t)total * ((size_t)N + 1) * sizeof(uint64_t)))
+  if (ranges_overlap(d_out, (size_t)plan.outputs * 2 * N * sizeof(uint64_t), d_in, (size_t)total * ((size_t)N + 1) * sizeof(uint64_t)))
     return fail(MOSFHET_HIP_EINVAL, "%s: d_out overlaps d_in", who);
   HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t s = pick(ctx, stream);
@@ -184,7 +184,7 @@ extern "C" int mosfhet_hip_trlwe_rlwe_priv_keyswitch_batch(mosfhet_hip_ctx_t ctx
   const int rc = trace_check(who, TRACE_KIND_PRIV, ctx, tks, entry0, d_out, d_in, 0, count, &run);
   if (rc || !run) return rc;
   const size_t bytes = (size_t)count * 2 * tks->N * sizeof(uint64_t);
-  if (d_out != d_in && linear_overlap(d_out, bytes, d_in, bytes)) return fail(MOSFHET_HIP_EINVAL, "%s: d_out overlaps d_in without being d_in (in place is fine, a shifted overlap is not)", who);
+  if (d_out != d_in && ranges_overlap(d_out, bytes, d_in, bytes)) return fail(MOSFHET_HIP_EINVAL, "%s: d_out overlaps d_in without being d_in (in place is fine, a shifted overlap is not)", who);
   HIP_TRY(hipSetDevice(ctx->device));
   return launch_trace(ctx, tks, TRACE_KIND_PRIV, entry0, d_in, d_out, nullptr, 1, (unsigned)count, pick(ctx, stream));
 }
@@ -195,7 +195,7 @@ extern "C" int mosfhet_hip_trgsw_from_gadget_batch(mosfhet_hip_ctx_t ctx, mosfhe
   const int rc = trace_check(who, TRACE_KIND_GADGET, ctx, tks, entry0, d_out_dft, d_gadget, l, count, &run);
   if (rc || !run) return rc;
   const size_t in_bytes = (size_t)count * l * 2 * tks->N * sizeof(uint64_t);
-  if (linear_overlap(d_out_dft, 2 * in_bytes, d_gadget, in_bytes)) return fail(MOSFHET_HIP_EINVAL, "%s: d_out_dft overlaps d_gadget", who);
+  if (ranges_overlap(d_out_dft, 2 * in_bytes, d_gadget, in_bytes)) return fail(MOSFHET_HIP_EINVAL, "%s: d_out_dft overlaps d_gadget", who);
   HIP_TRY(hipSetDevice(ctx->device));
   return launch_trace(ctx, tks, TRACE_KIND_GADGET, entry0, d_gadget, nullptr, (d2 *)d_out_dft, l, (unsigned)count * (unsigned)l, pick(ctx, stream));
 }

@@ -115,7 +115,7 @@ static int trlwe_unpack_body(const char *who, mosfhet_hip_ctx_t ctx, uint64_t *d
   if (rc) return rc;
   if (total == 0) return MOSFHET_HIP_OK;
   if (!d_out || !d_in) return fail(MOSFHET_HIP_EINVAL, "%s: null buffer", who);
-  if (linear_overlap(d_out, (size_t)total * ((size_t)N + 1) * sizeof(uint64_t), d_in, (size_t)plan.outputs * 2 * N * sizeof(uint64_t)))
+  if (ranges_overlap(d_out, (size_t)total * ((size_t)N + 1) * sizeof(uint64_t), d_in, (size_t)plan.outputs * 2 * N * sizeof(uint64_t)))
     return fail(MOSFHET_HIP_EINVAL, "%s: d_out overlaps d_in", who);
   HIP_TRY(hipSetDevice(ctx->device));
   return launch_trlwe_unpack(d_out, d_in, N, total, per, first, stride, unpack_rows(plan.outputs, per, ksw_device_cus()), pick(ctx, stream));
@@ -148,7 +148,7 @@ static int unpack_keyswitch_check(const char *who, mosfhet_hip_ctx_t ctx, mosfhe
   HIP_TRY(hipSetDevice(ctx->device));
   const int rc = unpack_plan(who, ksk->n_in, ksk->n_out, ksk->t, ksk->base_bit, ksk->compressed, total, per, first, stride, ksw_device_cus(), plan);   // per <= N = n_in, the geometry, the size limits
   if (rc) return rc;
-  if (linear_overlap(d_out, (size_t)total * out_row * sizeof(uint64_t), d_in, (size_t)plan->outputs * 2 * ksk->n_in * sizeof(uint64_t)))
+  if (ranges_overlap(d_out, (size_t)total * out_row * sizeof(uint64_t), d_in, (size_t)plan->outputs * 2 * ksk->n_in * sizeof(uint64_t)))
     return fail(MOSFHET_HIP_EINVAL, "%s: d_out overlaps d_in", who);
   return MOSFHET_HIP_OK;
 }
@@ -199,8 +199,7 @@ static int unpack_keyswitch_bootstrap_body(const char *who, mosfhet_hip_ctx_t ct
   if (!ctx) return fail(MOSFHET_HIP_EINVAL, "%s: null ctx", who);
   if (!ksk || !bsk) return fail(MOSFHET_HIP_EINVAL, "%s: null key", who);
   if (int rs = unpack_scalars(who, total, per, first, stride)) return rs;
-  if (ksk->n_in != bsk->k * bsk->N || ksk->n_out != bsk->n || ksk->b_word != ksk->n_out)
-    return fail(MOSFHET_HIP_EINVAL, "%s: key-switch key is %d -> %d, expected %d -> %d", who, ksk->n_in, ksk->n_out, bsk->k * bsk->N, bsk->n);
+  if (int rk = ks_bootstrap_keys_match(who, ksk, bsk)) return rk;
   if (bsk->k != 1) return fail(MOSFHET_HIP_EINVAL, "%s: packed inputs have one mask polynomial (k = 1), the bootstrap key has k = %d", who, bsk->k);
   if (total == 0) return MOSFHET_HIP_OK;
   UnpackPlan plan;

@@ -161,9 +161,22 @@ def trlwe_automaton_plan(N, l, states, layers, steps, count, start=-1, cus=256):
     return dict(launches=int(plan[0]), chunk=int(plan[1]), workspace_bytes=int(plan[2]), products=int(plan[3]), buffers=int(plan[4]))
 
 
-class Automaton:
+class _Handle:
+    """What the handle classes share: self.h is the native handle, _destroy the symbol that gives it back."""
+    _destroy = None
+
+    def close(self):
+        if self.h:
+            getattr(lib(), self._destroy)(self.h)
+            self.h = None
+
+    free = close
+
+
+class Automaton(_Handle):
     """The transition tables of a deterministic weighted automaton / layered branching program (mosfhet_hip_automaton_t): made by automaton_create or
     Engine.automaton_create, shared by every call and batch that runs it."""
+    _destroy = "mosfhet_hip_automaton_destroy"
 
     def __init__(self, handle):
         self.h = handle
@@ -173,13 +186,6 @@ class Automaton:
 
     def info(self):
         return dict(N=self.N, states=self.states, layers=self.layers)
-
-    def close(self):
-        if self.h:
-            lib().mosfhet_hip_automaton_destroy(self.h)
-            self.h = None
-
-    free = close
 
 
 def automaton_create(next0, next1, rot0, rot1, N):
@@ -206,8 +212,9 @@ def trgsw_logic_plan(N, l, n_in, n_gates, levels, widest_level, count, cus=256):
     return dict(launches=int(plan[0]), teams=int(plan[1]), products=int(plan[2]), inverses=int(plan[3]), forwards=int(plan[4]))
 
 
-class SelLogic:
+class SelLogic(_Handle):
     """A circuit of gates over TRGSW_DFT selectors (mosfhet_hip_sellogic_t): made by sellogic_create or Engine.sellogic_create, shared by every call and batch."""
+    _destroy = "mosfhet_hip_sellogic_destroy"
 
     def __init__(self, handle):
         self.h = handle
@@ -217,13 +224,6 @@ class SelLogic:
 
     def info(self):
         return dict(N=self.N, n_in=self.n_in, n_gates=self.n_gates, levels=self.levels, product_gates=self.product_gates)
-
-    def close(self):
-        if self.h:
-            lib().mosfhet_hip_sellogic_destroy(self.h)
-            self.h = None
-
-    free = close
 
 
 def sellogic_create(gates, n_in, N):
@@ -249,8 +249,9 @@ def trgsw_encrypt_plan(N, l, count, outputs="dft"):
     return dict(launches=int(info[0]), workgroups=int(info[1]), workspace_bytes=int(info[2]), chunks=int(info[3]))
 
 
-class ClientKey:
+class ClientKey(_Handle):
     """Secret keys for the encrypt and phase calls (mosfhet_hip_client_key_t): made by client_key_create, shared by every engine, call and host thread."""
+    _destroy = "mosfhet_hip_client_key_destroy"
 
     def __init__(self, handle):
         self.h = handle
@@ -261,13 +262,6 @@ class ClientKey:
 
     def info(self):
         return dict(N=self.N, n=self.n, rlwe_weight=self.rlwe_weight, rlwe_binary=self.rlwe_binary, lwe_weight=self.lwe_weight, lwe_binary=self.lwe_binary)
-
-    def close(self):
-        if self.h:
-            lib().mosfhet_hip_client_key_destroy(self.h)
-            self.h = None
-
-    free = close
 
 
 def client_key_create(s_rlwe=None, s_lwe=None):
@@ -391,9 +385,10 @@ def trlwe_linear_plan(N, rows_out, rows_in, count, nnz=-1, extract=False, cus=25
                 weight_bytes=int(plan[6]), input_bytes=int(plan[7]))
 
 
-class PolyLinearMap:
+class PolyLinearMap(_Handle):
     """The cleartext polynomial weights of y = W x + bias on packed TRLWE samples, transformed, on the device (mosfhet_hip_polylinear_t): made by
     Engine.polylinear_create_dense / Engine.polylinear_create_sparse."""
+    _destroy = "mosfhet_hip_polylinear_destroy"
 
     def __init__(self, engine, handle):
         self.engine, self.h = engine, handle
@@ -404,13 +399,6 @@ class PolyLinearMap:
         v = (C.c_longlong * 6)()
         _check(lib().mosfhet_hip_polylinear_info(self.h, v))
         return dict(rows_out=int(v[0]), rows_in=int(v[1]), nnz=int(v[2]), N=int(v[3]), nbytes=int(v[4]), form=("dense", "sparse")[v[5]])
-
-    def close(self):
-        if self.h:
-            lib().mosfhet_hip_polylinear_destroy(self.h)
-            self.h = None
-
-    free = close
 
 
 def trlwe_gsw_linear_plan(N, l, rows_out, rows_in, count, nnz=-1, extract=False, cus=256, workspace_bytes=0):
@@ -425,9 +413,10 @@ def trlwe_gsw_linear_plan(N, l, rows_out, rows_in, count, nnz=-1, extract=False,
                 weight_bytes=int(plan[6]), digit_bytes=int(plan[7]))
 
 
-class GswLinearMap:
+class GswLinearMap(_Handle):
     """The encrypted polynomial weights (TRGSW_DFT samples) of y = W x + bias on packed TRLWE samples, on the device (mosfhet_hip_gswlinear_t): made by
     Engine.gswlinear_create_dense / _sparse / _from_selectors."""
+    _destroy = "mosfhet_hip_gswlinear_destroy"
 
     def __init__(self, engine, handle):
         self.engine, self.h = engine, handle
@@ -440,16 +429,10 @@ class GswLinearMap:
         return dict(rows_out=int(v[0]), rows_in=int(v[1]), nnz=int(v[2]), N=int(v[3]), l=int(v[4]), Bg_bit=int(v[5]), nbytes=int(v[6]),
                     form=("dense", "sparse", "selectors")[v[7]])
 
-    def close(self):
-        if self.h:
-            lib().mosfhet_hip_gswlinear_destroy(self.h)
-            self.h = None
 
-    free = close
-
-
-class LinearMap:
+class LinearMap(_Handle):
     """The cleartext weights of y = W x + bias on the device (mosfhet_hip_linear_t): made by Engine.linear_dense / Engine.linear_sparse."""
+    _destroy = "mosfhet_hip_linear_destroy"
 
     def __init__(self, engine, handle):
         self.engine, self.h = engine, handle
@@ -460,13 +443,6 @@ class LinearMap:
         v = (C.c_longlong * 6)()
         _check(lib().mosfhet_hip_linear_info(self.h, v))
         return dict(rows_out=int(v[0]), rows_in=int(v[1]), nnz=int(v[2]), narrow=bool(v[3]), nbytes=int(v[4]), form=("dense", "sparse")[v[5]])
-
-    def close(self):
-        if self.h:
-            lib().mosfhet_hip_linear_destroy(self.h)
-            self.h = None
-
-    free = close
 
 
 class BootstrapKey:
@@ -1340,29 +1316,41 @@ class Engine:
 
     # ---- cleartext-weight linear layers (include/mosfhet_hip.h: mosfhet_hip_linear_*, mosfhet_hip_tlwe_linear_batch) ----
     @staticmethod
-    def _bias(bias, rows_out):
+    def _bias(bias, shape):
+        """(the array to keep alive, its pointer) of a bias of `shape`: (rows_out,) torus words, or (rows_out, N) for the layers on packed samples"""
         if bias is None:
             return None, None
         b = np.ascontiguousarray(np.asarray(bias).astype(np.uint64, copy=False))
-        assert b.shape == (rows_out,), "bias: one torus word per output row"
+        assert b.shape == tuple(shape), "bias: one %s per output row" % ("torus word" if len(shape) == 1 else "polynomial of N torus words")
         return b, b.ctypes.data_as(C.c_void_p)
+
+    @staticmethod
+    def _csr(row_ptr, col, n_entries):
+        """(row_ptr, col, rows_out) of a sparse creator: the lists as contiguous int32, one column per entry and no fewer entries than row_ptr names"""
+        row_ptr, col = np.ascontiguousarray(row_ptr, dtype=np.int32), np.ascontiguousarray(col, dtype=np.int32)
+        rows_out = len(row_ptr) - 1
+        assert len(col) == n_entries and (rows_out < 0 or len(col) >= row_ptr[-1])
+        return row_ptr, col, rows_out
+
+    def _clone(self, symbol, cls, lin):
+        h = C.c_void_p()
+        _check(getattr(lib(), symbol)(self.h, lin.h, C.byref(h)))
+        return cls(self, h)
 
     def linear_dense(self, W, bias=None):
         """Handle of a dense layer: W [rows_out][rows_in] int64 (the multipliers tlwe_scale takes), bias [rows_out] torus words or None."""
         W = np.ascontiguousarray(W, dtype=np.int64)
         assert W.ndim == 2
-        keep, pb = self._bias(bias, W.shape[0])
+        keep, pb = self._bias(bias, (W.shape[0],))
         h = C.c_void_p()
         _check(lib().mosfhet_hip_linear_create_dense(self.h, C.byref(h), W.ctypes.data_as(C.c_void_p), pb, int(W.shape[0]), int(W.shape[1])))
         return LinearMap(self, h)
 
     def linear_sparse(self, row_ptr, col, val, rows_in, bias=None):
         """Handle of a sparse map in CSR: row_ptr [rows_out + 1], col / val [nnz] (columns may be unsorted or repeat within a row; rows may be empty)."""
-        row_ptr = np.ascontiguousarray(row_ptr, dtype=np.int32)
-        col, val = np.ascontiguousarray(col, dtype=np.int32), np.ascontiguousarray(val, dtype=np.int64)
-        rows_out = len(row_ptr) - 1
-        assert len(col) == len(val) and (rows_out < 0 or len(col) >= row_ptr[-1])
-        keep, pb = self._bias(bias, rows_out)
+        val = np.ascontiguousarray(val, dtype=np.int64)
+        row_ptr, col, rows_out = self._csr(row_ptr, col, len(val))
+        keep, pb = self._bias(bias, (rows_out,))
         h = C.c_void_p()
         _check(lib().mosfhet_hip_linear_create_sparse(self.h, C.byref(h), row_ptr.ctypes.data_as(C.c_void_p), col.ctypes.data_as(C.c_void_p),
                                                       val.ctypes.data_as(C.c_void_p), pb, int(rows_out), int(rows_in)))
@@ -1370,9 +1358,7 @@ class Engine:
 
     def clone_linear(self, lin):
         """A copy of a LinearMap of another engine for this one (mosfhet_hip_linear_clone)."""
-        h = C.c_void_p()
-        _check(lib().mosfhet_hip_linear_clone(self.h, lin.h, C.byref(h)))
-        return LinearMap(self, h)
+        return self._clone("mosfhet_hip_linear_clone", LinearMap, lin)
 
     def tlwe_linear(self, lin, ct, out=None):
         """out[b][j] = (0, bias[j]) + sum_i W[j][i] ct[b][i]: ct [count][rows_in][n + 1] -> [count][rows_out][n + 1], exact mod 2^64."""
@@ -1393,19 +1379,11 @@ class Engine:
         return out
 
     # ---- cleartext polynomial-weight linear layers on packed TRLWE samples (include/mosfhet_hip.h: mosfhet_hip_polylinear_*, mosfhet_hip_trlwe_linear_batch) ----
-    @staticmethod
-    def _poly_bias(bias, rows_out, N):
-        if bias is None:
-            return None, None
-        b = np.ascontiguousarray(np.asarray(bias).astype(np.uint64, copy=False))
-        assert b.shape == (rows_out, N), "bias: one polynomial of N torus words per output row"
-        return b, b.ctypes.data_as(C.c_void_p)
-
     def polylinear_create_dense(self, W, bias=None):
         """Handle of a dense layer: W [rows_out][rows_in][N] int64 coefficients of the cleartext weight polynomials, bias [rows_out][N] torus words or None."""
         W = np.ascontiguousarray(W, dtype=np.int64)
         assert W.ndim == 3
-        keep, pb = self._poly_bias(bias, W.shape[0], W.shape[2])
+        keep, pb = self._bias(bias, (W.shape[0], W.shape[2]))
         h = C.c_void_p()
         _check(lib().mosfhet_hip_polylinear_create_dense(self.h, C.byref(h), W.ctypes.data_as(C.c_void_p), pb, int(W.shape[0]), int(W.shape[1]), int(W.shape[2])))
         return PolyLinearMap(self, h)
@@ -1413,11 +1391,9 @@ class Engine:
     def polylinear_create_sparse(self, row_ptr, col, val, rows_in, N, bias=None):
         """Handle of a sparse map in CSR over polynomial blocks: row_ptr [rows_out + 1], col [nnz], val [nnz][N] (columns may be unsorted or repeat within a row --
         they add in the stored order; rows may be empty)."""
-        row_ptr = np.ascontiguousarray(row_ptr, dtype=np.int32)
-        col, val = np.ascontiguousarray(col, dtype=np.int32), np.ascontiguousarray(val, dtype=np.int64).reshape(-1, int(N))
-        rows_out = len(row_ptr) - 1
-        assert len(col) == len(val) and (rows_out < 0 or len(col) >= row_ptr[-1])
-        keep, pb = self._poly_bias(bias, rows_out, int(N))
+        val = np.ascontiguousarray(val, dtype=np.int64).reshape(-1, int(N))
+        row_ptr, col, rows_out = self._csr(row_ptr, col, len(val))
+        keep, pb = self._bias(bias, (rows_out, int(N)))
         h = C.c_void_p()
         _check(lib().mosfhet_hip_polylinear_create_sparse(self.h, C.byref(h), row_ptr.ctypes.data_as(C.c_void_p), col.ctypes.data_as(C.c_void_p),
                                                           val.ctypes.data_as(C.c_void_p), pb, int(rows_out), int(rows_in), int(N)))
@@ -1425,9 +1401,7 @@ class Engine:
 
     def clone_polylinear(self, lin):
         """A copy of a PolyLinearMap of another engine for this one (mosfhet_hip_polylinear_clone)."""
-        h = C.c_void_p()
-        _check(lib().mosfhet_hip_polylinear_clone(self.h, lin.h, C.byref(h)))
-        return PolyLinearMap(self, h)
+        return self._clone("mosfhet_hip_polylinear_clone", PolyLinearMap, lin)
 
     def trlwe_linear(self, lin, ct, out=None):
         """out[b][j] = (0, bias[j]) + sum_e ct[b][col_e] * val_e, negacyclic products through the transform in the stored order: ct [count][rows_in][2][N] ->
@@ -1461,7 +1435,7 @@ class Engine:
         """Handle of a dense layer: W [rows_out][rows_in][2l][2][N] torus words (TRGSW samples), bias [rows_out][N] torus words or None."""
         W = np.ascontiguousarray(np.asarray(W).astype(np.uint64, copy=False))
         assert W.ndim == 5 and W.shape[3] == 2 and W.shape[2] % 2 == 0
-        keep, pb = self._poly_bias(bias, W.shape[0], W.shape[4])
+        keep, pb = self._bias(bias, (W.shape[0], W.shape[4]))
         h = C.c_void_p()
         _check(lib().mosfhet_hip_gswlinear_create_dense(self.h, C.byref(h), W.ctypes.data_as(C.c_void_p), pb, int(W.shape[0]), int(W.shape[1]), int(W.shape[4]),
                                                         int(W.shape[2] // 2), int(Bg_bit)))
@@ -1470,12 +1444,9 @@ class Engine:
     def gswlinear_create_sparse(self, row_ptr, col, W, rows_in, N, l, Bg_bit, bias=None):
         """Handle of a sparse map in CSR over TRGSW blocks: row_ptr [rows_out + 1], col [nnz], W [nnz][2l][2][N] torus words (columns may be unsorted or repeat
         within a row -- they add in the stored order; rows may be empty)."""
-        row_ptr = np.ascontiguousarray(row_ptr, dtype=np.int32)
-        col = np.ascontiguousarray(col, dtype=np.int32)
         W = np.ascontiguousarray(np.asarray(W).astype(np.uint64, copy=False)).reshape(-1, 2 * int(l), 2, int(N))
-        rows_out = len(row_ptr) - 1
-        assert len(col) == len(W) and (rows_out < 0 or len(col) >= row_ptr[-1])
-        keep, pb = self._poly_bias(bias, rows_out, int(N))
+        row_ptr, col, rows_out = self._csr(row_ptr, col, len(W))
+        keep, pb = self._bias(bias, (rows_out, int(N)))
         h = C.c_void_p()
         _check(lib().mosfhet_hip_gswlinear_create_sparse(self.h, C.byref(h), row_ptr.ctypes.data_as(C.c_void_p), col.ctypes.data_as(C.c_void_p),
                                                          W.ctypes.data_as(C.c_void_p), pb, int(rows_out), int(rows_in), int(N), int(l), int(Bg_bit)))
@@ -1484,12 +1455,10 @@ class Engine:
     def gswlinear_create_from_selectors(self, sel_dft, row_ptr, col, rows_in, Bg_bit, bias=None):
         """The same map over weights already on the device: sel_dft [nnz][2l][2][N] float64 (TRGSW_DFT samples in the engine's slot order, as trgsw_from_gadget,
         circuit_bootstrap_3_dft or torus_to_dft wrote them), copied into the handle."""
-        row_ptr, col = np.ascontiguousarray(row_ptr, dtype=np.int32), np.ascontiguousarray(col, dtype=np.int32)
         nnz, rows, two, N = sel_dft.shape
         assert two == 2 and rows % 2 == 0 and sel_dft.dtype == self.torch.float64 and sel_dft.is_contiguous()
-        rows_out = len(row_ptr) - 1
-        assert len(col) == nnz and (rows_out < 0 or nnz >= row_ptr[-1])
-        keep, pb = self._poly_bias(bias, rows_out, int(N))
+        row_ptr, col, rows_out = self._csr(row_ptr, col, nnz)
+        keep, pb = self._bias(bias, (rows_out, int(N)))
         h = C.c_void_p()
         _check(lib().mosfhet_hip_gswlinear_create_from_selectors(self.h, C.byref(h), _ptr(sel_dft) if nnz else None, row_ptr.ctypes.data_as(C.c_void_p),
                                                                  col.ctypes.data_as(C.c_void_p), pb, int(rows_out), int(rows_in), int(N), int(rows // 2), int(Bg_bit)))
@@ -1497,9 +1466,7 @@ class Engine:
 
     def clone_gswlinear(self, lin):
         """A copy of a GswLinearMap of another engine for this one (mosfhet_hip_gswlinear_clone)."""
-        h = C.c_void_p()
-        _check(lib().mosfhet_hip_gswlinear_clone(self.h, lin.h, C.byref(h)))
-        return GswLinearMap(self, h)
+        return self._clone("mosfhet_hip_gswlinear_clone", GswLinearMap, lin)
 
     def trlwe_gsw_linear(self, lin, ct, out=None):
         """out[b][j] = (0, bias[j]) + sum_e W_e x ct[b][col_e], external products summed in the DFT domain in the stored order and rounded once: ct

@@ -100,6 +100,8 @@ def test_polylinear_symbols_and_argument_checks(native_lib):
     assert x(fake, fake, fake, fake, 0, -2, None) == EINVAL and "count = -2" in err()
     assert x(fake, fake, fake, fake, -1, 1, None) == EINVAL and "idx = -1" in err()
     assert x(fake, fake, fake, fake, -1, 0, None) == EINVAL and "idx = -1" in err()       # ... before count == 0 returns
+    assert x(fake, fake, fake, fake, 0, 0, None) == 0                             # count == 0: nothing to do, no handle read
+    assert x(fake, fake, None, None, 5000, 0, None) == 0                          # ... not even for idx >= N
     g = native_lib.mosfhet_hip_trlwe_linear_keyswitch_functional_bootstrap_batch
     g.argtypes = [C.c_void_p] * 6 + [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
     assert g(None, fake, fake, fake, fake, fake, 1, fake, 0, 1, 4, 1, None) == EINVAL and "ctx" in err()
